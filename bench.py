@@ -2,7 +2,7 @@
 """bench.py — headline benchmark of the LP-relaxation hot path (BASELINE.json `metric`:
 "simplex pivots/sec on 2048x4096 fp64 dense LP; relaxations/sec at 1/2/4/8 GPUs").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload M|C2|C4|C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload M|C2|C4|C3] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     (python bench.py --gpus N without a torchrun environment starts that launcher itself.)
 
@@ -20,6 +20,10 @@ persistent loop kernel k_bt_loop (pivot workgroups + update workgroups in one la
 (64 blocks of 8 pivots: the rank-8 update's pass over the tableau + the pivot workgroups' columns, rows and terms) over the
 HIP-event time of that launch against the HBM peak; `limited_by` names what sets its pace (the pivot chain, not bandwidth); `roofline.loop` does the same with the wall time of the whole pivot loop (launch boundaries and host waits included).  `cpu_baseline` times the CPU oracle (the reference algorithm: 3 fresh LU per pivot) on a
 bounded sample of the same workload on the host cores.
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its caller goes to DIR/<name>.npy (float64):
+at N = 1 the solve's x, z, status and final basis; at N > 1 the whole wave in the children's order (status, z, x, has_x) and the
+incumbent.  The inputs are seeded, so two builds run with the same arguments can be compared array by array.
 """
 from __future__ import annotations
 
@@ -34,7 +38,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X: HBM3E 8.0 TB/s spec
 LOOP_CHUNK = 512       # pivots per launch of the persistent loop kernel: handed to the engine (knob "loop_chunk") AND used by the byte model below
 
 
@@ -64,7 +68,28 @@ def parse_args():
     ap.add_argument("--general", type=int, default=1, help="extra figure: an equality-constrained LP (no slack basis: the findLinearlyIndependent path) (0 = skip)")
     ap.add_argument("--pool-knob", action="append", default=[], help="key=value set on the frontier pools (A/B runs of a schedule knob, e.g. batch_virt=0); recorded in the line")
     ap.add_argument("--c4", type=int, default=1, help="extra figure: one timed solve of the 4096x8192 LP (BASELINE config 4) (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned to its caller "
+                    "as DIR/<name>.npy (float64), so that two builds can be compared output for output on the same seeded inputs")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy in float64 (status codes, indices and bases are exact in float64).  Returns the names."""
+    import numpy as np
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(out)
 
 
 def newest_pmc(kernel_substr):
@@ -239,7 +264,8 @@ def main() -> int:
     # ------------------------------------------------------------------------------------------------------------------
     # the frontier wave (BASELINE config 5): headline for N > 1, `frontier` object of the N = 1 line
     # ------------------------------------------------------------------------------------------------------------------
-    def frontier_leg(steps, warmup, nvars=None, light=False):
+    def frontier_leg(steps, warmup, nvars=None, light=False, keep=None):
+        """keep: a dict that receives the last timed wave under "wave" (this rank's shard results and the incumbent)."""
         nvars = args.frontier_vars if nvars is None else nvars
         m5, seed5 = synth.CONFIGS["C5"]
         c5, A5, b5 = synth.dense_lp_standard_form(m5, seed5)
@@ -299,6 +325,8 @@ def main() -> int:
             acc["fallbacks"] += st["host_fallbacks"]; acc["batched"] += st["batched_relaxations"]
         barrier()
         dt = allmax(time.perf_counter() - t0)
+        if keep is not None:
+            keep["wave"] = wave
         # kernel durations: two more waves with a HIP event pair around every batched launch (outside the timed region: the
         # event records cost ~10 % of a wave)
         pool.set("sample_batch", 1)
@@ -419,7 +447,23 @@ def main() -> int:
     # N > 1: the sharded frontier is the headline
     # ------------------------------------------------------------------------------------------------------------------
     if world > 1:
-        fout, roof, _ = frontier_leg(args.steps, args.warmup)
+        timed = {}
+        fout, roof, _ = frontier_leg(args.steps, args.warmup, keep=timed)
+        dumped = None
+        if args.dump_outputs:
+            # the whole wave as the job returns it: every rank's shard put back in the children's order, and the incumbent
+            w = timed["wave"]
+            shards = [None] * world
+            dist.all_gather_object(shards, (list(w["indices"]), w["status"], w["z"], w["x"], w["has_x"]))
+            if rank == 0:
+                count = sum(len(s[0]) for s in shards)
+                status, z, has_x = np.zeros(count), np.zeros(count), np.zeros(count)
+                x = np.zeros((count, w["x"].shape[1]))
+                for idx, st_, z_, x_, hx in shards:
+                    idx = np.asarray(idx, dtype=np.int64)
+                    status[idx], z[idx], x[idx], has_x[idx] = st_, z_, x_, hx
+                dumped = dump_outputs(args.dump_outputs, {"status": status, "z": z, "x": x, "has_x": has_x,
+                                                          "incumbent_z": [w["incumbent_z"]], "incumbent_index": [w["incumbent_index"]]})
         wide = None
         if args.frontier_wide_vars > args.frontier_vars:
             # second line: a frontier wider than one GPU's 256 CUs (2^11 = 2048 children of the same root), sharded the same way — the
@@ -446,6 +490,8 @@ def main() -> int:
                 "mfma": {"util": 0.0, "why": "no GEMM-shaped step on this path: every relaxation has its own tableau (no shared operand for a batched "
                          "pricing GEMM) and the rank-8 update is HBM-bound at 1 flop/byte (f64 MFMA ridge ~10 flop/byte)"},
             }
+            if dumped is not None:
+                out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
             emit(out)
         dist.barrier()
         dist.destroy_process_group()
@@ -485,6 +531,13 @@ def main() -> int:
         final_host += last.stats["seconds_final_host"]
     barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:
+        # what gomilp_lp_solve_resident hands its caller: x, z, the status and the final basis
+        res = {"x": last.x, "z": [last.z], "status": [last.status]}
+        if last.basis is not None:
+            res["basis"] = last.basis
+        dumped = dump_outputs(args.dump_outputs, res)
     value = pivots / dt
     nn = n - m
     pipeline = last.stats["pipeline"]
@@ -579,6 +632,8 @@ def main() -> int:
         "breakdown": {"pivot_loop_s": loop_s, "final_solve_s": final_s, "final_device_s": final_dev, "final_host_s": final_host, "wall_s": dt,
                       "drift_xb": last.stats["drift_xb"], "z": last.z},
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
 
     # ---- CPU baseline (the oracle = the reference algorithm), bounded sample of the same workload.  Timed LAST (deferred below): 15-25 s
     # of 16 busy host threads in front of the latency-bound GPU legs cost those legs 5-10 % (frontier wave 3.7 -> 4.1 ms on the same box)

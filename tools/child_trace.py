@@ -1,6 +1,6 @@
 """Developer tool: time the children of the C5 wave one by one (1 worker) to see the fixed cost per relaxation.
    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/ct -o ct -- python3 tools/child_trace.py"""
-import sys, time; sys.path.insert(0, '/root/repo')
+import sys, time, os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from gomilp_amd import lp, synth
 m, seed = synth.CONFIGS['C5']

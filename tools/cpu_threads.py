@@ -1,5 +1,5 @@
 """Developer tool: CPU oracle pivots/s at the metric size for several OpenMP thread counts."""
-import sys, time, os; sys.path.insert(0, '/root/repo')
+import sys, time, os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gomilp_amd import synth
 from oracle import oracle as O
 m, seed = synth.CONFIGS['M']

@@ -2,7 +2,7 @@
 set -x
 OUT=gpurun_out/r4n
 mkdir -p $OUT
-cd $GRAFT_REPO_ROOT
+cd "$(dirname "$0")/.."
 export GOMILP_DEBUG_BUILD=1
 : > $OUT/sweep.log
 for cfg in 12 11 10 13; do GOMILP_LUC_SLOTS=$cfg python tools/final_cfg.py M >> $OUT/sweep.log 2>&1 || exit 1; grep -q "Memory access fault" $OUT/sweep.log && exit 3; done

@@ -1,5 +1,5 @@
 """Developer tool: final-solve schedules side by side (bitwise equality + time).  gpurun -- python tools/lu_check.py"""
-import sys; sys.path.insert(0, '/root/repo')
+import sys, os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from gomilp_amd import lp, synth
 for name in ('C3', 'C2', 'M', 'C4'):

@@ -1,5 +1,5 @@
 """Developer tool: the first N pivots of the metric LP (2048x4096) against the CPU oracle (whole solve: 20 min of CPU)."""
-import sys, time; sys.path.insert(0, '/root/repo')
+import sys, time, os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from gomilp_amd import lp, synth
 from oracle import oracle as O

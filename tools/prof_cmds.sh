@@ -3,7 +3,7 @@ set -x
 TAG=${1:-r5}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 cd $R
 HEAD="--no-cpu-baseline --concurrent 0 --milp-nodes 0 --c4 0 --frontier-vars 0 --general 0"

@@ -1,6 +1,6 @@
 """Developer tool: projects the N-GPU time of the C5 frontier wave by solving the N shards of
 frontier.shard_indices one after the other on one GPU."""
-import sys, time; sys.path.insert(0,'/root/repo')
+import sys, time, os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gomilp_amd import lp, synth, frontier
 import numpy as np
 m,seed=512,3

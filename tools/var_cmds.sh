@@ -1,7 +1,7 @@
 set -x
 OUT=gpurun_out/var
 mkdir -p $OUT
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 cd $R
 HEAD="--no-cpu-baseline --concurrent 0 --milp-nodes 0 --c4 0 --frontier-vars 0"
