@@ -1275,8 +1275,17 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
     badly_scaled_ = P.scale_span > 1e9;
     const int nn_max = n + 1 - m;
     // a non-slack starting basis (equality rows, supplied basis) always takes the tableau pipelines: their set-up accepts
-    // any B^-1; the n - m < 2m rule is only the bytes-per-pivot trade-off between the two formulations
-    const bool use_tab = tableau_ && ((n - m) < 2 * m || !unit_basis) && (size_t)tab_ld(nn_max) * sizeof(double) <= 64 * 1024;
+    // any B^-1; the n - m < 2m rule is only the bytes-per-pivot trade-off between the two formulations.  So does a wide LP whose
+    // exact_degenerate mode asks for exact steps on this problem (the predicate of make_bt_args' guard, engine_tableau.cpp) when the
+    // BLOCKED tableau takes it: only the block kernels stop in front of a degenerate pivot (ST_NEED_EXACT) for Engine::exact_step — the
+    // single-kernel tableau and the revised pipelines decide every pivot on their updated quantities.  (tableau = 0 keeps the revised
+    // pipelines, blocked = 0 the n - m < 2m rule, both without the guard: A/B knobs.)
+    const bool tab_fits = (size_t)tab_ld(nn_max) * sizeof(double) <= 64 * 1024;
+    const bool bt_ok = blocked_ && bt_supported(m, nn_max);
+    const bool exact_wanted = exact_degenerate_ == 3 || exact_degenerate_ == 2 || (exact_degenerate_ == 1 && (m <= 256 || !unit_basis || badly_scaled_));
+    const bool use_tab = tableau_ && ((n - m) < 2 * m || !unit_basis || (exact_wanted && bt_ok)) && tab_fits;
+    // strict mode IS the exact steps: where the blocked tableau does not run, the solve refuses instead of deciding the default way
+    if (exact_degenerate_ == 3 && !(use_tab && bt_ok)) return finish(GOMILP_ERR_UNSUPPORTED);
     std::vector<double> xb(m, 0.0), binv_host;
     bool feasible = true;
     if (unit_basis) {
@@ -1331,7 +1340,7 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
 
     // pipeline choice: the explicit tableau moves 16*m*(n-m) bytes per pivot in one launch, the revised form
     // 8*[m(n-m) + 2m^2] in two: the tableau wins while n - m < 2m
-    use_bt_ = use_tab && blocked_ && bt_supported(m, nn_max);
+    use_bt_ = use_tab && bt_ok;
     st->pipeline = use_tab ? (use_bt_ ? 3 : 2) : ((fused_ && fused_supported(P.ld)) ? 1 : 0);
     int loop_rc = GOMILP_OK;
     if (use_tab) {

@@ -94,3 +94,27 @@ def degenerate_integer_milp(seed):
     integ = [bool(v) for v in rng.integers(0, 2, nv)]
     integ[int(rng.integers(0, nv))] = True
     return c, G, h, integ
+
+
+def wide_degenerate_lp(m: int, seed: int, ratio: float = 2.5):
+    """(c, A = [G | I_m], b) of a WIDE integer-data LP, nv = int(ratio * m) structural columns: with n - m >= 2m a slack-basis start
+    takes the revised-simplex pipelines (DESIGN.md §2).  Entries of G in 0..3 (row 0 kept >= 1: every column bounded), m // 4 rows
+    duplicates of earlier rows with equal right-hand sides, b integer in 1..8, c = [-(0..4), 0]: vertices with several basic variables
+    at level zero, ties in the ratio test, Bland steps — and on some seeds the reference's rule cycles (a run of it ends only by a
+    pivot budget)."""
+    rng = np.random.default_rng(8000 + 7919 * m + seed)
+    nv = int(ratio * m)
+    G = rng.integers(0, 4, (m, nv)).astype(float)
+    G[0] = np.maximum(G[0], 1.0)
+    h = rng.integers(1, 9, m).astype(float)
+    ndup = m // 4
+    if ndup:
+        dst = rng.choice(np.arange(1, m), size=ndup, replace=False)
+        keep = np.setdiff1d(np.arange(m), dst)          # duplicates copy rows that are not themselves overwritten
+        src = rng.choice(keep, size=ndup)
+        G[dst], h[dst] = G[src], h[src]
+    c = np.concatenate([-rng.integers(0, 5, nv).astype(float), np.zeros(m)])
+    A = np.zeros((m, nv + m))
+    A[:, :nv] = G
+    A[np.arange(m), nv + np.arange(m)] = 1.0
+    return c, A, h

@@ -125,7 +125,10 @@ int gomilp_ctx_device(const gomilp_ctx *ctx);
  * "exact_degenerate" (0 never, 1 default: bases of up to 256 rows, non-slack starts and badly scaled inputs, 2 always — degenerate,
  * tied and tiny pivots are decided on fresh gonum-order solves; 3 strict: EVERY pivot and the stop test are the
  * reference's iteration on fresh gonum-order solves with its condition guard, simplex.go:233-293 — milliseconds per pivot, the mode that
- * follows the reference wherever the rounding noise of its solves leads), "cond_guard" (1 default: gonum's
+ * follows the reference wherever the rounding noise of its solves leads).  The exact steps exist on the BLOCKED tableau pipeline only: a
+ * wide slack-basis LP (n - m >= 2m) whose mode asks for them takes the blocked tableau instead of the revised pipelines when that
+ * pipeline takes the shape; with "tableau" = 0 or "blocked" = 0 modes 1 / 2 run WITHOUT them (A/B knobs), and mode 3 returns
+ * GOMILP_ERR_UNSUPPORTED from the solve whenever the blocked tableau does not run.  "cond_guard" (1 default: gonum's
  * mat.Condition guard, from a pivot-by-pivot replay up to 64 rows and from the tableau's exact condition numbers beyond — at every exact
  * step (Phase I too), on the final basis, and in front of any pivot whose element is of rounding-noise size).
  * Returns GOMILP_OK or GOMILP_ERR_BAD_SHAPE. */

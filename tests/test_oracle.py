@@ -126,3 +126,26 @@ def test_bnb_child_layout_matches_convert_to_equalities():
     assert np.array_equal(c, [1, 2, 0, 0, 0])
     assert np.array_equal(A, [[1, 1, 1, 0, 0], [0, 1, 0, 1, 0], [-1, 0, 0, 0, 1]])
     assert np.array_equal(b, [4, 2, -3])
+
+
+def test_wide_degenerate_family_keeps_its_degeneracy():
+    """synth.wide_degenerate_lp is the family of tests/test_gpu_wide.py: its point is Bland steps and ties on wide LPs.  Over the GPU
+    test's roots the oracle takes Bland steps by the dozen, and on the cycling instances the reference's rule never ends (truncated by
+    stop_after_pivots) — an edit that made the family non-degenerate would fail here first."""
+    c, A, b = synth.wide_degenerate_lp(24, 0, 2.5)
+    m, nv = 24, 60
+    assert A.shape == (m, nv + m) and np.array_equal(A[:, nv:], np.eye(m)) and np.all(c[nv:] == 0)
+    G = A[:, :nv]
+    assert np.all(G == np.floor(G)) and G.min() >= 0 and G.max() <= 3 and G[0].min() >= 1
+    assert np.all((b >= 1) & (b <= 8) & (b == np.floor(b))) and np.all((c[:nv] <= 0) & (c[:nv] >= -4))
+    rows = {tuple(G[i]) + (b[i],) for i in range(m)}
+    assert len(rows) <= m - m // 4 + 1          # ~m // 4 duplicated rows (equal right-hand sides)
+    bland = 0
+    for m_ in (8, 24, 48, 64, 96, 128):
+        for ratio in (2, 2.5, 4):
+            for seed in (0, 1):
+                o = O.simplex(*synth.wide_degenerate_lp(m_, seed, ratio), 0.0, None, fast_initial_basis=True, stop_after_pivots=400)
+                bland += o.bland_steps
+    assert bland >= 40, bland
+    cyc = O.simplex(*synth.wide_degenerate_lp(32, 11, 2.5), 0.0, None, fast_initial_basis=True, stop_after_pivots=400)
+    assert cyc.truncated and cyc.pivots_phase2 == 400

@@ -1,11 +1,17 @@
-"""Developer tool: time full solves of one config under context knobs.  usage: solve_n.py M [reps] [knob=value ...]"""
+"""Developer tool: time full solves of one config under context knobs.  usage: solve_n.py M [reps] [knob=value ...]
+The config is a name of synth.CONFIGS, or a shape m x n: "256x1024" (dense random data, seed 1), "wd256x1024" (synth.wide_degenerate_lp,
+seed 0: integer data, duplicated rows)."""
 import sys, time, os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gomilp_amd import lp, synth
 name = sys.argv[1] if len(sys.argv) > 1 else "M"
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 knobs = dict((k, int(v)) for k, v in (a.split("=") for a in sys.argv[3:]))
-m, seed = synth.CONFIGS[name]
-c, A, b = synth.dense_lp_standard_form(m, seed)
+if "x" in name:
+    m, n = (int(v) for v in name.lstrip("wd").split("x"))
+    c, A, b = synth.wide_degenerate_lp(m, 0, (n - m) / m) if name.startswith("wd") else synth.dense_lp_standard_form(m, 1, n - m)
+else:
+    m, seed = synth.CONFIGS[name]
+    c, A, b = synth.dense_lp_standard_form(m, seed)
 cx = lp.Context(sample_events=64, chunk=64, **knobs)
 p = cx.upload(c, A, b)
 for i in range(reps):
