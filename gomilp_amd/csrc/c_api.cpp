@@ -193,6 +193,9 @@ gomilp_pool *gomilp_pool_create(int device, int workers, int *status) {
         // the workers finish the relaxations of a wave side by side, next to the batched schedule's own persistent launches: their final
         // solves keep the LU schedule that waits for nobody (lu_compressed.hip: look-ahead launches wait for their own workgroups)
         p->eng.back()->set("lu_look", 0);
+        // pools (frontier waves, batched schedules, warm starts) keep the row limit of one-pass LDS staging: roots and children
+        // beyond 8192 rows are refused as GOMILP_ERR_UNSUPPORTED
+        p->eng.back()->limit_rows_to_lds_window();
     }
     p->batch.reset(new BatchEngine(device));
     for (int w = 0; w < workers; w++) p->threads.emplace_back([p, w] { p->worker(w); });

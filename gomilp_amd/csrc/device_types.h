@@ -103,6 +103,7 @@ struct LPArgs {
     DevState *st;
     DevPivot *trace;
     int64_t trace_cap;
+    int32_t row_chunk2;    // > 0: K1-K3 in the chunked form, vectors staged this many double2 at a time (multiple of 256)
 };
 
 // Arguments of the single-kernel tableau pivot (tableau_kernels.hip).

@@ -112,6 +112,7 @@ int Engine::set(const std::string &key, int64_t v) {
     else if (key == "loop_rep") loop_rep_ = v ? 1 : 0;
     else if (key == "loop_g") { if (v != 0 && v != 8 && v != 16) return GOMILP_ERR_BAD_SHAPE; loop_g_ = v; }
     else if (key == "loop_k") { if (v != 0 && v != 8 && v != 12 && v != 16) return GOMILP_ERR_BAD_SHAPE; loop_k_ = v; }
+    else if (key == "row_chunk") { if (v < 0 || v % 512 != 0 || v > kLdsWindowLd) return GOMILP_ERR_BAD_SHAPE; row_chunk_ = v; }   // (whole 256-double2 steps of wave_dot_row)
     else if (key == "block_k") { if (v < 0 || v > bt_max_k()) return GOMILP_ERR_BAD_SHAPE; block_k_ = v; }
     else return GOMILP_ERR_BAD_SHAPE;
     return GOMILP_OK;
@@ -185,7 +186,7 @@ int64_t Engine::upload(const double *c, const double *A, int64_t lda, const doub
     if (!c || !A || !b || m64 <= 0 || n64 <= 0 || lda < n64 || m64 > (1 << 20) || n64 > (1 << 22)) return -GOMILP_ERR_BAD_SHAPE;
     const int m = (int)m64, n = (int)n64;
     const int ld = (m + 1) & ~1;
-    if ((size_t)ld * sizeof(double) > 64 * 1024) return -GOMILP_ERR_UNSUPPORTED;  // LDS staging of one row
+    if (ld > kLdsWindowLd && lds_window_only_) return -GOMILP_ERR_UNSUPPORTED;  // one-pass LDS staging of one row
     if (hipSetDevice(device_) != hipSuccess) return -GOMILP_ERR_DEVICE;
     if (!stream_ && hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking) != hipSuccess) return -GOMILP_ERR_DEVICE;
     const double t0 = now_s();
@@ -200,6 +201,13 @@ int64_t Engine::upload(const double *c, const double *A, int64_t lda, const doub
         }
     }
     const bool recycled = (bool)P;
+    if (ld > kLdsWindowLd) {   // beyond the LDS window: shapes whose buffers do not fit are refused before anything is allocated
+        const size_t dbl = (up_dA_cap_ < (size_t)m * n ? (size_t)m * n : 0) + (recycled ? 0 : need_at + 2 * need_c + need_b);
+        if (!device_fits(dbl * sizeof(double))) {
+            if (recycled) root_pool_.push_back(std::move(P));
+            return -GOMILP_ERR_UNSUPPORTED;
+        }
+    }
     if (!P) P.reset(new Problem);
     P->m = m; P->n = n; P->ld = ld;
     double *dA = nullptr;
@@ -314,7 +322,7 @@ int64_t Engine::upload_child_impl(const Problem &R, int64_t root, int K, const i
     const int m0 = R.m, n0 = R.n, m = m0 + K, n = n0 + K;
     const int ld = (m + 1) & ~1;
     for (int k = 0; k < K; k++) if (var[k] < 0 || var[k] >= n0) return -GOMILP_ERR_BAD_SHAPE;
-    if ((size_t)ld * sizeof(double) > 64 * 1024) return -GOMILP_ERR_UNSUPPORTED;
+    if (ld > kLdsWindowLd && lds_window_only_) return -GOMILP_ERR_UNSUPPORTED;
     if (hipSetDevice(device_) != hipSuccess) return -GOMILP_ERR_DEVICE;
     if (!stream_ && hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking) != hipSuccess) return -GOMILP_ERR_DEVICE;
     const double t0 = now_s();
@@ -341,6 +349,7 @@ int64_t Engine::upload_child_impl(const Problem &R, int64_t root, int K, const i
         P->cap_at = (size_t)(ncap + 1) * ldcap; P->cap_c = (size_t)ncap + 1; P->cap_b = (size_t)ldcap; P->cap_k = kcap;
         // b | c | c1 | sign (doubles) | var (ints) in one device block, mirrored by the pinned staging block: one copy
         const size_t blk = P->cap_b + 2 * P->cap_c + 2 * (size_t)P->cap_k + 8;
+        if (ld > kLdsWindowLd && !device_fits((P->cap_at + blk) * sizeof(double))) return -GOMILP_ERR_UNSUPPORTED;
         if (dmalloc(&P->dAt, P->cap_at) != hipSuccess || dmalloc(&P->db, blk) != hipSuccess) {
             release(*P);
             return -GOMILP_ERR_DEVICE;
@@ -437,7 +446,34 @@ LPArgs Engine::make_args(const Problem &P, int phase, double tol, int nn, const 
     a.st = w.st;
     a.trace = (trace_on_ || shadow_trace_) ? w.trace : nullptr;
     a.trace_cap = w.trace_cap;
+    a.row_chunk2 = row_chunk2(P);
     return a;
+}
+
+int Engine::row_chunk2(const Problem &P) const {
+    if (row_chunk_ > 0) return (int)(row_chunk_ / 2);
+    return P.ld > kLdsWindowLd ? kAutoRowChunk / 2 : 0;
+}
+
+bool Engine::device_fits(size_t bytes) {
+    size_t avail = 0, total = 0;
+    if (hipSetDevice(device_) != hipSuccess || hipMemGetInfo(&avail, &total) != hipSuccess) return false;
+    return bytes + bytes / 16 + ((size_t)256 << 20) <= avail;   // (head-room: allocation granularity, the runtime's own buffers)
+}
+
+// What ensure_work will allocate for P (its head-room formula), beyond what is held already: a solve beyond the LDS window (the
+// three-kernel revised simplex, no tableau) is refused up front instead of failing an allocation halfway.  (Buffers that a
+// re-allocation releases are not counted as free: conservative.)
+bool Engine::large_solve_fits(const Problem &P) {
+    const Work &w = *w_;
+    const int m = P.m, ncols = P.n + 1;
+    size_t dbl = 0;
+    if (!(m <= w.cap_m && ncols <= w.cap_cols)) {
+        const int nmi = std::max(m + 32 + m / 16, w.cap_m), nci = std::max(ncols + 64 + ncols / 16, w.cap_cols);
+        const size_t nm = (size_t)nmi, nc = (size_t)nci, nld = (size_t)std::max((nmi + 1) & ~1, w.cap_ld);
+        dbl += 4 * nm * nld + 512 + 200 * nld + 4 * nc + 8 * nm;   // B^-1 x 2, W, Wd; x_B, y, d, move, y scratch, LU panels; r; index lists
+    }
+    return dbl == 0 || device_fits(dbl * sizeof(double));
 }
 
 void Engine::sync_state_to_device() {
@@ -447,7 +483,7 @@ void Engine::sync_state_to_device() {
 
 int Engine::refresh_xb_y(const Problem &P, const double *cost) {
     Work &w = *w_;
-    launch_matvec_rows(w.binv[cur_], P.ld, P.m, P.db, w.xb, stream_);
+    launch_matvec_rows(w.binv[cur_], P.ld, P.m, P.db, w.xb, stream_, row_chunk2(P));
     launch_y_from_binv(w.binv[cur_], P.ld, P.m, cost, w.basic, w.yscratch, w.yb[ycur_], stream_);
     launches_ += 3;
     return GOMILP_OK;
@@ -1220,6 +1256,8 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
         return finish(P.verify_status);
     }
     const int m = P.m, n = P.n;
+    // beyond the LDS window (chunked staging): slack-basis starts only, and only what fits the free device memory
+    if (P.ld > kLdsWindowLd && (initial_basic || m >= n || !large_solve_fits(P))) return finish(GOMILP_ERR_UNSUPPORTED);
     int rc = ensure_work(m, n + 1);
     if (rc != GOMILP_OK) return finish(rc);
     Work &w = *w_;
@@ -1270,6 +1308,7 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
             rho[pos] = P.lastrow[j]; used[rho[pos]] = 1; basic[pos] = j;
         }
     }
+    if (!unit_basis && P.ld > kLdsWindowLd) return finish(GOMILP_ERR_UNSUPPORTED);   // (the general start's search and set-up stage m-long rows)
     gen_start_ = !unit_basis;
     gen_binv_dev_ = false;
     badly_scaled_ = P.scale_span > 1e9;
@@ -1283,7 +1322,9 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
     const bool tab_fits = (size_t)tab_ld(nn_max) * sizeof(double) <= 64 * 1024;
     const bool bt_ok = blocked_ && bt_supported(m, nn_max);
     const bool exact_wanted = exact_degenerate_ == 3 || exact_degenerate_ == 2 || (exact_degenerate_ == 1 && (m <= 256 || !unit_basis || badly_scaled_));
-    const bool use_tab = tableau_ && ((n - m) < 2 * m || !unit_basis || (exact_wanted && bt_ok)) && tab_fits;
+    // (beyond the LDS window only the three-kernel revised simplex runs: the single-kernel tableau returned a wrong ErrUnbounded on a
+    // 12288 x 18432 slack start after a run of Bland steps — DESIGN.md §2.1, "Beyond 8192 rows")
+    const bool use_tab = tableau_ && ((n - m) < 2 * m || !unit_basis || (exact_wanted && bt_ok)) && tab_fits && P.ld <= kLdsWindowLd;
     // strict mode IS the exact steps: where the blocked tableau does not run, the solve refuses instead of deciding the default way
     if (exact_degenerate_ == 3 && !(use_tab && bt_ok)) return finish(GOMILP_ERR_UNSUPPORTED);
     std::vector<double> xb(m, 0.0), binv_host;

@@ -15,6 +15,11 @@
 
 namespace gomilp {
 
+// The revised-simplex kernels stage one m-long vector (ld doubles) per workgroup in LDS.  Up to kLdsWindowLd (64 KB) it is staged
+// in one pass; beyond it the chunked form streams it kAutoRowChunk doubles at a time (simplex_kernels.hip).
+constexpr int kLdsWindowLd = 8192;
+constexpr int kAutoRowChunk = 4096;
+
 // A standard-form LP resident in HBM.
 struct Problem {
     int m = 0, n = 0, ld = 0;
@@ -106,8 +111,14 @@ class Engine {
     // diagnostic: the device column search on a resident problem (tests compare it with the host forms)
     int debug_find_independent(int64_t id, std::vector<int32_t> &idxs);
 
+    // pools, batched waves and warm starts keep the row limit of one-pass LDS staging (ld <= kLdsWindowLd)
+    void limit_rows_to_lds_window() { lds_window_only_ = true; }
+
    private:
     struct Work;  // device work buffers, sized for the largest problem seen
+    int row_chunk2(const Problem &P) const;   // LPArgs::row_chunk2 for this problem (0: the one-pass kernels)
+    bool device_fits(size_t bytes);           // free device memory (hipMemGetInfo) holds `bytes` with a margin
+    bool large_solve_fits(const Problem &P);  // the work set of a solve beyond the LDS window fits the free memory
     int ensure_work(int m, int ncols);
     const Problem *problem_ptr(int64_t id);
     int64_t upload_child_impl(const Problem &R, int64_t root_id, int K, const int32_t *var, const double *sign, const double *rhs);
@@ -186,7 +197,9 @@ class Engine {
             loop_g_ = 0,       // its pivot workgroups (0 / 16: 16 x 128 threads up to 2048 rows, 16 x 256 beyond; 8: 8 x 256 / 8 x 512)
             loop_k_ = 0,       // its pivots per block (0: 8 up to 2048 rows, 16 beyond; 8 / 16 forced where instantiated)
             exact_degenerate_ = 1,   // 0 never, 1 bases of up to 256 rows and every non-slack start, 2 always: pivots whose winning ratio is (nearly) zero are decided on a fresh gonum-order x_B; 3 strict: EVERY pivot and the stop test are decided on fresh gonum-order solves
-            cond_guard_ = 1;   // replay the condition guards of the reference on the host for bases of up to 64 rows
+            cond_guard_ = 1,   // replay the condition guards of the reference on the host for bases of up to 64 rows
+            row_chunk_ = 0;    // doubles per LDS chunk of the revised-simplex kernels' staged vectors; 0: one-pass staging up to ld = kLdsWindowLd, chunks of kAutoRowChunk beyond
+    bool lds_window_only_ = false;   // refuse problems beyond the one-pass LDS window, as before the chunked form (pool workers)
     bool badly_scaled_ = false;   // the current problem's entries span more than nine decades (Problem::scale_span): guard on, tableau checked
     bool gen_binv_dev_ = false;   // the searched basis' B^-1 = R^-1 Q^T is resident in the first B^-1 buffer (the device judged the square step): no upload
     bool gen_start_ = false;      // the current solve starts from a searched (non-slack) basis: the degenerate-pivot guard stays on
@@ -329,7 +342,7 @@ void launch_col_stats(const double *At, int ld, int m, int n, int32_t *nnz, int3
 void launch_set_binv_perm(double *binv, int ld, int m, const int32_t *rho, hipStream_t s);
 void launch_child_assemble(const double *At0, int ld0, int m0, int n0, double *At1, int ld1, int K, const int32_t *var,
                            const double *sign, hipStream_t s);
-void launch_matvec_rows(const double *M, int ld, int m, const double *vec, double *out, hipStream_t s);
+void launch_matvec_rows(const double *M, int ld, int m, const double *vec, double *out, hipStream_t s, int row_chunk2 = 0);
 int y_chunks(int m);
 void launch_y_from_binv(const double *binv, int ld, int m, const double *cost, const int32_t *basic, double *scratch,
                         double *y, hipStream_t s);

@@ -288,4 +288,47 @@ __device__ __forceinline__ void stage_vec(double2 *__restrict__ svec, const doub
     __syncthreads();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Chunked staging (vectors longer than the LDS window): the vector goes through LDS in chunks of
+// ck2 double2 (a multiple of 256), and wave_dot_row's four accumulators are carried from chunk to chunk.  A chunk
+// [c0, c1) that is not the last one holds whole 256-wide steps of wave_dot_row's main loop, so every lane adds the
+// same terms into the same accumulator in the same order as the one-pass form: the result is bit-identical.
+// ------------------------------------------------------------------------------------------------
+struct DotAcc {
+    double a0, a1, a2, a3;
+};
+
+// (every thread of the workgroup: a barrier in front, so that the previous chunk is no longer read, and one behind)
+__device__ __forceinline__ void stage_chunk(double2 *__restrict__ svec, const double *__restrict__ src, int c0, int c1) {
+    const double2 *s2 = reinterpret_cast<const double2 *>(src) + c0;
+    __syncthreads();
+    for (int c = threadIdx.x; c < c1 - c0; c += kBlock) svec[c] = s2[c];
+    __syncthreads();
+}
+
+// the part of wave_dot_row that falls into the staged chunk [c0, c1) of a row of ld2 double2 (svec holds element c0 at 0)
+__device__ __forceinline__ void wave_dot_chunk(const double *__restrict__ row, const double2 *__restrict__ svec, int c0, int c1,
+                                               int ld2, int lane, DotAcc &acc) {
+    const double2 *r2 = reinterpret_cast<const double2 *>(row);
+    int c = c0 + lane;
+    for (; c + 192 < c1; c += 256) {
+        double2 v0 = r2[c], v1 = r2[c + 64], v2 = r2[c + 128], v3 = r2[c + 192];
+        const int o = c - c0;
+        double2 s0 = svec[o], s1 = svec[o + 64], s2 = svec[o + 128], s3 = svec[o + 192];
+        acc.a0 += v0.x * s0.x + v0.y * s0.y;
+        acc.a1 += v1.x * s1.x + v1.y * s1.y;
+        acc.a2 += v2.x * s2.x + v2.y * s2.y;
+        acc.a3 += v3.x * s3.x + v3.y * s3.y;
+    }
+    if (c1 == ld2) {   // the last chunk: wave_dot_row's tail
+        for (; c < ld2; c += 64) {
+            double2 v0 = r2[c];
+            double2 s0 = svec[c - c0];
+            acc.a0 += v0.x * s0.x + v0.y * s0.y;
+        }
+    }
+}
+
+__device__ __forceinline__ double wave_dot_finish(const DotAcc &acc) { return wave_sum((acc.a0 + acc.a1) + (acc.a2 + acc.a3)); }
+
 }  // namespace gomilp

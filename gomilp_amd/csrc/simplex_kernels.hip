@@ -173,6 +173,199 @@ __global__ __launch_bounds__(kBlock) void k_update(LPArgs a, int nparts_ratio, i
 }
 
 // ------------------------------------------------------------------------------------------------
+// K1-K3 and the refresh in the chunked form (kernels_common.h: stage_chunk / wave_dot_chunk): for vectors longer than
+// the LDS window (ld > 8192), or wherever the context knob row_chunk forces it.  Same operations per element, same
+// first-index argmins as the one-pass kernels above, bit-identical results.  A wave takes its rows kCkRows at a time
+// (rows wave, wave + nwaves, ... as above), and the workgroup streams the vector through LDS once per such group, so
+// the loops run to a workgroup-uniform bound: every thread reaches every barrier.
+// ------------------------------------------------------------------------------------------------
+constexpr int kCkRows = 4;
+
+// one group of up to kCkRows rows of a wave: dot[r] = M[row(r), :] . vec (valid where row(r) < rows)
+__device__ __forceinline__ void dot_group(const double *__restrict__ M, int ld, const int32_t *__restrict__ rowmap, int rows,
+                                          int k0, int wave, int nwaves, const double *__restrict__ vec, double2 *svec, int ck2,
+                                          int lane, double (&dot)[kCkRows]) {
+    const int ld2 = ld >> 1;
+    const double *rowp[kCkRows];
+    DotAcc acc[kCkRows];
+#pragma unroll
+    for (int r = 0; r < kCkRows; r++) {
+        const int pos = wave + (k0 + r) * nwaves;
+        rowp[r] = pos < rows ? M + (size_t)(rowmap ? rowmap[pos] : pos) * ld : nullptr;
+        acc[r].a0 = acc[r].a1 = acc[r].a2 = acc[r].a3 = 0;
+    }
+    for (int c0 = 0; c0 < ld2; c0 += ck2) {
+        const int c1 = min(c0 + ck2, ld2);
+        stage_chunk(svec, vec, c0, c1);
+#pragma unroll
+        for (int r = 0; r < kCkRows; r++)
+            if (rowp[r]) wave_dot_chunk(rowp[r], svec, c0, c1, ld2, lane, acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < kCkRows; r++) dot[r] = rowp[r] ? wave_dot_finish(acc[r]) : 0.0;
+}
+
+__global__ __launch_bounds__(kBlock) void k_price_ck(LPArgs a, int ck2) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    DevState *st = a.st;
+    if (st->done) return;
+    if (st->max_pivots > 0 && st->pivots >= st->max_pivots) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_MAX_PIVOTS; }
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    const int kmax = (a.nn + nwaves - 1) / nwaves;
+    unsigned long long bk = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        double dot[kCkRows];
+        dot_group(a.At, a.ld, a.nonbasic, a.nn, k0, wave, nwaves, a.y, svec, ck2, lane, dot);
+#pragma unroll
+        for (int r = 0; r < kCkRows; r++) {
+            const int pos = wave + (k0 + r) * nwaves;
+            if (pos >= a.nn) continue;
+            const double rc = a.cost[a.nonbasic[pos]] - dot[r];
+            if (lane == 0) a.rvec[pos] = rc;
+            amin_take(bk, bi, ordkey(rc), (unsigned int)pos);
+        }
+    }
+    block_argmin(bk, bi, sk, si);
+    if (threadIdx.x == 0) { a.pk_price[blockIdx.x] = bk; a.pi_price[blockIdx.x] = bi; }
+}
+
+__global__ __launch_bounds__(kBlock) void k_ftran_ck(LPArgs a, int nparts_price, int forced_pos, int forced_var, int ck2) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    DevState *st = a.st;
+    if (st->done) return;
+    int q = forced_pos;
+    int var;
+    if (forced_var >= 0) {
+        var = forced_var;
+    } else {
+        if (q < 0) {
+            q = (int)reduce_partials(a.pk_price, a.pi_price, nparts_price, sk, si, nullptr);
+            const double rq = a.rvec[q];
+            if (rq >= -a.tol) {
+                if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_OPTIMAL; st->q = q; st->rq = rq; }
+                return;
+            }
+            if (blockIdx.x == 0 && threadIdx.x == 0) { st->q = q; st->rq = rq; }
+        } else if (blockIdx.x == 0 && threadIdx.x == 0) {
+            st->q = q; st->rq = a.rvec[q];
+        }
+        var = a.nonbasic[q];
+    }
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    const int kmax = (a.m + nwaves - 1) / nwaves;
+    unsigned long long bk = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        double dot[kCkRows];
+        dot_group(a.binv_cur, a.ld, nullptr, a.m, k0, wave, nwaves, a.At + (size_t)var * a.ld, svec, ck2, lane, dot);
+#pragma unroll
+        for (int r = 0; r < kCkRows; r++) {
+            const int i = wave + (k0 + r) * nwaves;
+            if (i >= a.m) continue;
+            const double dp = dot[r];
+            double d = -dp;
+            if (fabs(d) < 1e-13) d = 0;
+            const double mv = (d >= 0) ? __builtin_inf() : a.xb[i] / fabs(d);
+            if (lane == 0) { a.dvec[i] = dp; a.move[i] = mv; }
+            amin_take(bk, bi, ordkey(mv), (unsigned int)i);
+        }
+    }
+    block_argmin(bk, bi, sk, si);
+    if (threadIdx.x == 0) { a.pk_ratio[blockIdx.x] = bk; a.pi_ratio[blockIdx.x] = bi; }
+}
+
+__global__ __launch_bounds__(kBlock) void k_update_ck(LPArgs a, int nparts_ratio, int forced_p, int no_swap, int bland, int ck2) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    DevState *st = a.st;
+    if (st->done) return;
+    int p = forced_p;
+    if (p < 0) {
+        p = (int)reduce_partials(a.pk_ratio, a.pi_ratio, nparts_ratio, sk, si, nullptr);
+        const double mv = a.move[p];
+        if (mv == __builtin_inf()) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_UNBOUNDED; st->p = p; st->mv = mv; }
+            return;
+        }
+        if (mv <= 0) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_NEED_BLAND; st->p = p; st->mv = mv; }
+            return;
+        }
+    }
+    const double dpv = a.dvec[p];
+    const int ld2 = a.ld >> 1;
+    const double *rowp_g = a.binv_cur + (size_t)p * a.ld;   // old row p (binv_cur is only read here)
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    const int kmax = (a.m + nwaves - 1) / nwaves;
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        for (int c0 = 0; c0 < ld2; c0 += ck2) {
+            const int c1 = min(c0 + ck2, ld2);
+            stage_chunk(svec, rowp_g, c0, c1);
+#pragma unroll
+            for (int r = 0; r < kCkRows; r++) {
+                const int i = wave + (k0 + r) * nwaves;
+                if (i >= a.m) continue;
+                const double2 *src = reinterpret_cast<const double2 *>(a.binv_cur + (size_t)i * a.ld);
+                double2 *dst = reinterpret_cast<double2 *>(a.binv_next + (size_t)i * a.ld);
+                if (i == p) {
+                    for (int c = c0 + lane; c < c1; c += 64) {
+                        double2 v = svec[c - c0];
+                        v.x = v.x / dpv; v.y = v.y / dpv;
+                        dst[c] = v;
+                    }
+                } else {
+                    const double f = a.dvec[i] / dpv;
+                    for (int c = c0 + lane; c < c1; c += 64) {
+                        double2 v = src[c];
+                        const double2 rp = svec[c - c0];
+                        v.x = v.x - f * rp.x; v.y = v.y - f * rp.y;
+                        dst[c] = v;
+                    }
+                }
+            }
+        }
+    }
+    if (blockIdx.x == 0) {
+        // O(m) vector updates by workgroup 0, as in k_update (row p read from B^-1 itself instead of LDS: same values)
+        const double theta = a.xb[p] / dpv;
+        const double rq = no_swap ? 0.0 : st->rq;
+        const double alpha = rq / dpv;
+        __syncthreads();
+        for (int i = threadIdx.x; i < a.m; i += kBlock) a.xb[i] = (i == p) ? theta : a.xb[i] - theta * a.dvec[i];
+        for (int j = threadIdx.x; j < a.ld; j += kBlock) a.y[j] = a.y[j] + alpha * rowp_g[j];
+        if (threadIdx.x == 0) {
+            const int q = st->q;
+            st->p = p; st->dp = dpv; st->mv = a.move[p];
+            if (!no_swap) {
+                const int ent = a.nonbasic[q], lea = a.basic[p];
+                a.basic[p] = ent; a.nonbasic[q] = lea;
+                if (a.trace && st->trace_len < a.trace_cap) {
+                    DevPivot &t = a.trace[st->trace_len];
+                    t.phase = a.phase; t.bland = bland; t.min_idx = q; t.replace = p; t.entering = ent; t.leaving = lea;
+                }
+                st->trace_len += 1;
+                st->pivots += 1;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // set-up / refresh kernels (outside the per-pivot path)
 // ------------------------------------------------------------------------------------------------
 
@@ -264,6 +457,24 @@ __global__ __launch_bounds__(kBlock) void k_matvec_rows(const double *__restrict
     for (int i = wave; i < m; i += nwaves) {
         const double d = wave_dot_row(M + (size_t)i * ld, svec, ld2, lane);
         if (lane == 0) out[i] = d;
+    }
+}
+// the chunked form of k_matvec_rows
+__global__ __launch_bounds__(kBlock) void k_matvec_rows_ck(const double *__restrict__ M, int ld, int m,
+                                                           const double *__restrict__ vec, double *__restrict__ out, int ck2) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    const int kmax = (m + nwaves - 1) / nwaves;
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        double dot[kCkRows];
+        dot_group(M, ld, nullptr, m, k0, wave, nwaves, vec, svec, ck2, lane, dot);
+#pragma unroll
+        for (int r = 0; r < kCkRows; r++) {
+            const int i = wave + (k0 + r) * nwaves;
+            if (i < m && lane == 0) out[i] = dot[r];
+        }
     }
 }
 
@@ -416,21 +627,30 @@ static inline int grid_for_rows(int rows) {
 
 int launch_price(const LPArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const int g = grid_for_rows(a.nn);
-    hipExtLaunchKernelGGL(k_price, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a);
+    if (a.row_chunk2 > 0) hipExtLaunchKernelGGL(k_price_ck, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, a.row_chunk2);
+    else hipExtLaunchKernelGGL(k_price, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a);
     return g;
 }
 int launch_ftran(const LPArgs &a, int nparts_price, int forced_pos, int forced_var, hipStream_t s, hipEvent_t e0,
                  hipEvent_t e1) {
     const int g = grid_for_rows(a.m);
-    hipExtLaunchKernelGGL(k_ftran, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a, nparts_price,
-                          forced_pos, forced_var);
+    if (a.row_chunk2 > 0)
+        hipExtLaunchKernelGGL(k_ftran_ck, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, nparts_price,
+                              forced_pos, forced_var, a.row_chunk2);
+    else
+        hipExtLaunchKernelGGL(k_ftran, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a, nparts_price,
+                              forced_pos, forced_var);
     return g;
 }
 void launch_update(const LPArgs &a, int nparts_ratio, int forced_p, int no_swap, int bland, hipStream_t s, hipEvent_t e0,
                    hipEvent_t e1) {
     const int g = grid_for_rows(a.m);
-    hipExtLaunchKernelGGL(k_update, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a, nparts_ratio,
-                          forced_p, no_swap, bland);
+    if (a.row_chunk2 > 0)
+        hipExtLaunchKernelGGL(k_update_ck, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, nparts_ratio,
+                              forced_p, no_swap, bland, a.row_chunk2);
+    else
+        hipExtLaunchKernelGGL(k_update, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a, nparts_ratio,
+                              forced_p, no_swap, bland);
 }
 void launch_transpose_in(const double *A, int64_t lda, int m, int n, double *At, int ld, hipStream_t s) {
     dim3 grid((n + 31) / 32, (m + 31) / 32), block(32, 8);
@@ -447,8 +667,12 @@ void launch_child_assemble(const double *At0, int ld0, int m0, int n0, double *A
 void launch_set_binv_perm(double *binv, int ld, int m, const int32_t *rho, hipStream_t s) {
     hipLaunchKernelGGL(k_set_binv_perm, dim3((m + 255) / 256), dim3(256), 0, s, binv, ld, m, rho);
 }
-void launch_matvec_rows(const double *M, int ld, int m, const double *vec, double *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_matvec_rows, dim3(grid_for_rows(m)), dim3(kBlock), (size_t)ld * sizeof(double), s, M, ld, m, vec, out);
+void launch_matvec_rows(const double *M, int ld, int m, const double *vec, double *out, hipStream_t s, int row_chunk2) {
+    if (row_chunk2 > 0)
+        hipLaunchKernelGGL(k_matvec_rows_ck, dim3(grid_for_rows(m)), dim3(kBlock), (size_t)row_chunk2 * sizeof(double2), s, M, ld, m, vec, out,
+                           row_chunk2);
+    else
+        hipLaunchKernelGGL(k_matvec_rows, dim3(grid_for_rows(m)), dim3(kBlock), (size_t)ld * sizeof(double), s, M, ld, m, vec, out);
 }
 // scratch must hold y_chunks(m) * ld doubles
 int y_chunks(int m) { int c = (m + 63) / 64; return c > 64 ? 64 : c; }

@@ -131,7 +131,20 @@ int gomilp_ctx_device(const gomilp_ctx *ctx);
  * GOMILP_ERR_UNSUPPORTED from the solve whenever the blocked tableau does not run.  "cond_guard" (1 default: gonum's
  * mat.Condition guard, from a pivot-by-pivot replay up to 64 rows and from the tableau's exact condition numbers beyond — at every exact
  * step (Phase I too), on the final basis, and in front of any pivot whose element is of rounding-noise size).
+ * "row_chunk" (doubles; 0 default): the revised-simplex kernels stage one m-long vector per workgroup in LDS — in one pass up to
+ * 8192 rows, in chunks of 4096 doubles beyond (bit-identical either way); a multiple of 512 up to 8192 forces the chunked form with
+ * that many doubles per chunk at every size (tests).
  * Returns GOMILP_OK or GOMILP_ERR_BAD_SHAPE. */
+
+/* Row limit.  Upload accepts m < 2^20 rows; the device memory decides what solves.  Up to 8192 rows every path below applies.
+ * Beyond 8192 rows ("Beyond 8192 rows") a single context solves SLACK-BASIS starts — every row has its own
+ * unit column, GoMILP's inequality form [G | I] — with Phase I where b has negative entries, through gomilp_lp_simplex,
+ * gomilp_lp_upload + gomilp_lp_solve_resident, and gomilp_lp_upload_child on such a root; with the statuses, trace, basis and point
+ * semantics of the same pipelines at 8192 rows.  A shape whose buffers (A^T, the two B^-1 copies, the final solve's matrices, the
+ * tableau) do not fit the free device memory returns GOMILP_ERR_UNSUPPORTED before anything is allocated; the context stays usable.
+ * Still GOMILP_ERR_UNSUPPORTED beyond 8192 rows: non-slack starts (equality rows, a supplied initial_basic, m >= n), frontier pools
+ * (gomilp_pool_set_root, their waves and warm starts), and exact_degenerate = 3 (the blocked tableau does not run there).  The final
+ * solve of those bases takes the one-launch-per-column LU (k_lu_step): seconds, not milliseconds. */
 int gomilp_ctx_set(gomilp_ctx *ctx, const char *key, int64_t value);
 
 /* Upload a standard-form LP (row-major A, stride lda) and keep it resident.  Returns a problem id >= 0, or
