@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import List, Optional
 
 import numpy as np
@@ -79,14 +80,47 @@ def max_fun_branch_point(c, integrality) -> int:
     return cur
 
 
+def _context_wave(root_lp, wave, live, warm, dual_budget, n0, out):
+    """One FIFO wave solved node by node on a context (solve_milp(context=...)): the arrays of a FrontierResult.  A node is the
+    root's child with all its branch rows; warm: it starts from its parent's kept state and keeps its own (in `live`)."""
+    k = len(wave)
+    res = SimpleNamespace(status=np.zeros(k, dtype=np.int32), z=np.full(k, math.nan), x=np.zeros((k, n0)), has_x=np.zeros(k, dtype=np.int32),
+                          stats={"pivots_phase1": 0, "pivots_phase2": 0})
+    for i, nd in enumerate(wave):
+        ch = root_lp.child(nd.constraints)
+        if warm:
+            r = ch.solve(parent=live.get(nd.parent), keep=True, dual_budget=dual_budget)
+            w = r.stats["warm"]
+            out.warm_started += w["warm_started"]
+            out.warm_fallbacks += int(w["fallback"] == 4)
+            out.pivots_dual += w["pivots_dual"]
+            out.pivots += w["pivots_dual"]
+            live[nd.id] = ch
+        else:
+            r = ch.solve()
+            ch.free()
+        res.status[i], res.z[i] = r.status, r.z
+        if r.x is not None:
+            res.x[i] = r.x[:n0]          # the root's width (subproblem.go:157-159)
+            res.has_x[i] = 1
+        res.stats["pivots_phase1"] += r.stats["pivots_phase1"]
+        res.stats["pivots_phase2"] += r.stats["pivots_phase2"]
+    return res
+
+
 def solve_milp(c, A, b, G, h, integrality, *, max_nodes: int = 255, workers: int = 8, device: int = -1,
-               pool=None, warm: bool = False, dual_budget: int = 0) -> Result:
+               pool=None, warm: bool = False, dual_budget: int = 0, context: "Optional[lp.Context]" = None) -> Result:
     """milpProblem.solve (ilp.go:75-116) with every relaxation on the GPU.  `max_nodes` stands in for the context
     deadline of the reference (its tree does not terminate on many inputs: SURVEY.md §3.4).
 
     warm (opt-in; /root/reference/README.md TODO "initiate the simplex at solution of parent"): every node that branches keeps its final
     basis resident (gomilp_frontier_solve_warm), its two children start from it with the dual simplex; a parent is released once both
-    children are solved.  Statuses, decisions and z agree with the cold run to 1e-9 (tests), the pivot paths do not."""
+    children are solved.  Statuses, decisions and z agree with the cold run to 1e-9 (tests), the pivot paths do not.
+
+    context (an lp.Context): the tree runs node by node on that one context instead of a pool — the root uploaded once, every node
+    the root's child with its branch rows, freed when done; with warm, a node starts from its parent's kept state
+    (gomilp_lp_solve_warm) and keeps its own while it has unsolved children.  Same node order, decisions and outputs as the pool
+    path.  The only way to run a tree on MILPs beyond 8192 rows: pools refuse them."""
     c = np.asarray(c, dtype=np.float64)
     integrality = list(integrality)
     if G is not None:
@@ -99,27 +133,49 @@ def solve_milp(c, A, b, G, h, integrality, *, max_nodes: int = 255, workers: int
     out = Result(None, None, math.nan)
     root = Node(0, 0, [])
     out.nodes.append(root)
-    own_pool = pool is None
-    if own_pool:
-        pool = lp.FrontierPool(device=device, workers=workers)   # (a caller that solves several MILPs keeps one pool)
-    pool.set_root(c0, A0, b0)
-    if warm:   # the root through the batched schedule, so that its final state can stay resident for its children
-        rr = pool.solve_warm([[]], tags=[0], keep=[1])
-        r = lp.LPResult(int(rr.status[0]), float(rr.z[0]), rr.x[0].copy() if rr.has_x[0] else None, None, rr.stats)
+    on_ctx = context is not None
+    own_pool = pool is None and not on_ctx
+    live: dict = {}   # context path: node id -> its ResidentLP while it is needed (0: the root)
+    if on_ctx:
+        root_lp = context.upload(c0, A0, b0)
+        live[0] = root_lp
+        r = root_lp.solve(keep=warm) if warm else root_lp.solve()   # subproblem.go:172 (warm: kept for its children)
+        if warm:
+            out.pivots_dual += r.stats["warm"]["pivots_dual"]
+
+        def close():
+            for nid in sorted(live, reverse=True):   # children before the root they were assembled from
+                live.pop(nid).free()
+
+        def release(nid):
+            if nid != 0 and nid in live:   # (the root stays until the end: every node is its child)
+                live.pop(nid).free()
     else:
-        r = pool.solve_root(0.0)                         # subproblem.go:172
+        if own_pool:
+            pool = lp.FrontierPool(device=device, workers=workers)   # (a caller that solves several MILPs keeps one pool)
+        pool.set_root(c0, A0, b0)
+        if warm:   # the root through the batched schedule, so that its final state can stay resident for its children
+            rr = pool.solve_warm([[]], tags=[0], keep=[1])
+            r = lp.LPResult(int(rr.status[0]), float(rr.z[0]), rr.x[0].copy() if rr.has_x[0] else None, None, rr.stats)
+        else:
+            r = pool.solve_root(0.0)                         # subproblem.go:172
+
+        def close():
+            if own_pool:
+                pool.close()
+
+        def release(nid):
+            pool.release_warm(nid)
     root.status, root.z, root.x = r.status, r.z, r.x
     out.relaxations, out.pivots = 1, r.stats["pivots_phase1"] + r.stats["pivots_phase2"]
     if r.status != lp.OK:
         out.error = "panic:" + lp.STATUS_NAMES.get(r.status, str(r.status))   # subproblem.go:173-176
-        if own_pool:
-            pool.close()
+        close()
         return out
     if feasible_for_ip(int0, r.x):
         root.decision = "INITIAL_RX_FEASIBLE_FOR_IP"
         out.x, out.z = r.x[: len(c)].copy(), r.z
-        if own_pool:
-            pool.close()
+        close()
         return out
     incumbent: Optional[Node] = None
     queue: List[Node] = []
@@ -158,8 +214,7 @@ def solve_milp(c, A, b, G, h, integrality, *, max_nodes: int = 255, workers: int
     err = check(root)
     if err:
         out.error = err
-        if own_pool:
-            pool.close()
+        close()
         return out
     try:
         solved = 0
@@ -169,7 +224,14 @@ def solve_milp(c, A, b, G, h, integrality, *, max_nodes: int = 255, workers: int
                 out.error = "DeadlineExceeded"
                 break
             wave, queue = queue[:budget], queue[budget:]
-            if warm:
+            if on_ctx:
+                res = _context_wave(root_lp, wave, live, warm, dual_budget, n0, out)
+                if warm:
+                    for nd in wave:   # a parent whose two children are solved is not needed any more
+                        kids_left[nd.parent] = kids_left.get(nd.parent, 2) - 1
+                        if kids_left[nd.parent] == 0:
+                            release(nd.parent)
+            elif warm:
                 res = pool.solve_warm([nd.constraints for nd in wave], parents=[nd.parent for nd in wave], tags=[nd.id for nd in wave],
                                       keep=[1] * len(wave), dual_budget=dual_budget)
                 out.pivots += res.stats["pivots_dual"]
@@ -194,13 +256,12 @@ def solve_milp(c, A, b, G, h, integrality, *, max_nodes: int = 255, workers: int
                     out.error = err
                     return out
                 if warm and nd.decision != "BETTER_THAN_INCUMBENT_BRANCHING":
-                    pool.release_warm(nd.id)   # a leaf (pruned, integer feasible, infeasible): nobody will start from its basis
+                    release(nd.id)   # a leaf (pruned, integer feasible, infeasible): nobody will start from its basis
             queue = pending + queue
     finally:
-        if warm:
+        if warm and not on_ctx:
             pool.release_warm(-1)   # whatever is still kept (the deadline, an early return): 2-3 MB of HBM per 520-row node
-        if own_pool:
-            pool.close()
+        close()
     if out.error == "DeadlineExceeded":
         if incumbent is not None:
             out.x, out.z = incumbent.x[: len(c)].copy(), incumbent.z

@@ -174,6 +174,12 @@ int gomilp_lp_solve_resident(gomilp_ctx *ctx, int64_t problem, double tol, const
     if (!ctx) return GOMILP_ERR_BAD_SHAPE;
     return ctx->eng->solve(problem, tol, initial_basic, opt_f, opt_x, has_x, basis_out, stats);
 }
+int gomilp_lp_solve_warm(gomilp_ctx *ctx, int64_t problem, int64_t parent, int32_t keep, int32_t dual_budget, double tol,
+                         double *opt_f, double *opt_x, int32_t *has_x, int64_t *basis_out, gomilp_lp_stats *stats,
+                         gomilp_warm_stats *wstats) {
+    if (!ctx) return GOMILP_ERR_BAD_SHAPE;
+    return ctx->eng->solve_warm(problem, parent, keep, dual_budget, tol, opt_f, opt_x, has_x, basis_out, stats, wstats);
+}
 int64_t gomilp_lp_upload_child(gomilp_ctx *ctx, int64_t root_problem, int32_t K, const int32_t *var, const double *sign,
                                const double *rhs) {
     if (!ctx) return -GOMILP_ERR_BAD_SHAPE;

@@ -29,6 +29,9 @@ enum : int32_t {
                             // current basis before the decision is taken (simplex.go:268-277 sees a fresh x_B every pivot)
 };
 
+// k_ftran's forced_pos / k_update's forced_p: the dual pivot of a warm start (dual_kernels.hip) — the entering position is the argmin
+// of the dual pricing kernel's partials (none: ST_DUAL_INFEASIBLE), the leaving row the one k_dual_leave put into DevState::p
+constexpr int kDualPick = -2;
 constexpr int kMaxPartials = 1024;  // per-workgroup partial arg-reductions (grid <= 1024 workgroups)
 constexpr int kBlock = 256;         // threads per workgroup (4 waves of 64)
 constexpr int kWavesPerBlock = 4;

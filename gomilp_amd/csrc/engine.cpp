@@ -33,6 +33,8 @@ Engine::~Engine() {
                 if (p->dsign) hipFree(p->dsign);
             }
         }
+    for (auto &kv : kept_) if (kv.second.d) hipFree(kv.second.d);
+    for (auto &b : keep_pool_) hipFree(b.first);
     w_->release_all();
     if (stream_) hipStreamDestroy(stream_);
 }
@@ -415,6 +417,7 @@ int Engine::free_problem(int64_t id) {
     std::lock_guard<std::mutex> g(mu_);
     if (id < 0 || (size_t)id >= problems_.size() || !problems_[id]) return GOMILP_ERR_BAD_SHAPE;
     hipSetDevice(device_);
+    drop_kept(id);
     if (problems_[id]->is_child) {  // keep the buffers for the next child (no hipFree: it synchronises the device)
         child_pool_.push_back(std::move(problems_[id]));
         problems_[id].reset();
@@ -1211,6 +1214,12 @@ int Engine::lu_solve(const Problem &P, std::vector<double> &x, const double *rhs
 int Engine::solve(int64_t id, double tol, const int64_t *initial_basic, double *opt_f, double *opt_x, int32_t *has_x,
                   int64_t *basis_out, gomilp_lp_stats *stats) {
     std::lock_guard<std::mutex> g(mu_);
+    drop_kept(id);   // a kept state belongs to the solve that made it
+    return solve_cold_locked(id, tol, initial_basic, opt_f, opt_x, has_x, basis_out, stats);
+}
+
+int Engine::solve_cold_locked(int64_t id, double tol, const int64_t *initial_basic, double *opt_f, double *opt_x, int32_t *has_x,
+                              int64_t *basis_out, gomilp_lp_stats *stats) {
     xchg_timeout_ = false;
     int rc = solve_locked(id, tol, initial_basic, opt_f, opt_x, has_x, basis_out, stats);
     if (rc == GOMILP_ERR_DEVICE && xchg_timeout_ && bt_groups_ >= 0) {
@@ -1517,9 +1526,19 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
     }
     loop_rc = run_loop(P, 2, tol, (int)nonbasic.size(), P.dc, st);
     }  // revised-simplex pipelines
-    if (loop_rc == GOMILP_ERR_DEVICE) return finish(loop_rc);
+    rc = solve_tail(P, id, loop_rc, basic, xb, basic_start, unit_basis ? &rho : nullptr, opt_f, opt_x, has_x, basis_out, st);
+    return finish(rc);
+}
+
+int Engine::solve_tail(const Problem &P, int64_t id, int loop_rc, std::vector<int32_t> &basic, std::vector<double> &xb,
+                       const std::vector<int32_t> &basic_start, const std::vector<int32_t> *rho_slack, double *opt_f, double *opt_x,
+                       int32_t *has_x, int64_t *basis_out, gomilp_lp_stats *st) {
+    const double inf = std::numeric_limits<double>::infinity();
+    const int m = P.m, n = P.n;
+    Work &w = *w_;
+    if (loop_rc == GOMILP_ERR_DEVICE) return loop_rc;
     const bool loop_unbounded = loop_rc == GOMILP_ERR_UNBOUNDED;   // :261-263, :272-274 — after the condition guards below
-    if (loop_unbounded && !shadow_trace_) { *opt_f = -inf; return finish(loop_rc); }
+    if (loop_unbounded && !shadow_trace_) { *opt_f = -inf; return loop_rc; }
 
     // ---- epilogue (simplex.go:296-301): x_B from a fresh gonum-order solve on the final basis ----
     HIP_TRY(hipMemcpyAsync(w.h_idx, w.basic, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
@@ -1553,14 +1572,15 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
                 if (basis_out) for (int i = 0; i < m; i++) basis_out[i] = bas[i];
                 st->pivots_phase2 = stop;
                 shadow_trace_ = false;
-                return finish(cst);
+                return cst;
             }
         }
     }
     shadow_trace_ = false;
-    if (loop_unbounded) { *opt_f = -inf; return finish(loop_rc); }
-    rc = epilogue(P, basic, xb, loop_rc, opt_f, opt_x, has_x, basis_out, st);
-    if (rc == GOMILP_ERR_DEVICE) return finish(rc);
+    if (loop_unbounded) { *opt_f = -inf; return loop_rc; }
+    if (keep_id_ == id && loop_rc == GOMILP_OK) keep_capture(P, id, st->pipeline, basic, basic_start, rho_slack);
+    const int rc = epilogue(P, basic, xb, loop_rc, opt_f, opt_x, has_x, basis_out, st);
+    if (rc == GOMILP_ERR_DEVICE) return rc;
     if (trace_on_) {
         HIP_TRY(hipMemcpyAsync(w.st_host, w.st, sizeof(DevState), hipMemcpyDeviceToHost, stream_));
         HIP_TRY(sync_stream());
@@ -1575,7 +1595,7 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
             last_trace_[i].entering = tmp[i].entering; last_trace_[i].leaving = tmp[i].leaving;
         }
     }
-    return finish(rc);
+    return rc;
 }
 
 // x_B = ab^-1 b from a fresh gonum-order LU of the final basis (the device list w.basic must hold `basic`), z = DotUnitary,

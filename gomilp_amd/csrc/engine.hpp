@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -70,9 +71,39 @@ class Engine {
     int64_t upload_child_of(Engine &owner, int64_t root, int K, const int32_t *var, const double *sign, const double *rhs);
     int solve(int64_t id, double tol, const int64_t *initial_basic, double *opt_f, double *opt_x, int32_t *has_x,
               int64_t *basis_out, gomilp_lp_stats *stats);
+    // gomilp_lp_solve_warm (engine_warm.cpp): a dual simplex from the kept state of `parent` (< 0: cold), keeping this problem's
+    // final state when `keep`
+    int solve_warm(int64_t id, int64_t parent, int keep, int dual_budget, double tol, double *opt_f, double *opt_x, int32_t *has_x,
+                   int64_t *basis_out, gomilp_lp_stats *stats, gomilp_warm_stats *wstats);
    private:
     int solve_locked(int64_t id, double tol, const int64_t *initial_basic, double *opt_f, double *opt_x, int32_t *has_x,
                      int64_t *basis_out, gomilp_lp_stats *stats);
+    // solve_locked, repeated once on the single-workgroup kernels after an exchange timeout (Engine::solve)
+    int solve_cold_locked(int64_t id, double tol, const int64_t *initial_basic, double *opt_f, double *opt_x, int32_t *has_x,
+                          int64_t *basis_out, gomilp_lp_stats *stats);
+    // everything after the Phase-II loop of a solve (engine.cpp): the condition replay of small bases, the epilogue, the trace; keeps the
+    // final state when keep_id_ asks for it.  rho_slack: the rows of the slack-basis start (basic_start), null for other starts
+    int solve_tail(const Problem &P, int64_t id, int loop_rc, std::vector<int32_t> &basic, std::vector<double> &xb,
+                   const std::vector<int32_t> &basic_start, const std::vector<int32_t> *rho_slack, double *opt_f, double *opt_x,
+                   int32_t *has_x, int64_t *basis_out, gomilp_lp_stats *st);
+    // ---- single-context warm start (engine_warm.cpp) ----
+    struct Kept {                    // the final state of a solved problem: positional basis + explicit B^-1 (m x ld)
+        double *d = nullptr;         // null: nothing kept (no_warm: the pipeline that ran has no way to give its B^-1)
+        size_t cap = 0;              // doubles
+        int m = 0, ld = 0;
+        bool no_warm = false;
+        std::vector<int32_t> basic;
+    };
+    std::map<int64_t, Kept> kept_;                        // by problem id
+    std::vector<std::pair<double *, size_t>> keep_pool_;  // released B^-1 buffers (no hipFree per node: it synchronises the device)
+    int64_t keep_id_ = -1;                                // the solve running keeps its final state under this id
+    void keep_capture(const Problem &P, int64_t id, int pipeline, const std::vector<int32_t> &basic, const std::vector<int32_t> &basic_start,
+                      const std::vector<int32_t> *rho_slack);
+    void drop_kept(int64_t id);
+    bool descendant(const Problem &P, int64_t parent, int *J) const;
+    int warm_locked(int64_t id, const Kept &K, int J, int dual_budget, double tol, double *opt_f, double *opt_x, int32_t *has_x,
+                    int64_t *basis_out, gomilp_lp_stats *st, gomilp_warm_stats *ws);
+    int run_dual_loop(const Problem &P, double tol, int nn, int dual_budget, gomilp_warm_stats *ws);
    public:
     int64_t last_trace(gomilp_pivot *out, int64_t cap);
 
@@ -248,6 +279,11 @@ int launch_ftran(const LPArgs &a, int nparts_price, int forced_pos, int forced_v
                  hipEvent_t e1 = nullptr);
 void launch_update(const LPArgs &a, int nparts_ratio, int forced_p, int no_swap, int bland, hipStream_t s,
                    hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// dual_kernels.hip (warm start)
+void launch_dual_leave(const double *xb, int m, double tol, DevState *st, hipStream_t s);
+int launch_dual_price(const LPArgs &a, hipStream_t s);
+void launch_warm_binv(const double *Bp, int ldp, int mp, double *B, int ld, int m, const int32_t *kpos, const double *ksign, hipStream_t s);
+void launch_tab_to_binv(const double *T, int ldt, bool tiled, int m, const int32_t *src, double *B, int ld, hipStream_t s);
 // fused_kernels.hip
 bool fused_supported(int ld);
 int launch_price_fused(const LPArgs &a, const double *y_in, double *y_out, int pending, int nparts_ratio, hipStream_t s,

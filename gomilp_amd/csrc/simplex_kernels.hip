@@ -52,7 +52,8 @@ __global__ __launch_bounds__(kBlock) void k_price(LPArgs a) {
 // ------------------------------------------------------------------------------------------------
 // K2  FTRAN + ratio test:  d' = Binv a_q ; move_i = x_B[i]/|d_i| for d_i = -d'_i < 0 (simplex.go:306-342),
 //     fused first-index argmin of move (:268).   traffic: m*m*8 bytes read (B^-1 once)
-//     forced_pos >= 0: entering position given (Bland / setup); forced_var >= 0: entering variable id given.
+//     forced_pos >= 0: entering position given (Bland / setup); forced_var >= 0: entering variable id given;
+//     forced_pos = kDualPick: the dual pivot's entering position, from the partials of k_dual_price (dual_kernels.hip).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_ftran(LPArgs a, int nparts_price, int forced_pos, int forced_var) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
@@ -64,6 +65,15 @@ __global__ __launch_bounds__(kBlock) void k_ftran(LPArgs a, int nparts_price, in
     int var;
     if (forced_var >= 0) {
         var = forced_var;
+    } else if (q == kDualPick) {
+        unsigned long long key;
+        q = (int)reduce_partials(a.pk_price, a.pi_price, nparts_price, sk, si, &key);
+        if (key >= ordkey(__builtin_inf())) {   // no alpha_pj < -1e-13 in row p: x_B[p] < 0 cannot be repaired, the LP is infeasible
+            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_DUAL_INFEASIBLE; }
+            return;
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) { st->q = q; st->rq = a.rvec[q]; }
+        var = a.nonbasic[q];
     } else {
         if (q < 0) {
             q = (int)reduce_partials(a.pk_price, a.pi_price, nparts_price, sk, si, nullptr);
@@ -100,7 +110,8 @@ __global__ __launch_bounds__(kBlock) void k_ftran(LPArgs a, int nparts_price, in
 // ------------------------------------------------------------------------------------------------
 // K3  basis change: rank-1 update of B^-1 (ping-pong), x_B, y, index swap (simplex.go:280-292 without
 //     the three fresh LU factorizations).   traffic: m*m*8 read + m*m*8 written
-//     forced_p >= 0: leaving position given.  no_swap: setup pivot (indices managed by the host).
+//     forced_p >= 0: leaving position given; kDualPick: the one k_dual_leave chose (DevState::p).  no_swap: setup pivot (indices
+//     managed by the host).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_update(LPArgs a, int nparts_ratio, int forced_p, int no_swap, int bland) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
@@ -108,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void k_update(LPArgs a, int nparts_ratio, i
     __shared__ unsigned int si[kWavesPerBlock];
     DevState *st = a.st;
     if (st->done) return;
-    int p = forced_p;
+    int p = forced_p == kDualPick ? st->p : forced_p;
     if (p < 0) {
         p = (int)reduce_partials(a.pk_ratio, a.pi_ratio, nparts_ratio, sk, si, nullptr);
         const double mv = a.move[p];
@@ -247,6 +258,15 @@ __global__ __launch_bounds__(kBlock) void k_ftran_ck(LPArgs a, int nparts_price,
     int var;
     if (forced_var >= 0) {
         var = forced_var;
+    } else if (q == kDualPick) {
+        unsigned long long key;
+        q = (int)reduce_partials(a.pk_price, a.pi_price, nparts_price, sk, si, &key);
+        if (key >= ordkey(__builtin_inf())) {   // no alpha_pj < -1e-13 in row p: x_B[p] < 0 cannot be repaired, the LP is infeasible
+            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_DUAL_INFEASIBLE; }
+            return;
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) { st->q = q; st->rq = a.rvec[q]; }
+        var = a.nonbasic[q];
     } else {
         if (q < 0) {
             q = (int)reduce_partials(a.pk_price, a.pi_price, nparts_price, sk, si, nullptr);
@@ -292,7 +312,7 @@ __global__ __launch_bounds__(kBlock) void k_update_ck(LPArgs a, int nparts_ratio
     __shared__ unsigned int si[kWavesPerBlock];
     DevState *st = a.st;
     if (st->done) return;
-    int p = forced_p;
+    int p = forced_p == kDualPick ? st->p : forced_p;
     if (p < 0) {
         p = (int)reduce_partials(a.pk_ratio, a.pi_ratio, nparts_ratio, sk, si, nullptr);
         const double mv = a.move[p];

@@ -43,6 +43,17 @@ class Stats(C.Structure):
     ]
 
 
+class WarmStats(C.Structure):
+    """gomilp_warm_stats (include/gomilp_lp.h): what gomilp_lp_solve_warm did."""
+    _fields_ = [("warm_started", C.c_int32), ("fallback", C.c_int32), ("new_rows", C.c_int32), ("kept", C.c_int32),
+                ("pivots_dual", C.c_int64), ("keep_bytes", C.c_int64), ("seconds_setup", C.c_double), ("seconds_dual", C.c_double)]
+
+
+# WarmStats.fallback
+WARM_FALLBACKS = {0: "none", 1: "no parent", 2: "parent not kept", 3: "not a descendant", 4: "dual budget spent",
+                  5: "no warm path for this mode / shape"}
+
+
 class Pivot(C.Structure):
     _fields_ = [("phase", C.c_int32), ("bland", C.c_int32), ("min_idx", C.c_int64), ("replace", C.c_int64),
                 ("entering", C.c_int64), ("leaving", C.c_int64)]
@@ -59,7 +70,7 @@ class FrontierStats(C.Structure):
 
 
 EXPORTS = [
-    "gomilp_frontier_solve_warm", "gomilp_pool_release_warm",
+    "gomilp_lp_solve_warm", "gomilp_frontier_solve_warm", "gomilp_pool_release_warm",
     "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond",
     "gomilp_lp_simplex", "gomilp_ctx_create", "gomilp_ctx_destroy", "gomilp_ctx_device", "gomilp_ctx_set",
     "gomilp_lp_upload", "gomilp_lp_free", "gomilp_lp_solve_resident", "gomilp_lp_last_trace", "gomilp_version",
@@ -91,6 +102,8 @@ def lib():
     L.gomilp_lp_free.argtypes = [C.c_void_p, C.c_int64]
     L.gomilp_lp_solve_resident.argtypes = [C.c_void_p, C.c_int64, C.c_double, ip, dp, dp, C.POINTER(C.c_int32), ip,
                                            C.POINTER(Stats)]
+    L.gomilp_lp_solve_warm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, dp, dp,
+                                       C.POINTER(C.c_int32), ip, C.POINTER(Stats), C.POINTER(WarmStats)]
     L.gomilp_lp_last_trace.restype = C.c_int64
     L.gomilp_lp_last_trace.argtypes = [C.c_void_p, C.POINTER(Pivot), C.c_int64]
     L.gomilp_lp_simplex.argtypes = [dp, dp, C.c_int64, dp, C.c_int64, C.c_int64, C.c_double, ip, dp, dp,
@@ -244,19 +257,31 @@ class ResidentLP:
             raise RuntimeError("gomilp_lp_upload_child failed: %s" % STATUS_NAMES.get(-pid, -pid))
         return ResidentLP(self.ctx, pid, self.m + K, self.n + K)
 
-    def solve(self, tol: float = 0.0, trace: bool = False, initial_basic=None) -> LPResult:
+    def solve(self, tol: float = 0.0, trace: bool = False, initial_basic=None, parent: "Optional[ResidentLP]" = None,
+              keep: bool = False, dual_budget: int = 0) -> LPResult:
+        """Solve on the device.  With parent / keep / dual_budget the call is gomilp_lp_solve_warm: start from the kept final state
+        of `parent` (a ResidentLP solved with keep=True that this problem descends from; None: cold), keep this problem's final
+        state for its own children when `keep`; stats["warm"] holds the WarmStats."""
         L = lib()
         ib = None if initial_basic is None else np.ascontiguousarray(initial_basic, dtype=np.int64)
         if ib is not None and ib.shape != (self.m,):
             raise ValueError("lp: incorrect number of initial vectors")   # simplex.go:149-151 panics
+        warm = parent is not None or keep or dual_budget != 0
+        if warm and ib is not None:
+            raise ValueError("a warm start takes no initial basis")
         x = np.zeros(self.n)
         basis = np.zeros(self.m, dtype=np.int64)
         z = C.c_double(math.nan)
         has_x = C.c_int32(0)
         st = Stats()
+        ws = WarmStats()
         self.ctx.set("trace", 1 if trace else 0)
-        rc = L.gomilp_lp_solve_resident(self.ctx._h, self.pid, float(tol), _ip(ib) if ib is not None else None, C.byref(z), _dp(x), C.byref(has_x),
-                                        _ip(basis), C.byref(st))
+        if warm:
+            rc = L.gomilp_lp_solve_warm(self.ctx._h, self.pid, -1 if parent is None else parent.pid, 1 if keep else 0, int(dual_budget),
+                                        float(tol), C.byref(z), _dp(x), C.byref(has_x), _ip(basis), C.byref(st), C.byref(ws))
+        else:
+            rc = L.gomilp_lp_solve_resident(self.ctx._h, self.pid, float(tol), _ip(ib) if ib is not None else None, C.byref(z), _dp(x),
+                                            C.byref(has_x), _ip(basis), C.byref(st))
         piv = []
         if trace:
             total = L.gomilp_lp_last_trace(self.ctx._h, None, 0)
@@ -264,8 +289,11 @@ class ResidentLP:
                 buf = (Pivot * total)()
                 L.gomilp_lp_last_trace(self.ctx._h, buf, total)
                 piv = [(p.phase, p.bland, p.min_idx, p.replace, p.entering, p.leaving) for p in buf]
+        stats = _stats_dict(st)
+        if warm:
+            stats["warm"] = {k: getattr(ws, k) for k, _ in WarmStats._fields_}
         return LPResult(rc, z.value, x if has_x.value else None,
-                        basis if has_x.value and self.m != self.n else None, _stats_dict(st), piv)
+                        basis if has_x.value and self.m != self.n else None, stats, piv)
 
     def free(self) -> None:
         if self.pid >= 0:

@@ -74,7 +74,7 @@ typedef struct gomilp_lp_stats {
 
 /* One record per pivot, execution order (Phase I first).  Same fields as the oracle's trace. */
 typedef struct gomilp_pivot {
-    int32_t phase;    /* 1 = Phase I, 2 = Phase II */
+    int32_t phase;    /* 1 = Phase I, 2 = Phase II, 3 = dual pivot of a warm start (gomilp_lp_solve_warm) */
     int32_t bland;    /* 1 when chosen by the Bland rule */
     int64_t min_idx;  /* position in nonBasicIdx (simplex.go:247) */
     int64_t replace;  /* position in basicIdxs   (simplex.go:268) */
@@ -142,8 +142,9 @@ int gomilp_ctx_device(const gomilp_ctx *ctx);
  * gomilp_lp_upload + gomilp_lp_solve_resident, and gomilp_lp_upload_child on such a root; with the statuses, trace, basis and point
  * semantics of the same pipelines at 8192 rows.  A shape whose buffers (A^T, the two B^-1 copies, the final solve's matrices, the
  * tableau) do not fit the free device memory returns GOMILP_ERR_UNSUPPORTED before anything is allocated; the context stays usable.
+ * Warm starts on a context (gomilp_lp_solve_warm) work there too: the dual loop runs on the same chunked revised-simplex kernels.
  * Still GOMILP_ERR_UNSUPPORTED beyond 8192 rows: non-slack starts (equality rows, a supplied initial_basic, m >= n), frontier pools
- * (gomilp_pool_set_root, their waves and warm starts), and exact_degenerate = 3 (the blocked tableau does not run there).  The final
+ * (gomilp_pool_set_root, their waves and their warm starts), and exact_degenerate = 3 (the blocked tableau does not run there).  The final
  * solve of those bases takes the one-launch-per-column LU (k_lu_step): seconds, not milliseconds. */
 int gomilp_ctx_set(gomilp_ctx *ctx, const char *key, int64_t value);
 
@@ -169,6 +170,43 @@ int64_t gomilp_lp_last_trace(gomilp_ctx *ctx, gomilp_pivot *out, int64_t cap);
  * first n0 like subproblem.go:157-159) or -(gomilp_status). */
 int64_t gomilp_lp_upload_child(gomilp_ctx *ctx, int64_t root_problem, int32_t K, const int32_t *var, const double *sign,
                                const double *rhs);
+
+/* ------------------------------------------------------------------------------------------
+ * Warm start on a context: a child starts from the kept final state of its parent — the parent's basis
+ * plus the slacks of the new branch rows, dual feasible — and a dual simplex on the revised-simplex kernels repairs the rows the
+ * parent violates; a primal Phase-II loop (usually 0 pivots) and the usual final solve follow.  At every row count a context
+ * solves, beyond 8192 rows included.  Parity (as gomilp_frontier_solve_warm): status, branching decisions, |z - z_cold| <= 1e-9
+ * max(1, |z_cold|); not the reference's pivot path.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct gomilp_warm_stats {
+    int32_t warm_started;   /* 1: the solve started from the parent's basis */
+    int32_t fallback;       /* why it ran cold: 0 none, 1 parent < 0, 2 parent has no kept state, 3 not a descendant,
+                               4 dual-pivot budget spent (then solved cold in the same call), 5 mode / shape without a warm path */
+    int32_t new_rows;       /* J: branch rows the problem has beyond the parent */
+    int32_t kept;           /* 1: this problem's final state is now kept (keep != 0, status OK, and it fit in device memory) */
+    int64_t pivots_dual;
+    int64_t keep_bytes;
+    double seconds_setup;   /* building the child's B^-1 / x_B from the parent's state */
+    double seconds_dual;    /* dual loop (HIP events) */
+} gomilp_warm_stats;
+
+/* Solve `problem`, warm from `parent`, and keep its final state when `keep` != 0.
+ *   parent < 0       a cold solve, bit for bit gomilp_lp_solve_resident, plus keeping (how a root gets kept).
+ *   keep != 0        when the status is GOMILP_OK the final positional basis and an explicit B^-1 (m x ld doubles: 538 MB at
+ *                    8200 rows) stay on the device with the problem, if they fit the free device memory; gomilp_lp_free(problem)
+ *                    and the next solve of the same problem drop them.
+ *   descendant       `problem` was assembled by gomilp_lp_upload_child from `parent` itself (J = its K rows), or both come from
+ *                    the same root and the parent's (var, sign, rhs) rows are a bitwise prefix of the problem's (J = K - K_parent).
+ *                    Any J >= 1.  Anything else runs cold with fallback = 3 (not an error).
+ *   dual_budget      dual pivots before the call gives up the warm start (0: 64) and solves the problem cold, fallback = 4: the
+ *                    result is then bit-identical to gomilp_lp_solve_resident.
+ *   A child the dual loop proves infeasible returns GOMILP_ERR_INFEASIBLE without x.  exact_degenerate = 3, and parents that
+ *   started from a non-slack basis on a tableau pipeline, run cold with fallback = 5.
+ *   Dual pivots are recorded in the trace with phase = 3, ahead of the Phase-II pivots; stats->pivots_phase2 counts the latter.
+ *   wstats may be NULL. */
+int gomilp_lp_solve_warm(gomilp_ctx *ctx, int64_t problem, int64_t parent, int32_t keep, int32_t dual_budget, double tol,
+                         double *opt_f, double *opt_x, int32_t *has_x, int64_t *basis_out,
+                         gomilp_lp_stats *stats, gomilp_warm_stats *wstats);
 
 /* ------------------------------------------------------------------------------------------
  * Frontier API: one FIFO level of the enumeration tree (independent relaxations sharing the root data,
