@@ -38,38 +38,9 @@ __global__ __launch_bounds__(kBlock) void k_dual_leave(const double *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
-// dual pricing: both dots of one row of At against the two staged vectors over the chunk [c0, c1) — per vector exactly the
-// accumulation of wave_dot_chunk (kernels_common.h), so the one-pass form (one chunk [0, ld2)) and the chunked form agree bit for bit.
-// The row is read once for both.
+// dual pricing: per nonbasic column a_j.y and a_j.rho, the row of At read once for both (kernels_common.h: wave_dot_chunk<2>),
+// so the one-pass form (one chunk [0, ld2)) and the chunked form (dot_group<2>) agree bit for bit.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_dot2_chunk(const double *__restrict__ row, const double2 *__restrict__ sy,
-                                                const double2 *__restrict__ sr, int c0, int c1, int ld2, int lane, DotAcc &ay,
-                                                DotAcc &ar) {
-    const double2 *r2 = reinterpret_cast<const double2 *>(row);
-    int c = c0 + lane;
-    for (; c + 192 < c1; c += 256) {
-        const double2 v0 = r2[c], v1 = r2[c + 64], v2 = r2[c + 128], v3 = r2[c + 192];
-        const int o = c - c0;
-        const double2 y0 = sy[o], y1 = sy[o + 64], y2 = sy[o + 128], y3 = sy[o + 192];
-        ay.a0 += v0.x * y0.x + v0.y * y0.y;
-        ay.a1 += v1.x * y1.x + v1.y * y1.y;
-        ay.a2 += v2.x * y2.x + v2.y * y2.y;
-        ay.a3 += v3.x * y3.x + v3.y * y3.y;
-        const double2 s0 = sr[o], s1 = sr[o + 64], s2 = sr[o + 128], s3 = sr[o + 192];
-        ar.a0 += v0.x * s0.x + v0.y * s0.y;
-        ar.a1 += v1.x * s1.x + v1.y * s1.y;
-        ar.a2 += v2.x * s2.x + v2.y * s2.y;
-        ar.a3 += v3.x * s3.x + v3.y * s3.y;
-    }
-    if (c1 == ld2) {   // the last chunk: the tail of wave_dot_row
-        for (; c < ld2; c += 64) {
-            const double2 v0 = r2[c];
-            const double2 y0 = sy[c - c0], s0 = sr[c - c0];
-            ay.a0 += v0.x * y0.x + v0.y * y0.y;
-            ar.a0 += v0.x * s0.x + v0.y * s0.y;
-        }
-    }
-}
 
 // r_pos = cost[j] - a_j.y (kept in rvec for k_ftran / k_update), the ratio key of column pos
 __device__ __forceinline__ unsigned long long dual_key(const LPArgs &a, int pos, double dy, double da, int lane) {
@@ -97,62 +68,37 @@ __global__ __launch_bounds__(kBlock) void k_dual_price(LPArgs a) {
     unsigned long long bk = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
     for (int pos = wave; pos < a.nn; pos += nwaves) {
-        DotAcc ay = {0, 0, 0, 0}, ar = {0, 0, 0, 0};
-        wave_dot2_chunk(a.At + (size_t)a.nonbasic[pos] * a.ld, sy, sr, 0, ld2, ld2, lane, ay, ar);
-        amin_take(bk, bi, dual_key(a, pos, wave_dot_finish(ay), wave_dot_finish(ar), lane), (unsigned int)pos);
+        DotAcc acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        wave_dot_chunk<2>(a.At + (size_t)a.nonbasic[pos] * a.ld, svec, ld2, 0, ld2, ld2, lane, acc);
+        amin_take(bk, bi, dual_key(a, pos, wave_dot_finish(acc[0]), wave_dot_finish(acc[1]), lane), (unsigned int)pos);
     }
-    block_argmin(bk, bi, sk, si);
-    if (threadIdx.x == 0) { a.pk_price[blockIdx.x] = bk; a.pi_price[blockIdx.x] = bi; }
+    publish_partials(bk, bi, sk, si, a.pk_price, a.pi_price);
 }
 
-// chunked form: the two vectors streamed through LDS ck2 double2 at a time (a multiple of 256), rows taken kDualCkRows per wave
-// as simplex_kernels.hip's dot_group does, the loops run to workgroup-uniform bounds (every thread reaches every barrier)
-constexpr int kDualCkRows = 4;
-
+// chunked form: y and rho streamed through LDS ck2 double2 each at a time
 __global__ __launch_bounds__(kBlock) void k_dual_price_ck(LPArgs a, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
     DevState *st = a.st;
     if (st->done) return;
-    const int ld2 = a.ld >> 1;
-    double2 *sy = svec, *sr = svec + ck2;
-    const double2 *y2 = reinterpret_cast<const double2 *>(a.y);
-    const double2 *rho2 = reinterpret_cast<const double2 *>(a.binv_cur + (size_t)st->p * a.ld);
+    const double *rho = a.binv_cur + (size_t)st->p * a.ld;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
     const int kmax = (a.nn + nwaves - 1) / nwaves;
     unsigned long long bk = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
-    for (int k0 = 0; k0 < kmax; k0 += kDualCkRows) {
-        const double *rowp[kDualCkRows];
-        DotAcc ay[kDualCkRows], ar[kDualCkRows];
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        double dot[kCkRows][2];
+        dot_group<2>(a.At, a.ld, a.nonbasic, a.nn, k0, wave, nwaves, {a.y, rho}, svec, ck2, lane, dot);
 #pragma unroll
-        for (int r = 0; r < kDualCkRows; r++) {
+        for (int r = 0; r < kCkRows; r++) {
             const int pos = wave + (k0 + r) * nwaves;
-            rowp[r] = pos < a.nn ? a.At + (size_t)a.nonbasic[pos] * a.ld : nullptr;
-            ay[r].a0 = ay[r].a1 = ay[r].a2 = ay[r].a3 = 0;
-            ar[r].a0 = ar[r].a1 = ar[r].a2 = ar[r].a3 = 0;
-        }
-        for (int c0 = 0; c0 < ld2; c0 += ck2) {
-            const int c1 = min(c0 + ck2, ld2);
-            __syncthreads();   // the previous chunk is no longer read
-            for (int c = threadIdx.x; c < c1 - c0; c += kBlock) { sy[c] = y2[c0 + c]; sr[c] = rho2[c0 + c]; }
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < kDualCkRows; r++)
-                if (rowp[r]) wave_dot2_chunk(rowp[r], sy, sr, c0, c1, ld2, lane, ay[r], ar[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < kDualCkRows; r++) {
-            const int pos = wave + (k0 + r) * nwaves;
-            if (pos >= a.nn) continue;
-            amin_take(bk, bi, dual_key(a, pos, wave_dot_finish(ay[r]), wave_dot_finish(ar[r]), lane), (unsigned int)pos);
+            if (pos < a.nn) amin_take(bk, bi, dual_key(a, pos, dot[r][0], dot[r][1], lane), (unsigned int)pos);
         }
     }
-    block_argmin(bk, bi, sk, si);
-    if (threadIdx.x == 0) { a.pk_price[blockIdx.x] = bk; a.pi_price[blockIdx.x] = bi; }
+    publish_partials(bk, bi, sk, si, a.pk_price, a.pi_price);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -197,18 +143,12 @@ __global__ __launch_bounds__(kBlock) void k_tab_to_binv(const double *__restrict
 // ------------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------------
-static inline int grid_for_cols(int rows) {
-    int g = (rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (g > kMaxPartials) g = kMaxPartials;
-    return g < 1 ? 1 : g;
-}
-
 void launch_dual_leave(const double *xb, int m, double tol, DevState *st, hipStream_t s) {
     hipLaunchKernelGGL(k_dual_leave, dim3(1), dim3(kBlock), 0, s, xb, m, tol, st);
 }
 
 int launch_dual_price(const LPArgs &a, hipStream_t s) {
-    const int g = grid_for_cols(a.nn);
+    const int g = grid_for_rows(a.nn);
     // one pass while both vectors fit the 64 KB window; else (and whenever the row_chunk knob forces it) the chunked form
     if (a.row_chunk2 == 0 && a.ld <= kDualOnePassLd) {
         hipLaunchKernelGGL(k_dual_price, dim3(g), dim3(kBlock), (size_t)2 * a.ld * sizeof(double), s, a);

@@ -22,6 +22,14 @@ inline void lds_attr_once(const void *fn, int bytes) {
     if (done.insert(std::make_pair(dev, fn)).second) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
+// workgroups for a wave-per-row kernel over `rows` rows (at most kMaxPartials: one argmin partial per workgroup)
+static inline int grid_for_rows(int rows) {
+    int g = (rows + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (g > kMaxPartials) g = kMaxPartials;
+    if (g < 1) g = 1;
+    return g;
+}
+
 // ------------------------------------------------------------------------------------------------
 // helpers
 // ------------------------------------------------------------------------------------------------
@@ -253,28 +261,6 @@ __device__ __forceinline__ double div_pos(double x, double d) {
     return __builtin_fma(rem, r, q);
 }
 
-// dot of one padded row (ld doubles, 16-byte aligned) with the LDS-staged vector; result in all lanes
-__device__ __forceinline__ double wave_dot_row(const double *__restrict__ row, const double2 *__restrict__ svec,
-                                               int ld2, int lane) {
-    const double2 *r2 = reinterpret_cast<const double2 *>(row);
-    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-    int c = lane;
-    for (; c + 192 < ld2; c += 256) {
-        double2 v0 = r2[c], v1 = r2[c + 64], v2 = r2[c + 128], v3 = r2[c + 192];
-        double2 s0 = svec[c], s1 = svec[c + 64], s2 = svec[c + 128], s3 = svec[c + 192];
-        a0 += v0.x * s0.x + v0.y * s0.y;
-        a1 += v1.x * s1.x + v1.y * s1.y;
-        a2 += v2.x * s2.x + v2.y * s2.y;
-        a3 += v3.x * s3.x + v3.y * s3.y;
-    }
-    for (; c < ld2; c += 64) {
-        double2 v0 = r2[c];
-        double2 s0 = svec[c];
-        a0 += v0.x * s0.x + v0.y * s0.y;
-    }
-    return wave_sum((a0 + a1) + (a2 + a3));
-}
-
 // element (i, j) of the tableau T in either layout: row-major, or the 4x4 tiles of the blocked pipeline (bt_kernels.hip:
 // tile (I, J) at ((I * ldt/4) + J) * 16, element (i&3)*4 + (j&3))
 __device__ __forceinline__ size_t tab_idx(int i, int j, int ldt, int tiled) {
@@ -289,46 +275,110 @@ __device__ __forceinline__ void stage_vec(double2 *__restrict__ svec, const doub
 }
 
 // ------------------------------------------------------------------------------------------------
-// Chunked staging (vectors longer than the LDS window): the vector goes through LDS in chunks of
-// ck2 double2 (a multiple of 256), and wave_dot_row's four accumulators are carried from chunk to chunk.  A chunk
-// [c0, c1) that is not the last one holds whole 256-wide steps of wave_dot_row's main loop, so every lane adds the
-// same terms into the same accumulator in the same order as the one-pass form: the result is bit-identical.
+// Row dot products against LDS-staged vectors.  One pass stages the whole vector; the chunked form (vectors longer than the
+// LDS window) stages it in chunks of ck2 double2 (a multiple of 256) and carries the four accumulators of
+// wave_dot_chunk from chunk to chunk.  A chunk [c0, c1) that is not the last one holds whole 256-wide steps of the main
+// loop, so every lane adds the same terms into the same accumulator in the same order as one pass over [0, ld2): the
+// result is bit-identical.
 // ------------------------------------------------------------------------------------------------
 struct DotAcc {
     double a0, a1, a2, a3;
 };
 
-// (every thread of the workgroup: a barrier in front, so that the previous chunk is no longer read, and one behind)
-__device__ __forceinline__ void stage_chunk(double2 *__restrict__ svec, const double *__restrict__ src, int c0, int c1) {
-    const double2 *s2 = reinterpret_cast<const double2 *>(src) + c0;
-    __syncthreads();
-    for (int c = threadIdx.x; c < c1 - c0; c += kBlock) svec[c] = s2[c];
-    __syncthreads();
-}
-
-// the part of wave_dot_row that falls into the staged chunk [c0, c1) of a row of ld2 double2 (svec holds element c0 at 0)
-__device__ __forceinline__ void wave_dot_chunk(const double *__restrict__ row, const double2 *__restrict__ svec, int c0, int c1,
-                                               int ld2, int lane, DotAcc &acc) {
+// the part of the dots of one padded row (ld2 double2, 16-byte aligned) with NV staged vectors that falls into the chunk
+// [c0, c1): vector v at svec + v * sstride, element c0 at offset 0.  The row is read once for all NV vectors.
+template <int NV>
+__device__ __forceinline__ void wave_dot_chunk(const double *__restrict__ row, const double2 *__restrict__ svec, int sstride, int c0,
+                                               int c1, int ld2, int lane, DotAcc (&acc)[NV]) {
     const double2 *r2 = reinterpret_cast<const double2 *>(row);
     int c = c0 + lane;
     for (; c + 192 < c1; c += 256) {
-        double2 v0 = r2[c], v1 = r2[c + 64], v2 = r2[c + 128], v3 = r2[c + 192];
-        const int o = c - c0;
-        double2 s0 = svec[o], s1 = svec[o + 64], s2 = svec[o + 128], s3 = svec[o + 192];
-        acc.a0 += v0.x * s0.x + v0.y * s0.y;
-        acc.a1 += v1.x * s1.x + v1.y * s1.y;
-        acc.a2 += v2.x * s2.x + v2.y * s2.y;
-        acc.a3 += v3.x * s3.x + v3.y * s3.y;
+        const double2 v0 = r2[c], v1 = r2[c + 64], v2 = r2[c + 128], v3 = r2[c + 192];
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+            const double2 *s = svec + v * sstride + (c - c0);
+            const double2 s0 = s[0], s1 = s[64], s2 = s[128], s3 = s[192];
+            acc[v].a0 += v0.x * s0.x + v0.y * s0.y;
+            acc[v].a1 += v1.x * s1.x + v1.y * s1.y;
+            acc[v].a2 += v2.x * s2.x + v2.y * s2.y;
+            acc[v].a3 += v3.x * s3.x + v3.y * s3.y;
+        }
     }
-    if (c1 == ld2) {   // the last chunk: wave_dot_row's tail
+    if (c1 == ld2) {   // the last chunk: the tail
         for (; c < ld2; c += 64) {
-            double2 v0 = r2[c];
-            double2 s0 = svec[c - c0];
-            acc.a0 += v0.x * s0.x + v0.y * s0.y;
+            const double2 v0 = r2[c];
+#pragma unroll
+            for (int v = 0; v < NV; v++) {
+                const double2 s0 = svec[v * sstride + (c - c0)];
+                acc[v].a0 += v0.x * s0.x + v0.y * s0.y;
+            }
         }
     }
 }
 
 __device__ __forceinline__ double wave_dot_finish(const DotAcc &acc) { return wave_sum((acc.a0 + acc.a1) + (acc.a2 + acc.a3)); }
+
+// dot of one padded row (ld doubles, 16-byte aligned) with the whole LDS-staged vector; result in all lanes
+__device__ __forceinline__ double wave_dot_row(const double *__restrict__ row, const double2 *__restrict__ svec, int ld2, int lane) {
+    DotAcc acc[1] = {{0, 0, 0, 0}};
+    wave_dot_chunk<1>(row, svec, 0, 0, ld2, ld2, lane, acc);
+    return wave_dot_finish(acc[0]);
+}
+
+// chunk [c0, c1) of NV vectors into LDS (vector v at svec + v * sstride).  Every thread of the workgroup: a barrier in front, so
+// that the previous chunk is no longer read, and one behind.
+template <int NV>
+__device__ __forceinline__ void stage_chunk(double2 *__restrict__ svec, int sstride, const double *const (&src)[NV], int c0, int c1) {
+    const double2 *s2[NV];
+#pragma unroll
+    for (int v = 0; v < NV; v++) s2[v] = reinterpret_cast<const double2 *>(src[v]) + c0;
+    __syncthreads();
+    for (int c = threadIdx.x; c < c1 - c0; c += kBlock) {
+#pragma unroll
+        for (int v = 0; v < NV; v++) svec[v * sstride + c] = s2[v][c];
+    }
+    __syncthreads();
+}
+
+// The chunked kernels take a wave's rows (wave, wave + nwaves, ... as the one-pass kernels do) kCkRows at a time, and the
+// workgroup streams the vectors through LDS once per such group; the loops run to a workgroup-uniform bound, so every thread
+// reaches every barrier.
+constexpr int kCkRows = 4;
+
+// one group of up to kCkRows rows of a wave: dot[r][v] = M[row(r), :] . vec[v], valid where row(r) < rows (row(r) = rowmap[pos],
+// or pos without a rowmap); the NV vectors are staged ck2 double2 apart
+template <int NV>
+__device__ __forceinline__ void dot_group(const double *__restrict__ M, int ld, const int32_t *__restrict__ rowmap, int rows, int k0,
+                                          int wave, int nwaves, const double *const (&vec)[NV], double2 *svec, int ck2, int lane,
+                                          double (&dot)[kCkRows][NV]) {
+    const int ld2 = ld >> 1;
+    const double *rowp[kCkRows];
+    DotAcc acc[kCkRows][NV];
+#pragma unroll
+    for (int r = 0; r < kCkRows; r++) {
+        const int pos = wave + (k0 + r) * nwaves;
+        rowp[r] = pos < rows ? M + (size_t)(rowmap ? rowmap[pos] : pos) * ld : nullptr;
+#pragma unroll
+        for (int v = 0; v < NV; v++) acc[r][v].a0 = acc[r][v].a1 = acc[r][v].a2 = acc[r][v].a3 = 0;
+    }
+    for (int c0 = 0; c0 < ld2; c0 += ck2) {
+        const int c1 = min(c0 + ck2, ld2);
+        stage_chunk<NV>(svec, ck2, vec, c0, c1);
+#pragma unroll
+        for (int r = 0; r < kCkRows; r++)
+            if (rowp[r]) wave_dot_chunk<NV>(rowp[r], svec, ck2, c0, c1, ld2, lane, acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < kCkRows; r++)
+#pragma unroll
+        for (int v = 0; v < NV; v++) dot[r][v] = rowp[r] ? wave_dot_finish(acc[r][v]) : 0.0;
+}
+
+// the workgroup's first-index argmin into the per-workgroup partials that the next kernel reduces (reduce_partials)
+__device__ __forceinline__ void publish_partials(unsigned long long &bk, unsigned int &bi, unsigned long long *sk, unsigned int *si,
+                                                 unsigned long long *pk, unsigned int *pi) {
+    block_argmin(bk, bi, sk, si);
+    if (threadIdx.x == 0) { pk[blockIdx.x] = bk; pi[blockIdx.x] = bi; }
+}
 
 }  // namespace gomilp

@@ -18,6 +18,155 @@
 namespace gomilp {
 
 // ------------------------------------------------------------------------------------------------
+// K1-K3 come in two forms each: one pass (the m-long vector staged whole in LDS) and the chunked form *_ck (the vector streamed
+// through LDS in chunks, kernels_common.h: dot_group; for vectors longer than the LDS window, ld > 8192, or wherever the context
+// knob row_chunk forces it).  The two kernels of a pair differ only in their staging and row loops: the pivot rules, the
+// per-element work and the commit are the helpers below, so both forms take the same decisions from bit-identical values.
+// The helpers take the pointers they use, not the LPArgs: a reference to the kernel's argument hides from the compiler that those
+// pointers are kernel arguments that nothing in the kernel overwrites, and the kernel loses its scalar loads (rvec[q], nonbasic[q]).
+// ------------------------------------------------------------------------------------------------
+
+// K1's gate: false once the loop has stopped, and when the pivot budget is spent (ST_MAX_PIVOTS)
+__device__ __forceinline__ bool price_gate(DevState *st) {
+    if (st->done) return false;
+    if (st->max_pivots > 0 && st->pivots >= st->max_pivots) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_MAX_PIVOTS; }
+        return false;
+    }
+    return true;
+}
+
+// reduced cost of nonbasic position pos (variable j, dot = At[j,:].y): r = cost[j] - dot (simplex.go:242-243) into rvec and the
+// running first-index argmin (:247)
+__device__ __forceinline__ void price_elem(const double *cost, double *rvec, int pos, int j, double dot, int lane, unsigned long long &bk,
+                                           unsigned int &bi) {
+    const double r = cost[j] - dot;
+    if (lane == 0) rvec[pos] = r;
+    amin_take(bk, bi, ordkey(r), (unsigned int)pos);
+}
+
+// K2's entering variable, into var (wave-uniform).  forced_var >= 0: the variable given; forced_pos = kDualPick: the dual pivot's
+// entering position, from the partials of k_dual_price (dual_kernels.hip); forced_pos >= 0: the position given (Bland / setup);
+// else the first-index argmin of the reduced costs and the optimality test.  false: the loop has stopped or stops here.
+// (pk / pi: the pricing partials; rvec, nonbasic, tol as in LPArgs)
+__device__ __forceinline__ bool pick_entering(DevState *st, const unsigned long long *pk, const unsigned int *pi, int nparts_price,
+                                              const double *rvec, const int32_t *nonbasic, double tol, int forced_pos, int forced_var,
+                                              unsigned long long *sk, unsigned int *si, int &var) {
+    if (st->done) return false;
+    int q = forced_pos;
+    if (forced_var >= 0) {
+        var = forced_var;
+    } else if (q == kDualPick) {
+        unsigned long long key;
+        q = (int)reduce_partials(pk, pi, nparts_price, sk, si, &key);
+        if (key >= ordkey(__builtin_inf())) {   // no alpha_pj < -1e-13 in row p: x_B[p] < 0 cannot be repaired, the LP is infeasible
+            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_DUAL_INFEASIBLE; }
+            return false;
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) { st->q = q; st->rq = rvec[q]; }
+        var = nonbasic[q];
+    } else {
+        if (q < 0) {
+            q = (int)reduce_partials(pk, pi, nparts_price, sk, si, nullptr);
+            const double rq = rvec[q];
+            if (rq >= -tol) {  // simplex.go:248 — optimal
+                if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_OPTIMAL; st->q = q; st->rq = rq; }
+                return false;
+            }
+            if (blockIdx.x == 0 && threadIdx.x == 0) { st->q = q; st->rq = rq; }
+        } else if (blockIdx.x == 0 && threadIdx.x == 0) {
+            st->q = q; st->rq = rvec[q];
+        }
+        var = nonbasic[q];
+    }
+    return true;
+}
+
+// row i of the FTRAN (dp = B^-1[i,:].a_q): d = -d'_i, the ratio move_i = x_B[i]/|d_i| for d_i < 0 (simplex.go:306-342) into dvec /
+// move and the running first-index argmin of move (:268)
+__device__ __forceinline__ void ratio_elem(const double *xb, double *dvec, double *move, int i, double dp, int lane, unsigned long long &bk,
+                                           unsigned int &bi) {
+    double d = -dp;                       // simplex.go:319
+    if (fabs(d) < 1e-13) d = 0;           // dRoundTol, :321-325
+    const double mv = (d >= 0) ? __builtin_inf() : xb[i] / fabs(d);  // :334-340
+    if (lane == 0) { dvec[i] = dp; move[i] = mv; }
+    amin_take(bk, bi, ordkey(mv), (unsigned int)i);
+}
+
+// K3's leaving row, into p (wave-uniform).  forced_p >= 0: the row given; kDualPick: the one k_dual_leave chose (DevState::p); else
+// the first-index argmin of the ratios.  false: the loop has stopped or stops here (unbounded, or a degenerate step for Bland).
+// (pk / pi: the ratio partials)
+__device__ __forceinline__ bool pick_leaving(DevState *st, const unsigned long long *pk, const unsigned int *pi, int nparts_ratio,
+                                             const double *move, int forced_p, unsigned long long *sk, unsigned int *si, int &p) {
+    if (st->done) return false;
+    p = forced_p == kDualPick ? st->p : forced_p;
+    if (p < 0) {
+        p = (int)reduce_partials(pk, pi, nparts_ratio, sk, si, nullptr);
+        const double mv = move[p];
+        if (mv == __builtin_inf()) {  // no d_i < 0: unbounded (simplex.go:328-330)
+            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_UNBOUNDED; st->p = p; st->mv = mv; }
+            return false;
+        }
+        if (mv <= 0) {  // degenerate step -> Bland rule (simplex.go:269)
+            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_NEED_BLAND; st->p = p; st->mv = mv; }
+            return false;
+        }
+    }
+    return true;
+}
+
+// columns [c0, c1) of row i of the next B^-1 (rank-1 update with pivot row p, d'_p = dpv); rowp: old row p over the same columns
+// in LDS, element c0 at 0
+__device__ __forceinline__ void update_row(const double *binv_cur, double *binv_next, int ld, const double *dvec, int i, int p, double dpv,
+                                           const double2 *rowp, int c0, int c1, int lane) {
+    const double2 *src = reinterpret_cast<const double2 *>(binv_cur + (size_t)i * ld);
+    double2 *dst = reinterpret_cast<double2 *>(binv_next + (size_t)i * ld);
+    if (i == p) {
+        for (int c = c0 + lane; c < c1; c += 64) {
+            double2 v = rowp[c - c0];
+            v.x = v.x / dpv; v.y = v.y / dpv;
+            dst[c] = v;
+        }
+    } else {
+        const double f = dvec[i] / dpv;
+        for (int c = c0 + lane; c < c1; c += 64) {
+            double2 v = src[c];
+            const double2 rp = rowp[c - c0];
+            v.x = v.x - f * rp.x; v.y = v.y - f * rp.y;
+            dst[c] = v;
+        }
+    }
+}
+
+// the rest of K3, by workgroup 0 after its rows: x_B and y (O(m); nobody else touches them in this kernel), the index swap
+// (simplex.go:280), the trace record and the counters.  rowp: old row p of B^-1 (LDS in k_update, B^-1 itself in k_update_ck:
+// the same values).  (The other pointers and m, ld, trace_cap, phase as in LPArgs.)
+__device__ __forceinline__ void commit_pivot(DevState *st, double *xb, double *y, const double *dvec, const double *move, int32_t *basic,
+                                             int32_t *nonbasic, DevPivot *trace, int64_t trace_cap, int phase, int m, int ld, int p, double dpv,
+                                             const double *rowp, int no_swap, int bland) {
+    const double theta = xb[p] / dpv;
+    const double rq = no_swap ? 0.0 : st->rq;
+    const double alpha = rq / dpv;
+    __syncthreads();
+    for (int i = threadIdx.x; i < m; i += kBlock) xb[i] = (i == p) ? theta : xb[i] - theta * dvec[i];
+    for (int j = threadIdx.x; j < ld; j += kBlock) y[j] = y[j] + alpha * rowp[j];
+    if (threadIdx.x == 0) {
+        const int q = st->q;
+        st->p = p; st->dp = dpv; st->mv = move[p];
+        if (!no_swap) {
+            const int ent = nonbasic[q], lea = basic[p];
+            basic[p] = ent; nonbasic[q] = lea;  // simplex.go:280
+            if (trace && st->trace_len < trace_cap) {
+                DevPivot &t = trace[st->trace_len];
+                t.phase = phase; t.bland = bland; t.min_idx = q; t.replace = p; t.entering = ent; t.leaving = lea;
+            }
+            st->trace_len += 1;
+            st->pivots += 1;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K1  pricing:  r[pos] = cost[j] - At[j,:].y   (simplex.go:242-243), fused first-index argmin (:247)
 //     algorithmic traffic: m*(n-m)*8 bytes read (A_N once)
 // ------------------------------------------------------------------------------------------------
@@ -25,12 +174,7 @@ __global__ __launch_bounds__(kBlock) void k_price(LPArgs a) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
-    DevState *st = a.st;
-    if (st->done) return;
-    if (st->max_pivots > 0 && st->pivots >= st->max_pivots) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_MAX_PIVOTS; }
-        return;
-    }
+    if (!price_gate(a.st)) return;
     const int ld2 = a.ld >> 1;
     stage_vec(svec, a.y, ld2);
     const int lane = threadIdx.x & 63;
@@ -40,192 +184,16 @@ __global__ __launch_bounds__(kBlock) void k_price(LPArgs a) {
     unsigned int bi = 0xFFFFFFFFu;
     for (int pos = wave; pos < a.nn; pos += nwaves) {
         const int j = a.nonbasic[pos];
-        const double dot = wave_dot_row(a.At + (size_t)j * a.ld, svec, ld2, lane);
-        const double r = a.cost[j] - dot;
-        if (lane == 0) a.rvec[pos] = r;
-        amin_take(bk, bi, ordkey(r), (unsigned int)pos);
+        price_elem(a.cost, a.rvec, pos, j, wave_dot_row(a.At + (size_t)j * a.ld, svec, ld2, lane), lane, bk, bi);
     }
-    block_argmin(bk, bi, sk, si);
-    if (threadIdx.x == 0) { a.pk_price[blockIdx.x] = bk; a.pi_price[blockIdx.x] = bi; }
-}
-
-// ------------------------------------------------------------------------------------------------
-// K2  FTRAN + ratio test:  d' = Binv a_q ; move_i = x_B[i]/|d_i| for d_i = -d'_i < 0 (simplex.go:306-342),
-//     fused first-index argmin of move (:268).   traffic: m*m*8 bytes read (B^-1 once)
-//     forced_pos >= 0: entering position given (Bland / setup); forced_var >= 0: entering variable id given;
-//     forced_pos = kDualPick: the dual pivot's entering position, from the partials of k_dual_price (dual_kernels.hip).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_ftran(LPArgs a, int nparts_price, int forced_pos, int forced_var) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ unsigned long long sk[kWavesPerBlock];
-    __shared__ unsigned int si[kWavesPerBlock];
-    DevState *st = a.st;
-    if (st->done) return;
-    int q = forced_pos;
-    int var;
-    if (forced_var >= 0) {
-        var = forced_var;
-    } else if (q == kDualPick) {
-        unsigned long long key;
-        q = (int)reduce_partials(a.pk_price, a.pi_price, nparts_price, sk, si, &key);
-        if (key >= ordkey(__builtin_inf())) {   // no alpha_pj < -1e-13 in row p: x_B[p] < 0 cannot be repaired, the LP is infeasible
-            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_DUAL_INFEASIBLE; }
-            return;
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) { st->q = q; st->rq = a.rvec[q]; }
-        var = a.nonbasic[q];
-    } else {
-        if (q < 0) {
-            q = (int)reduce_partials(a.pk_price, a.pi_price, nparts_price, sk, si, nullptr);
-            const double rq = a.rvec[q];
-            if (rq >= -a.tol) {  // simplex.go:248 — optimal
-                if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_OPTIMAL; st->q = q; st->rq = rq; }
-                return;
-            }
-            if (blockIdx.x == 0 && threadIdx.x == 0) { st->q = q; st->rq = rq; }
-        } else if (blockIdx.x == 0 && threadIdx.x == 0) {
-            st->q = q; st->rq = a.rvec[q];
-        }
-        var = a.nonbasic[q];
-    }
-    const int ld2 = a.ld >> 1;
-    stage_vec(svec, a.At + (size_t)var * a.ld, ld2);
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    unsigned long long bk = ~0ull;
-    unsigned int bi = 0xFFFFFFFFu;
-    for (int i = wave; i < a.m; i += nwaves) {
-        const double dp = wave_dot_row(a.binv_cur + (size_t)i * a.ld, svec, ld2, lane);
-        double d = -dp;                       // simplex.go:319
-        if (fabs(d) < 1e-13) d = 0;           // dRoundTol, :321-325
-        const double mv = (d >= 0) ? __builtin_inf() : a.xb[i] / fabs(d);  // :334-340
-        if (lane == 0) { a.dvec[i] = dp; a.move[i] = mv; }
-        amin_take(bk, bi, ordkey(mv), (unsigned int)i);
-    }
-    block_argmin(bk, bi, sk, si);
-    if (threadIdx.x == 0) { a.pk_ratio[blockIdx.x] = bk; a.pi_ratio[blockIdx.x] = bi; }
-}
-
-// ------------------------------------------------------------------------------------------------
-// K3  basis change: rank-1 update of B^-1 (ping-pong), x_B, y, index swap (simplex.go:280-292 without
-//     the three fresh LU factorizations).   traffic: m*m*8 read + m*m*8 written
-//     forced_p >= 0: leaving position given; kDualPick: the one k_dual_leave chose (DevState::p).  no_swap: setup pivot (indices
-//     managed by the host).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_update(LPArgs a, int nparts_ratio, int forced_p, int no_swap, int bland) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ unsigned long long sk[kWavesPerBlock];
-    __shared__ unsigned int si[kWavesPerBlock];
-    DevState *st = a.st;
-    if (st->done) return;
-    int p = forced_p == kDualPick ? st->p : forced_p;
-    if (p < 0) {
-        p = (int)reduce_partials(a.pk_ratio, a.pi_ratio, nparts_ratio, sk, si, nullptr);
-        const double mv = a.move[p];
-        if (mv == __builtin_inf()) {  // no d_i < 0: unbounded (simplex.go:328-330)
-            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_UNBOUNDED; st->p = p; st->mv = mv; }
-            return;
-        }
-        if (mv <= 0) {  // degenerate step -> Bland rule (simplex.go:269)
-            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_NEED_BLAND; st->p = p; st->mv = mv; }
-            return;
-        }
-    }
-    const double dpv = a.dvec[p];
-    const int ld2 = a.ld >> 1;
-    stage_vec(svec, a.binv_cur + (size_t)p * a.ld, ld2);  // old row p
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    for (int i = wave; i < a.m; i += nwaves) {
-        const double2 *src = reinterpret_cast<const double2 *>(a.binv_cur + (size_t)i * a.ld);
-        double2 *dst = reinterpret_cast<double2 *>(a.binv_next + (size_t)i * a.ld);
-        if (i == p) {
-            for (int c = lane; c < ld2; c += 64) {
-                double2 v = svec[c];
-                v.x = v.x / dpv; v.y = v.y / dpv;
-                dst[c] = v;
-            }
-        } else {
-            const double f = a.dvec[i] / dpv;
-            for (int c = lane; c < ld2; c += 64) {
-                double2 v = src[c];
-                const double2 rp = svec[c];
-                v.x = v.x - f * rp.x; v.y = v.y - f * rp.y;
-                dst[c] = v;
-            }
-        }
-    }
-    if (blockIdx.x == 0) {
-        // O(m) vector updates by workgroup 0 (nobody else touches xb / y in this kernel)
-        const double theta = a.xb[p] / dpv;
-        const double rq = no_swap ? 0.0 : st->rq;
-        const double alpha = rq / dpv;
-        __syncthreads();
-        for (int i = threadIdx.x; i < a.m; i += kBlock) a.xb[i] = (i == p) ? theta : a.xb[i] - theta * a.dvec[i];
-        const double *rowp = reinterpret_cast<const double *>(svec);
-        for (int j = threadIdx.x; j < a.ld; j += kBlock) a.y[j] = a.y[j] + alpha * rowp[j];
-        if (threadIdx.x == 0) {
-            const int q = st->q;
-            st->p = p; st->dp = dpv; st->mv = a.move[p];
-            if (!no_swap) {
-                const int ent = a.nonbasic[q], lea = a.basic[p];
-                a.basic[p] = ent; a.nonbasic[q] = lea;  // simplex.go:280
-                if (a.trace && st->trace_len < a.trace_cap) {
-                    DevPivot &t = a.trace[st->trace_len];
-                    t.phase = a.phase; t.bland = bland; t.min_idx = q; t.replace = p; t.entering = ent; t.leaving = lea;
-                }
-                st->trace_len += 1;
-                st->pivots += 1;
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// K1-K3 and the refresh in the chunked form (kernels_common.h: stage_chunk / wave_dot_chunk): for vectors longer than
-// the LDS window (ld > 8192), or wherever the context knob row_chunk forces it.  Same operations per element, same
-// first-index argmins as the one-pass kernels above, bit-identical results.  A wave takes its rows kCkRows at a time
-// (rows wave, wave + nwaves, ... as above), and the workgroup streams the vector through LDS once per such group, so
-// the loops run to a workgroup-uniform bound: every thread reaches every barrier.
-// ------------------------------------------------------------------------------------------------
-constexpr int kCkRows = 4;
-
-// one group of up to kCkRows rows of a wave: dot[r] = M[row(r), :] . vec (valid where row(r) < rows)
-__device__ __forceinline__ void dot_group(const double *__restrict__ M, int ld, const int32_t *__restrict__ rowmap, int rows,
-                                          int k0, int wave, int nwaves, const double *__restrict__ vec, double2 *svec, int ck2,
-                                          int lane, double (&dot)[kCkRows]) {
-    const int ld2 = ld >> 1;
-    const double *rowp[kCkRows];
-    DotAcc acc[kCkRows];
-#pragma unroll
-    for (int r = 0; r < kCkRows; r++) {
-        const int pos = wave + (k0 + r) * nwaves;
-        rowp[r] = pos < rows ? M + (size_t)(rowmap ? rowmap[pos] : pos) * ld : nullptr;
-        acc[r].a0 = acc[r].a1 = acc[r].a2 = acc[r].a3 = 0;
-    }
-    for (int c0 = 0; c0 < ld2; c0 += ck2) {
-        const int c1 = min(c0 + ck2, ld2);
-        stage_chunk(svec, vec, c0, c1);
-#pragma unroll
-        for (int r = 0; r < kCkRows; r++)
-            if (rowp[r]) wave_dot_chunk(rowp[r], svec, c0, c1, ld2, lane, acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < kCkRows; r++) dot[r] = rowp[r] ? wave_dot_finish(acc[r]) : 0.0;
+    publish_partials(bk, bi, sk, si, a.pk_price, a.pi_price);
 }
 
 __global__ __launch_bounds__(kBlock) void k_price_ck(LPArgs a, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
-    DevState *st = a.st;
-    if (st->done) return;
-    if (st->max_pivots > 0 && st->pivots >= st->max_pivots) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_MAX_PIVOTS; }
-        return;
-    }
+    if (!price_gate(a.st)) return;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
@@ -233,54 +201,45 @@ __global__ __launch_bounds__(kBlock) void k_price_ck(LPArgs a, int ck2) {
     unsigned long long bk = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
     for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows];
-        dot_group(a.At, a.ld, a.nonbasic, a.nn, k0, wave, nwaves, a.y, svec, ck2, lane, dot);
+        double dot[kCkRows][1];
+        dot_group<1>(a.At, a.ld, a.nonbasic, a.nn, k0, wave, nwaves, {a.y}, svec, ck2, lane, dot);
 #pragma unroll
         for (int r = 0; r < kCkRows; r++) {
             const int pos = wave + (k0 + r) * nwaves;
-            if (pos >= a.nn) continue;
-            const double rc = a.cost[a.nonbasic[pos]] - dot[r];
-            if (lane == 0) a.rvec[pos] = rc;
-            amin_take(bk, bi, ordkey(rc), (unsigned int)pos);
+            if (pos < a.nn) price_elem(a.cost, a.rvec, pos, a.nonbasic[pos], dot[r][0], lane, bk, bi);
         }
     }
-    block_argmin(bk, bi, sk, si);
-    if (threadIdx.x == 0) { a.pk_price[blockIdx.x] = bk; a.pi_price[blockIdx.x] = bi; }
+    publish_partials(bk, bi, sk, si, a.pk_price, a.pi_price);
+}
+
+// ------------------------------------------------------------------------------------------------
+// K2  FTRAN + ratio test:  d' = Binv a_q ; move_i = x_B[i]/|d_i| for d_i = -d'_i < 0 (simplex.go:306-342),
+//     fused first-index argmin of move (:268).   traffic: m*m*8 bytes read (B^-1 once)
+//     entering variable: pick_entering
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_ftran(LPArgs a, int nparts_price, int forced_pos, int forced_var) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    int var;
+    if (!pick_entering(a.st, a.pk_price, a.pi_price, nparts_price, a.rvec, a.nonbasic, a.tol, forced_pos, forced_var, sk, si, var)) return;
+    const int ld2 = a.ld >> 1;
+    stage_vec(svec, a.At + (size_t)var * a.ld, ld2);
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    unsigned long long bk = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int i = wave; i < a.m; i += nwaves) ratio_elem(a.xb, a.dvec, a.move, i, wave_dot_row(a.binv_cur + (size_t)i * a.ld, svec, ld2, lane), lane, bk, bi);
+    publish_partials(bk, bi, sk, si, a.pk_ratio, a.pi_ratio);
 }
 
 __global__ __launch_bounds__(kBlock) void k_ftran_ck(LPArgs a, int nparts_price, int forced_pos, int forced_var, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
-    DevState *st = a.st;
-    if (st->done) return;
-    int q = forced_pos;
     int var;
-    if (forced_var >= 0) {
-        var = forced_var;
-    } else if (q == kDualPick) {
-        unsigned long long key;
-        q = (int)reduce_partials(a.pk_price, a.pi_price, nparts_price, sk, si, &key);
-        if (key >= ordkey(__builtin_inf())) {   // no alpha_pj < -1e-13 in row p: x_B[p] < 0 cannot be repaired, the LP is infeasible
-            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_DUAL_INFEASIBLE; }
-            return;
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) { st->q = q; st->rq = a.rvec[q]; }
-        var = a.nonbasic[q];
-    } else {
-        if (q < 0) {
-            q = (int)reduce_partials(a.pk_price, a.pi_price, nparts_price, sk, si, nullptr);
-            const double rq = a.rvec[q];
-            if (rq >= -a.tol) {
-                if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_OPTIMAL; st->q = q; st->rq = rq; }
-                return;
-            }
-            if (blockIdx.x == 0 && threadIdx.x == 0) { st->q = q; st->rq = rq; }
-        } else if (blockIdx.x == 0 && threadIdx.x == 0) {
-            st->q = q; st->rq = a.rvec[q];
-        }
-        var = a.nonbasic[q];
-    }
+    if (!pick_entering(a.st, a.pk_price, a.pi_price, nparts_price, a.rvec, a.nonbasic, a.tol, forced_pos, forced_var, sk, si, var)) return;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
@@ -288,43 +247,47 @@ __global__ __launch_bounds__(kBlock) void k_ftran_ck(LPArgs a, int nparts_price,
     unsigned long long bk = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
     for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows];
-        dot_group(a.binv_cur, a.ld, nullptr, a.m, k0, wave, nwaves, a.At + (size_t)var * a.ld, svec, ck2, lane, dot);
+        double dot[kCkRows][1];
+        dot_group<1>(a.binv_cur, a.ld, nullptr, a.m, k0, wave, nwaves, {a.At + (size_t)var * a.ld}, svec, ck2, lane, dot);
 #pragma unroll
         for (int r = 0; r < kCkRows; r++) {
             const int i = wave + (k0 + r) * nwaves;
-            if (i >= a.m) continue;
-            const double dp = dot[r];
-            double d = -dp;
-            if (fabs(d) < 1e-13) d = 0;
-            const double mv = (d >= 0) ? __builtin_inf() : a.xb[i] / fabs(d);
-            if (lane == 0) { a.dvec[i] = dp; a.move[i] = mv; }
-            amin_take(bk, bi, ordkey(mv), (unsigned int)i);
+            if (i < a.m) ratio_elem(a.xb, a.dvec, a.move, i, dot[r][0], lane, bk, bi);
         }
     }
-    block_argmin(bk, bi, sk, si);
-    if (threadIdx.x == 0) { a.pk_ratio[blockIdx.x] = bk; a.pi_ratio[blockIdx.x] = bi; }
+    publish_partials(bk, bi, sk, si, a.pk_ratio, a.pi_ratio);
 }
 
+// ------------------------------------------------------------------------------------------------
+// K3  basis change: rank-1 update of B^-1 (ping-pong), x_B, y, index swap (simplex.go:280-292 without
+//     the three fresh LU factorizations).   traffic: m*m*8 read + m*m*8 written
+//     leaving row: pick_leaving.  no_swap: setup pivot (indices managed by the host).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_update(LPArgs a, int nparts_ratio, int forced_p, int no_swap, int bland) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    int p;
+    if (!pick_leaving(a.st, a.pk_ratio, a.pi_ratio, nparts_ratio, a.move, forced_p, sk, si, p)) return;
+    const double dpv = a.dvec[p];
+    const int ld2 = a.ld >> 1;
+    stage_vec(svec, a.binv_cur + (size_t)p * a.ld, ld2);  // old row p
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    for (int i = wave; i < a.m; i += nwaves) update_row(a.binv_cur, a.binv_next, a.ld, a.dvec, i, p, dpv, svec, 0, ld2, lane);
+    if (blockIdx.x == 0)
+        commit_pivot(a.st, a.xb, a.y, a.dvec, a.move, a.basic, a.nonbasic, a.trace, a.trace_cap, a.phase, a.m, a.ld, p, dpv,
+                     reinterpret_cast<const double *>(svec), no_swap, bland);
+}
+
+// elementwise: its chunks are only bounds
 __global__ __launch_bounds__(kBlock) void k_update_ck(LPArgs a, int nparts_ratio, int forced_p, int no_swap, int bland, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
-    DevState *st = a.st;
-    if (st->done) return;
-    int p = forced_p == kDualPick ? st->p : forced_p;
-    if (p < 0) {
-        p = (int)reduce_partials(a.pk_ratio, a.pi_ratio, nparts_ratio, sk, si, nullptr);
-        const double mv = a.move[p];
-        if (mv == __builtin_inf()) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_UNBOUNDED; st->p = p; st->mv = mv; }
-            return;
-        }
-        if (mv <= 0) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_NEED_BLAND; st->p = p; st->mv = mv; }
-            return;
-        }
-    }
+    int p;
+    if (!pick_leaving(a.st, a.pk_ratio, a.pi_ratio, nparts_ratio, a.move, forced_p, sk, si, p)) return;
     const double dpv = a.dvec[p];
     const int ld2 = a.ld >> 1;
     const double *rowp_g = a.binv_cur + (size_t)p * a.ld;   // old row p (binv_cur is only read here)
@@ -335,54 +298,17 @@ __global__ __launch_bounds__(kBlock) void k_update_ck(LPArgs a, int nparts_ratio
     for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
         for (int c0 = 0; c0 < ld2; c0 += ck2) {
             const int c1 = min(c0 + ck2, ld2);
-            stage_chunk(svec, rowp_g, c0, c1);
+            stage_chunk<1>(svec, ck2, {rowp_g}, c0, c1);
 #pragma unroll
             for (int r = 0; r < kCkRows; r++) {
                 const int i = wave + (k0 + r) * nwaves;
-                if (i >= a.m) continue;
-                const double2 *src = reinterpret_cast<const double2 *>(a.binv_cur + (size_t)i * a.ld);
-                double2 *dst = reinterpret_cast<double2 *>(a.binv_next + (size_t)i * a.ld);
-                if (i == p) {
-                    for (int c = c0 + lane; c < c1; c += 64) {
-                        double2 v = svec[c - c0];
-                        v.x = v.x / dpv; v.y = v.y / dpv;
-                        dst[c] = v;
-                    }
-                } else {
-                    const double f = a.dvec[i] / dpv;
-                    for (int c = c0 + lane; c < c1; c += 64) {
-                        double2 v = src[c];
-                        const double2 rp = svec[c - c0];
-                        v.x = v.x - f * rp.x; v.y = v.y - f * rp.y;
-                        dst[c] = v;
-                    }
-                }
+                if (i < a.m) update_row(a.binv_cur, a.binv_next, a.ld, a.dvec, i, p, dpv, svec, c0, c1, lane);
             }
         }
     }
-    if (blockIdx.x == 0) {
-        // O(m) vector updates by workgroup 0, as in k_update (row p read from B^-1 itself instead of LDS: same values)
-        const double theta = a.xb[p] / dpv;
-        const double rq = no_swap ? 0.0 : st->rq;
-        const double alpha = rq / dpv;
-        __syncthreads();
-        for (int i = threadIdx.x; i < a.m; i += kBlock) a.xb[i] = (i == p) ? theta : a.xb[i] - theta * a.dvec[i];
-        for (int j = threadIdx.x; j < a.ld; j += kBlock) a.y[j] = a.y[j] + alpha * rowp_g[j];
-        if (threadIdx.x == 0) {
-            const int q = st->q;
-            st->p = p; st->dp = dpv; st->mv = a.move[p];
-            if (!no_swap) {
-                const int ent = a.nonbasic[q], lea = a.basic[p];
-                a.basic[p] = ent; a.nonbasic[q] = lea;
-                if (a.trace && st->trace_len < a.trace_cap) {
-                    DevPivot &t = a.trace[st->trace_len];
-                    t.phase = a.phase; t.bland = bland; t.min_idx = q; t.replace = p; t.entering = ent; t.leaving = lea;
-                }
-                st->trace_len += 1;
-                st->pivots += 1;
-            }
-        }
-    }
+    if (blockIdx.x == 0)
+        commit_pivot(a.st, a.xb, a.y, a.dvec, a.move, a.basic, a.nonbasic, a.trace, a.trace_cap, a.phase, a.m, a.ld, p, dpv, rowp_g,
+                     no_swap, bland);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -488,12 +414,12 @@ __global__ __launch_bounds__(kBlock) void k_matvec_rows_ck(const double *__restr
     const int nwaves = gridDim.x * kWavesPerBlock;
     const int kmax = (m + nwaves - 1) / nwaves;
     for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows];
-        dot_group(M, ld, nullptr, m, k0, wave, nwaves, vec, svec, ck2, lane, dot);
+        double dot[kCkRows][1];
+        dot_group<1>(M, ld, nullptr, m, k0, wave, nwaves, {vec}, svec, ck2, lane, dot);
 #pragma unroll
         for (int r = 0; r < kCkRows; r++) {
             const int i = wave + (k0 + r) * nwaves;
-            if (i < m && lane == 0) out[i] = dot[r];
+            if (i < m && lane == 0) out[i] = dot[r][0];
         }
     }
 }
@@ -637,13 +563,6 @@ __global__ __launch_bounds__(kBlock) void k_lu_step(LUArgs a, int k, int nparts)
 // ------------------------------------------------------------------------------------------------
 // host-callable launch wrappers (the engine is plain C++; only this file is device code)
 // ------------------------------------------------------------------------------------------------
-
-static inline int grid_for_rows(int rows) {
-    int g = (rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (g > kMaxPartials) g = kMaxPartials;
-    if (g < 1) g = 1;
-    return g;
-}
 
 int launch_price(const LPArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const int g = grid_for_rows(a.nn);
