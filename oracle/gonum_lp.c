@@ -424,3 +424,32 @@ int oracle_lp_simplex(const double *c, const double *A, int64_t lda, const doubl
     if (m <= 0 || n <= 0 || lda < n) { *opt_f = NAN; return ORACLE_ERR_BAD_SHAPE; }
     return simplex(ctx, 0, initial_basic, c, A, lda, b, m, n, tol, opt_f, opt_x, has_x, basis_out);
 }
+
+/* The end of simplex.go's loop on a given basis: ab = A[:, basis] (extractColumns, :474-488), x_B = ab \ b through one
+ * mat.LU Factorize / SolveVec (:288-292; the receiver stays zero when Det() == 0, :301-303 of mat/lu.go), opt = floats.Dot(cb, x_B)
+ * (:296), x scattered by basis position (:297-300).  One factorization, no pricing: what the loop returns once it stops on `basis`. */
+int oracle_basis_solve(const double *c, const double *A, int64_t lda, const double *b, int64_t m, int64_t n, const int64_t *basis,
+                       double *opt_f, double *opt_x, double *cond_out) {
+    *opt_f = NAN;
+    if (cond_out) *cond_out = NAN;
+    if (m <= 0 || n < m || lda < n) return 3;
+    for (int64_t i = 0; i < m; i++)
+        if (basis[i] < 0 || basis[i] >= n) return 3;
+    double *ab = (double *)malloc(sizeof(double) * (size_t)(m * m));
+    double *xb = (double *)calloc((size_t)m, sizeof(double));
+    double *cb = (double *)malloc(sizeof(double) * (size_t)m);
+    extract_columns(ab, m, A, lda, m, basis);
+    for (int64_t i = 0; i < m; i++) cb[i] = c[basis[i]];
+    g_lu f; g_lu_init(&f);
+    g_lu_factorize(&f, m, ab, m, G_NORM_MAXROWSUM);
+    memcpy(xb, b, sizeof(double) * (size_t)m);
+    int rc = g_lu_solve_vec(&f, xb);
+    if (rc == 2) memset(xb, 0, sizeof(double) * (size_t)m);
+    if (cond_out) *cond_out = f.cond;
+    g_lu_free(&f);
+    *opt_f = g_dot_unitary(m, cb, xb);
+    for (int64_t j = 0; j < n; j++) opt_x[j] = 0;
+    for (int64_t i = 0; i < m; i++) opt_x[basis[i]] = xb[i];
+    free(ab); free(xb); free(cb);
+    return rc;
+}

@@ -78,4 +78,13 @@ int oracle_lp_simplex(const double *c, const double *A, int64_t lda, const doubl
 int64_t oracle_find_linearly_independent(const double *A, int64_t lda, int64_t m, int64_t n, int64_t *idxs,
                                          oracle_ctx *ctx);
 
+/*
+ * The reference's end state on a given basis (simplex.go:288-300): x_B = ab \ b through one mat.LU, opt = cb . x_B, x by basis
+ * position.  opt_x: caller-owned, length n.  cond_out: NULL or the LU's condition estimate (mat/lu.go:28-50).
+ * Returns 0 = solved; 1 = solved, cond > 1e16 (mat.Condition); 2 = Det() == 0, x_B left at zero (mat.Condition(+Inf));
+ * 3 = bad shape or a basis index out of range (nothing written but opt_f = NaN).
+ */
+int oracle_basis_solve(const double *c, const double *A, int64_t lda, const double *b, int64_t m, int64_t n, const int64_t *basis,
+                       double *opt_f, double *opt_x, double *cond_out);
+
 #endif

@@ -95,6 +95,8 @@ def lib():
         _lib.g_solve_vec_trans.restype = C.c_int
         _lib.g_solve_vec_trans.argtypes = [C.c_int64, dp, C.c_int64, dp]
         _lib.g_dgeqrf.argtypes = [C.c_int64, C.c_int64, dp, C.c_int64, dp]
+        _lib.oracle_basis_solve.restype = C.c_int
+        _lib.oracle_basis_solve.argtypes = [dp, dp, C.c_int64, dp, C.c_int64, C.c_int64, ip, dp, dp, dp]
     return _lib
 
 
@@ -174,6 +176,34 @@ def simplex(c, A, b, tol: float = 0.0, initial_basic=None, *, fast_initial_basis
         lu_factorizations=ctx.lu_factorizations, cond_evaluations=ctx.cond_evaluations,
         phase1_used=bool(ctx.phase1_used), truncated=bool(ctx.truncated), wrapped_code=ctx.wrapped_code,
         seconds_loop=ctx.seconds_loop, art_exchanges=ctx.art_exchanges)
+
+
+@dataclass
+class BasisSolve:
+    status: int              # OK, or ERR_CONDITION where LU.Solve reports mat.Condition (cond > 1e16, or Det() == 0)
+    singular: bool           # Det() == 0: x_B stayed zero (mat/lu.go:301-303)
+    cond: float              # the LU's condition estimate (mat/lu.go:28-50)
+    z: float
+    x: np.ndarray
+
+
+def basis_solve(c, A, b, basis) -> BasisSolve:
+    """What lp.Simplex returns once its loop stops on `basis` (positional): x_B = ab \\ b through one mat.LU (simplex.go:288-292),
+    z = floats.Dot(cb, x_B) (:296), x scattered by basis position (:297-300).  One factorization and no pricing, so it says nothing
+    about whether `basis` is optimal: ask simplex(..., initial_basic=basis) for that."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    m, n = A.shape
+    bas = np.ascontiguousarray(basis, dtype=np.int64)
+    if c.shape != (n,) or b.shape != (m,) or bas.shape != (m,) or m > n:
+        raise ValueError("basis_solve: shapes c %s, A %s, b %s, basis %s" % (c.shape, A.shape, b.shape, bas.shape))
+    x = np.zeros(n, dtype=np.float64)
+    z, cond = C.c_double(math.nan), C.c_double(math.nan)
+    rc = lib().oracle_basis_solve(_dp(c), _dp(A), n, _dp(b), m, n, _ip(bas), C.byref(z), _dp(x), C.byref(cond))
+    if rc == 3:
+        raise ValueError("basis_solve: basis index out of range")
+    return BasisSolve(OK if rc == 0 else ERR_CONDITION, rc == 2, cond.value, z.value, x)
 
 
 def find_linearly_independent(A, fast: bool = False) -> List[int]:

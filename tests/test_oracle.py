@@ -1,6 +1,7 @@
 """CPU tests of the oracle's building blocks (no GPU): fast-path equivalence, LU blocking, generator."""
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import pytest
@@ -149,3 +150,78 @@ def test_wide_degenerate_family_keeps_its_degeneracy():
     assert bland >= 40, bland
     cyc = O.simplex(*synth.wide_degenerate_lp(32, 11, 2.5), 0.0, None, fast_initial_basis=True, stop_after_pivots=400)
     assert cyc.truncated and cyc.pivots_phase2 == 400
+
+
+# ---- basis_solve: the reference's end state on a given basis (the yardstick of tests/test_gpu_revised_reference.py) ----------------
+
+def _fixture(name):
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name), allow_pickle=False)
+
+
+@pytest.fixture
+def oracle_threads():
+    O.set_threads(min(16, os.cpu_count() or 1))
+    yield
+    O.set_threads(1)
+
+
+@pytest.mark.parametrize("name,end", [("C2", "lp_C2.npz"), ("M", "lp_M.npz"), ("C4", "lp_C4_end.npz")])
+def test_basis_solve_reproduces_the_fixture_end_states(oracle_threads, name, end):
+    """one factorization of the fixture's final positional basis gives the x and z bits the oracle's own loop ended on (C2, M: the full
+    solves; C4: the oracle restarted from the engine's final basis)"""
+    fx = _fixture(end)
+    c, A, b = synth.dense_lp_standard_form(*synth.CONFIGS[name])
+    s = O.basis_solve(c, A, b, fx["basis"])
+    assert s.status == O.OK and not s.singular and 1 <= s.cond < 1e16
+    assert s.x.tobytes() == np.ascontiguousarray(fx["x"], dtype=np.float64).tobytes()
+    assert np.float64(s.z).tobytes() == np.float64(fx["z"]).tobytes()
+
+
+def _small_lps():
+    from tests.test_gpu_large_rows import _gen
+    return {"dense64": synth.dense_lp_standard_form(64, 11), "dense200": synth.dense_lp_standard_form(200, 12),
+            "wide96": synth.wide_degenerate_lp(96, 0), "int256": _gen(256, 512, 0), "phase1-256": _gen(256, 512, 1, "phase1"),
+            "wide512": synth.wide_degenerate_lp(512, 1)}
+
+
+@pytest.mark.parametrize("name", ["dense64", "dense200", "wide96", "int256", "phase1-256", "wide512"])
+def test_basis_solve_equals_the_restarted_oracle(oracle_threads, name):
+    """64 to 512 rows (dense, wide degenerate integer, Phase I): the oracle restarted from the LP's own optimal basis takes no pivot, and
+    basis_solve of that basis gives its x and z bits, which are also the bits of the solve that found the basis"""
+    c, A, b = _small_lps()[name]
+    o = O.simplex(c, A, b, 0.0, None, fast_initial_basis=True)
+    assert o.status == O.OK
+    r = O.simplex(c, A, b, 0.0, o.basis)
+    assert r.status == O.OK and r.pivots_phase1 == r.pivots_phase2 == 0
+    s = O.basis_solve(c, A, b, o.basis)
+    assert s.status == O.OK and not s.singular
+    assert s.x.tobytes() == r.x.tobytes() == o.x.tobytes()
+    assert np.float64(s.z).tobytes() == np.float64(r.z).tobytes() == np.float64(o.z).tobytes()
+
+
+def test_basis_solve_of_a_basis_that_is_not_optimal(oracle_threads):
+    """the loop's point after k pivots (stop_after_pivots) is the solve of its basis at that moment: basis_solve does not price"""
+    c, A, b = synth.dense_lp_standard_form(200, 12)
+    for k in (1, 30):
+        t = O.simplex(c, A, b, 0.0, None, fast_initial_basis=True, stop_after_pivots=k)
+        assert t.truncated and t.pivots_phase2 == k
+        s = O.basis_solve(c, A, b, t.basis)
+        assert s.status == O.OK
+        assert s.x.tobytes() == t.x.tobytes() and np.float64(s.z).tobytes() == np.float64(t.z).tobytes()
+
+
+def test_basis_solve_singular_and_bad_bases():
+    """Det() == 0 (the slack column of row 0 twice, so row 1 has no pivot): mat.Condition, x_B left at zero; an index out of range or a
+    basis of the wrong length is refused"""
+    c, A, b = synth.dense_lp_standard_form(16, 2)
+    basis = np.arange(16, 32)
+    basis[1] = basis[0]
+    s = O.basis_solve(c, A, b, basis)
+    assert s.status == O.ERR_CONDITION and s.singular
+    assert not s.x.any() and s.z == 0.0
+    ok = O.basis_solve(c, A, b, np.arange(16, 32))
+    assert ok.status == O.OK and ok.cond == 1.0 and np.array_equal(ok.x[16:], b) and ok.z == 0.0
+    with pytest.raises(ValueError):
+        O.basis_solve(c, A, b, np.arange(17, 33))
+    with pytest.raises(ValueError):
+        O.basis_solve(c, A, b, np.arange(16, 31))
