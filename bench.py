@@ -2,14 +2,21 @@
 """bench.py — headline benchmark of the LP-relaxation hot path (BASELINE.json `metric`:
 "simplex pivots/sec on 2048x4096 fp64 dense LP; relaxations/sec at 1/2/4/8 GPUs").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload M|C2|C4|C3] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload M|C2|C4|C3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     (python bench.py --gpus N without a torchrun environment starts that launcher itself.)
 
 N = 1: one "step" = one complete pass of the hot path over one synthetic input: a full dense-simplex solve of the metric
 workload (2048x4096 fp64 dense LP, SURVEY.md §8d generator, seed 2) from HBM-resident inputs through the C-ABI of
-include/gomilp_lp.h; value = simplex pivots per second.  The same line carries the 1-GPU figure of the frontier metric
-(`frontier.relaxations_per_s`) the N > 1 lines scale from.
+include/gomilp_lp.h; value = simplex pivots per second.  With --full the same line carries the 1-GPU figure of the frontier
+metric (`frontier.relaxations_per_s`) the N > 1 lines scale from.
+
+A plain run does what its headline needs: set-up, the W warm-up steps, the K timed steps, --dump-outputs, the line.  At N = 1
+the line also holds `roofline`, `mfma` and `breakdown`, which come from the timed steps' own statistics.  Everything that takes
+runs of its own waits for --full and runs after the headline: at N = 1 the CPU baselines, the batched, C2, C4 and
+general-basis solves, the frontier waves, the C3 tree cold and warm and the degenerate trees; at N > 1 the sampled waves behind
+`roofline`, the heaviest child alone, one wave from the Python lists and the 2048- and 8192-wide lines.  The options that
+shape those legs (--no-cpu-baseline, --concurrent, --c4, --general, --frontier-*, --milp-*) act only with --full.
 
 N > 1: one "step" = one 256-wide branch-and-bound wave of 512x1024 relaxations (BASELINE config 5) sharded over the N
 ranks (one process per GPU, device-batched pivot loops per rank), closed by ONE RCCL all-reduce(min) of the incumbent
@@ -18,7 +25,7 @@ through the C-ABI (gomilp_incumbent_allreduce); value = relaxations per second o
 Rank 0 prints ONE JSON line.  `roofline` prices the kernel with the largest share of GPU time in the timed region — the
 persistent loop kernel k_bt_loop (pivot workgroups + update workgroups in one launch) — by its algorithmic bytes per full launch
 (64 blocks of 8 pivots: the rank-8 update's pass over the tableau + the pivot workgroups' columns, rows and terms) over the
-HIP-event time of that launch against the HBM peak; `limited_by` names what sets its pace (the pivot chain, not bandwidth); `roofline.loop` does the same with the wall time of the whole pivot loop (launch boundaries and host waits included).  `cpu_baseline` times the CPU oracle (the reference algorithm: 3 fresh LU per pivot) on a
+HIP-event time of that launch against the HBM peak; `limited_by` names what sets its pace (the pivot chain, not bandwidth); `roofline.loop` does the same with the wall time of the whole pivot loop (launch boundaries and host waits included).  `cpu_baseline` (--full) times the CPU oracle (the reference algorithm: 3 fresh LU per pivot) on a
 bounded sample of the same workload on the host cores.
 
 --dump-outputs DIR: after the timed steps, what the last timed step returned to its caller goes to DIR/<name>.npy (float64):
@@ -70,6 +77,8 @@ def parse_args():
     ap.add_argument("--c4", type=int, default=1, help="extra figure: one timed solve of the 4096x8192 LP (BASELINE config 4) (0 = skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned to its caller "
                     "as DIR/<name>.npy (float64), so that two builds can be compared output for output on the same seeded inputs")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run every leg that takes runs of its own: CPU baselines, "
+                    "other sizes and configurations, frontier lines, sampled kernel times (off: the headline alone)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -328,17 +337,20 @@ def main() -> int:
         if keep is not None:
             keep["wave"] = wave
         # kernel durations: two more waves with a HIP event pair around every batched launch (outside the timed region: the
-        # event records cost ~10 % of a wave)
+        # event records cost ~10 % of a wave); these and the other runs behind the timed waves only with --full
+        sampled = 2 if args.full and not light else 0
         pool.set("sample_batch", 1)
-        for _ in range(0 if light else 2):
+        for _ in range(sampled):
             fr.solve_wave(solve_shard, children, mask5, rank, world, wave_dist, dev, comm=comm, shard=shard)
             st = holder["stats"]
             acc["inner"] += st["seconds_inner_kernels"]; acc["update"] += st["seconds_update_kernels"]; acc["blocks_sampled"] += st["blocks_sampled"]
         pool.set("sample_batch", 0)
         # one wave from the Python lists (shard and flat description rebuilt inside the call), outside the timed region
-        tu = time.perf_counter()
-        fr.solve_wave(solve_shard, children, mask5, rank, world, wave_dist, dev, comm=comm)
-        unpacked_s = time.perf_counter() - tu
+        unpacked_s = None
+        if args.full:
+            tu = time.perf_counter()
+            fr.solve_wave(solve_shard, children, mask5, rank, world, wave_dist, dev, comm=comm)
+            unpacked_s = time.perf_counter() - tu
         tot = allsum([acc["pivots"], acc["phase1"], acc["bland"], acc["fallbacks"], acc["batched"],
                       float(sum(1 for s in wave["status"] if s == lp.OK))])
         # per rank: mean wave time and its split (one slot per rank, summed over the ranks: every rank fills its own)
@@ -349,7 +361,7 @@ def main() -> int:
                      "incumbent_scan_ms": 1e3 * slots[4 * rk + 2], "exchange_ms": 1e3 * slots[4 * rk + 3]} for rk in range(world)]
         # scaling bound: the heaviest child alone through the same batched path (a wave can never be faster than that)
         solo = None
-        if rank == 0 and not light:
+        if rank == 0 and not light and args.full:
             res_all = pool.solve(children)
             t_best, heavy = 0.0, 0
             for i in [i for i, st_ in enumerate(res_all.status) if st_ == lp.OK]:   # the feasible children are the long ones
@@ -380,11 +392,12 @@ def main() -> int:
                         "(k_b_loop: per relaxation a pivot workgroup + 7 update workgroups, update of block t beside block t + 1) once <= 24 relaxations are active (12 per schedule while two run); "
                         "a wide schedule of slack-start relaxations runs its set-up pivot and first block on VIRTUAL tableaus (entries computed from the root's A + branch rows + the set-up term) and writes out only what is alive behind that block; "
                         "%d block steps (of 8 pivots) and %.1f host looks per wave on rank 0" % (acc["blocks"] // max(steps, 1), holder["stats"]["supersteps"]),
-            "kernels_rank0": {"inner": "k_b_loop<512,2,4,7> (narrow) / k_bt_inner2_virt_batch<512,2,2,8,0> (set-up pivot + first block of a wide schedule, on computed tableau entries) / k_bt_inner2_batch<512,2,2,8,0> (wide)", "inner_us_per_launch": inner_us, "update_us_per_launch": upd_us,
-                              "time_share_inner": acc["inner"] / max(acc["inner"] + acc["update"], 1e-30),
-                              "algorithmic_bytes_per_pivot": alg_bytes,
-                              "note": "HIP events of the sampled waves: a k_b_loop launch (up to 32 blocks of 8 pivots for every active relaxation, updates inside) counts as ONE inner launch"},
         }
+        if sampled:
+            out["kernels_rank0"] = {"inner": "k_b_loop<512,2,4,7> (narrow) / k_bt_inner2_virt_batch<512,2,2,8,0> (set-up pivot + first block of a wide schedule, on computed tableau entries) / k_bt_inner2_batch<512,2,2,8,0> (wide)", "inner_us_per_launch": inner_us, "update_us_per_launch": upd_us,
+                                    "time_share_inner": acc["inner"] / max(acc["inner"] + acc["update"], 1e-30),
+                                    "algorithmic_bytes_per_pivot": alg_bytes,
+                                    "note": "HIP events of the sampled waves: a k_b_loop launch (up to 32 blocks of 8 pivots for every active relaxation, updates inside) counts as ONE inner launch"}
         if solo is not None:
             out["scaling_bound"] = {"heaviest_child": solo, "note": "a wave cannot finish before its heaviest child: relaxations/s at any GPU count "
                                     "<= %d / %.2f ms; more GPUs only remove what the other children add to that" % (len(children), 1e3 * solo["seconds_alone"]),
@@ -441,7 +454,7 @@ def main() -> int:
         if comm is not None:
             comm.close()
         pool.close()
-        return out, roof, cpu
+        return out, (roof if sampled else None), cpu
 
     # ------------------------------------------------------------------------------------------------------------------
     # N > 1: the sharded frontier is the headline
@@ -465,14 +478,14 @@ def main() -> int:
                 dumped = dump_outputs(args.dump_outputs, {"status": status, "z": z, "x": x, "has_x": has_x,
                                                           "incumbent_z": [w["incumbent_z"]], "incumbent_index": [w["incumbent_index"]]})
         wide = None
-        if args.frontier_wide_vars > args.frontier_vars:
+        if args.full and args.frontier_wide_vars > args.frontier_vars:
             # second line: a frontier wider than one GPU's 256 CUs (2^11 = 2048 children of the same root), sharded the same way — the
             # shape where more GPUs can pay; compare with `frontier_wide` of the --gpus 1 line
             wout, _, _ = frontier_leg(3, 2, nvars=args.frontier_wide_vars, light=True)
             wide = {k: wout[k] for k in ("workload", "relaxations_per_s", "wave_seconds", "waves_timed", "pivots_per_wave", "feasible_children",
                                          "host_fallbacks_per_wave", "device_batched_per_wave", "schedule", "per_rank")}
         xwide = None
-        if args.frontier_xwide_vars > args.frontier_wide_vars:
+        if args.full and args.frontier_xwide_vars > args.frontier_wide_vars:
             # third line: 2^13 = 8192 children — one GPU needs ~4x the 2048-wide wave for it, more than 6x its heaviest child: the width at
             # which the >= 6x of BASELINE.json is arithmetically reachable from 8 GPUs; compare with `frontier_xwide` of the --gpus 1 line
             xout, _, _ = frontier_leg(2, 1, nvars=args.frontier_xwide_vars, light=True)
@@ -634,6 +647,12 @@ def main() -> int:
     }
     if dumped is not None:
         out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if not args.full:
+        # a plain run ends at its headline: every leg below takes runs of its own
+        emit(out)
+        prob.free()
+        ctx.close()
+        return 0
 
     # ---- CPU baseline (the oracle = the reference algorithm), bounded sample of the same workload.  Timed LAST (deferred below): 15-25 s
     # of 16 busy host threads in front of the latency-bound GPU legs cost those legs 5-10 % (frontier wave 3.7 -> 4.1 ms on the same box)

@@ -7,8 +7,8 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 cd $R
 HEAD="--no-cpu-baseline --concurrent 0 --milp-nodes 0 --c4 0 --frontier-vars 0 --general 0"
-# 1. default bench, unprofiled (the numbers DESIGN.md quotes)
-python bench.py > $OUT/bench_unprofiled.json 2> $OUT/bench_unprofiled.err
+# 1. the full bench, unprofiled (the numbers DESIGN.md quotes)
+python bench.py --full > $OUT/bench_unprofiled.json 2> $OUT/bench_unprofiled.err
 # 2. kernel stats of the headline region alone (metric LP) and of the frontier leg alone
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_M -- python3 bench.py $HEAD > $OUT/bench_M_profiled.json 2> $OUT/stats_M.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_C5 -- python3 tools/wave_prof.py 8 4 > $OUT/wave_profiled.out 2> $OUT/stats_C5.err
