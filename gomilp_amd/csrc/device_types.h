@@ -107,6 +107,11 @@ struct LPArgs {
     DevPivot *trace;
     int64_t trace_cap;
     int32_t row_chunk2;    // > 0: K1-K3 in the chunked form, vectors staged this many double2 at a time (multiple of 256)
+    // Exact-step guard of K1-K3 (the meaning of BTArgs::guard; only the non-slack starts of the three-kernel loop set it): 0 off,
+    // 1e-9 guarded, +Inf strict.  > 0: the guard instances of the kernels, whose pricing / ratio partials carry each workgroup's
+    // runner-up key beside its winner (pk_price / pk_ratio + kMaxPartials), stop (ST_NEED_EXACT) in front of a decision the
+    // rounding noise of the reference's fresh solves takes: Engine::run_loop repeats it on fresh gonum-order solves
+    double guard;
 };
 
 // Arguments of the single-kernel tableau pivot (tableau_kernels.hip).

@@ -127,7 +127,8 @@ int Engine::ensure_work(int m, int ncols) {
     if (!w.st) {
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device_) == hipSuccess && ncu > 0) ncu_ = ncu;
-        HIP_TRY(dmalloc(&w.pk_price, kMaxPartials)); HIP_TRY(dmalloc(&w.pk_ratio, kMaxPartials));
+        // (the keys twice over: the runner-up keys of the guard instances of K1-K3 follow at + kMaxPartials, LPArgs::guard)
+        HIP_TRY(dmalloc(&w.pk_price, 2 * kMaxPartials)); HIP_TRY(dmalloc(&w.pk_ratio, 2 * kMaxPartials));
         HIP_TRY(dmalloc(&w.pi_price, kMaxPartials)); HIP_TRY(dmalloc(&w.pi_ratio, kMaxPartials));
         HIP_TRY(dmalloc(&w.pv_price, kMaxPartials)); HIP_TRY(dmalloc(&w.pb_ratio, kMaxPartials)); HIP_TRY(dmalloc(&w.pd_ratio, kMaxPartials)); HIP_TRY(dmalloc(&w.px_ratio, kMaxPartials));
         for (int t = 0; t < 2; t++) {
@@ -450,6 +451,7 @@ LPArgs Engine::make_args(const Problem &P, int phase, double tol, int nn, const 
     a.trace = (trace_on_ || shadow_trace_) ? w.trace : nullptr;
     a.trace_cap = w.trace_cap;
     a.row_chunk2 = row_chunk2(P);
+    a.guard = lp_guard_;
     return a;
 }
 
@@ -626,7 +628,7 @@ void Engine::account_samples(gomilp_lp_stats *st, const std::vector<int64_t> &sa
 }
 
 int Engine::run_loop(const Problem &P, int phase, double tol, int nn, const double *cost, gomilp_lp_stats *st) {
-    if (fused_ && fused_supported(P.ld)) return run_loop_fused(P, phase, tol, nn, cost, st);
+    if (fused_ && fused_supported(P.ld) && !gen_revised_) return run_loop_fused(P, phase, tol, nn, cost, st);   // (no guard there: general starts stay here)
     Work &w = *w_;
     DevState &hs = *w.st_host;
     hs.done = 0; hs.status = ST_RUNNING; hs.pivots = 0; hs.q = hs.p = -1; hs.rq = hs.dp = hs.mv = 0;
@@ -680,6 +682,61 @@ int Engine::run_loop(const Problem &P, int phase, double tol, int nn, const doub
             int rc = host_bland(P, a, st);
             if (rc != GOMILP_OK) { ret = rc; break; }
             // resume: the update kernel of the Bland step has been enqueued; read the state back after it
+            HIP_TRY(hipMemcpyAsync(w.st_host, w.st, sizeof(DevState), hipMemcpyDeviceToHost, stream_));
+            HIP_TRY(sync_stream());
+            hs.done = 0; hs.status = ST_RUNNING;
+            sync_state_to_device();
+            continue;
+        }
+        if (hs.status == ST_NEED_EXACT) {
+            // The guard instances stopped in front of a decision that the rounding noise of the reference's fresh solves takes
+            // (LPArgs::guard): the reference's iteration on fresh gonum-order solves decides it (exact_iter, as the blocked tableau's
+            // exact step does).  Its y, r and x_B replace the running ones; the pivot it decides runs as a forced pivot on the running
+            // B^-1, whose column a_q is checked against the fresh one first (re-inverted beyond 1e-6 of the column's size, up to 1024
+            // rows: the tableau's rule).
+            const DevState keep = hs;   // (the final solve keeps its singular flag in the same block and reads it back)
+            auto check = [&](int, int var, const std::vector<int32_t> &basic, const std::vector<double> &dsol) -> int {
+                if (P.m > 1024) return GOMILP_OK;
+                launch_matvec_rows(w.binv[cur_], P.ld, P.m, P.dAt + (size_t)var * P.ld, w.dvec, stream_, row_chunk2(P));
+                launches_++;
+                bool rebuilt = false;
+                return exact_column_check(P, basic, dsol, w.dvec, w.binv[cur_], &rebuilt, st);
+            };
+            int fq = -1, fp = -1;
+            const int verdict = exact_iter(P, phase, tol, nn, w.yb[ycur_], w.rvec, nn, check, &fq, &fp, st);
+            hs = keep;
+            hs.done = 0; hs.status = ST_RUNNING; hs.lu_singular = 0;
+            if (verdict < 0) {
+                ret = -verdict;
+                // an exactly singular basis is the reference's mat.Condition (gonum's ErrSingular is Condition(+Inf): simplex.go:236-239,
+                // 289-292 leave the loop with it) — past the reference's own Condition exit, where modes 1 / 2 may go on
+                double k1 = 0, kinf = 0;
+                if (ret == GOMILP_ERR_LINSOLVE && cond_fresh(P, nullptr, &k1, &kinf) == GOMILP_OK && !(k1 < 1e16)) ret = GOMILP_ERR_CONDITION;
+                // strict: the pivot into this basis was decided in the previous exact step, and a singular basis keeps that step's fresh
+                // x_B (the reference's receiver keeps its values when Det() == 0, simplex.go:289-292; the epilogue returns it)
+                if (ret == GOMILP_ERR_CONDITION && lp_guard_ == std::numeric_limits<double>::infinity() && exact_xb_.size() == (size_t)P.m) {
+                    std::vector<double> xpad(P.ld, 0.0);
+                    std::copy(exact_xb_.begin(), exact_xb_.end(), xpad.begin());
+                    const int rc = stage_upload(w.xb, xpad.data(), (size_t)P.ld * sizeof(double));
+                    if (rc != GOMILP_OK) ret = rc;
+                }
+                break;
+            }
+            if (verdict == 1) { hs.done = 1; hs.status = ST_OPTIMAL; break; }
+            if (verdict == 2) { ret = GOMILP_ERR_UNBOUNDED; break; }
+            if (verdict != 0 && verdict != 3) { ret = verdict; break; }   // (a runtime failure inside)
+            sync_state_to_device();
+            LPArgs a = make_args(P, phase, tol, nn, cost);
+            if (verdict == 3) {   // (no host copy of A for the kappa_1 test: the host Bland branch on the fresh r / x_B)
+                const int rc = host_bland(P, a, st);
+                if (rc != GOMILP_OK) { ret = rc; break; }
+            } else {
+                // st->q / st->rq come from the fresh r (pick_entering reads rvec[q]): commit_pivot updates y with them
+                launch_ftran(a, 0, fq, -1, stream_);
+                launch_update(a, 0, fp, 0, 0, stream_);
+                launches_ += 2;
+                cur_ ^= 1;
+            }
             HIP_TRY(hipMemcpyAsync(w.st_host, w.st, sizeof(DevState), hipMemcpyDeviceToHost, stream_));
             HIP_TRY(sync_stream());
             hs.done = 0; hs.status = ST_RUNNING;
@@ -1320,30 +1377,41 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
     if (!unit_basis && P.ld > kLdsWindowLd) return finish(GOMILP_ERR_UNSUPPORTED);   // (the general start's search and set-up stage m-long rows)
     gen_start_ = !unit_basis;
     gen_binv_dev_ = false;
+    struct RouteReset { Engine *e; ~RouteReset() { e->gen_revised_ = false; e->lp_guard_ = 0.0; } } route_reset{this};   // (per solve)
+    exact_xb_.clear();
     badly_scaled_ = P.scale_span > 1e9;
     const int nn_max = n + 1 - m;
-    // a non-slack starting basis (equality rows, supplied basis) always takes the tableau pipelines: their set-up accepts
-    // any B^-1; the n - m < 2m rule is only the bytes-per-pivot trade-off between the two formulations.  So does a wide LP whose
+    // a non-slack starting basis (equality rows, supplied basis) takes the tableau pipelines wherever their row fits: their set-up
+    // accepts any B^-1; the n - m < 2m rule is only the bytes-per-pivot trade-off between the two formulations.  So does a wide LP whose
     // exact_degenerate mode asks for exact steps on this problem (the predicate of make_bt_args' guard, engine_tableau.cpp) when the
-    // BLOCKED tableau takes it: only the block kernels stop in front of a degenerate pivot (ST_NEED_EXACT) for Engine::exact_step — the
-    // single-kernel tableau and the revised pipelines decide every pivot on their updated quantities.  (tableau = 0 keeps the revised
-    // pipelines, blocked = 0 the n - m < 2m rule, both without the guard: A/B knobs.)
+    // BLOCKED tableau takes it: on slack starts only the block kernels stop in front of a degenerate pivot (ST_NEED_EXACT) for
+    // Engine::exact_step — the single-kernel tableau and the revised pipelines decide every pivot on their updated quantities.
+    // (tableau = 0 keeps the revised pipelines, blocked = 0 the n - m < 2m rule, both without the guard on slack starts: A/B knobs.)
     const bool tab_fits = (size_t)tab_ld(nn_max) * sizeof(double) <= 64 * 1024;
     const bool bt_ok = blocked_ && bt_supported(m, nn_max);
     const bool exact_wanted = exact_degenerate_ == 3 || exact_degenerate_ == 2 || (exact_degenerate_ == 1 && (m <= 256 || !unit_basis || badly_scaled_));
     // (beyond the LDS window only the three-kernel revised simplex runs: the single-kernel tableau returned a wrong ErrUnbounded on a
     // 12288 x 18432 slack start after a run of Bland steps — DESIGN.md §2.1, "Beyond 8192 rows")
     const bool use_tab = tableau_ && ((n - m) < 2 * m || !unit_basis || (exact_wanted && bt_ok)) && tab_fits && P.ld <= kLdsWindowLd;
-    // strict mode IS the exact steps: where the blocked tableau does not run, the solve refuses instead of deciding the default way
-    if (exact_degenerate_ == 3 && !(use_tab && bt_ok)) return finish(GOMILP_ERR_UNSUPPORTED);
+    // A non-slack start the tableau does not take (its row beyond the LDS window: n - m > 8191, or knob tableau = 0) runs the
+    // three-kernel revised loop with the exact-step guard of make_bt_args for general starts (LPArgs::guard; the fused pipeline has
+    // none): the exact steps need the host copy of A, kept up to m * n = 2^25
+    const bool gen_rev = !unit_basis && !use_tab && (size_t)m * (size_t)n <= ((size_t)1 << 25) && ensure_host_A(P);
+    // strict mode IS the exact steps: where neither the blocked tableau nor that loop runs, the solve refuses instead of deciding the
+    // default way
+    if (exact_degenerate_ == 3 && !(use_tab && bt_ok) && !gen_rev) return finish(GOMILP_ERR_UNSUPPORTED);
+    if (gen_rev) {
+        gen_revised_ = true;
+        lp_guard_ = exact_degenerate_ == 3 ? inf : exact_degenerate_ == 0 ? 0.0 : 1e-9;
+    }
     std::vector<double> xb(m, 0.0), binv_host;
     bool feasible = true;
     if (unit_basis) {
         // ab = permutation, xb = ab^-1 b exactly (initializeFromBasic, simplex.go:447-471)
         for (int pos = 0; pos < m; pos++) { xb[pos] = P.hb[rho[pos]]; if (xb[pos] < -1e-13) feasible = false; }
     } else {
-        // general case (engine_general.cpp): host search over a kept copy of A, small problems on the tableau pipelines
-        if (!use_tab || !ensure_host_A(P)) return finish(GOMILP_ERR_UNSUPPORTED);
+        // general case (engine_general.cpp): host search over a kept copy of A; the tableau pipelines, or the guarded revised loop
+        if (!(use_tab || gen_rev) || !ensure_host_A(P)) return finish(GOMILP_ERR_UNSUPPORTED);
         const double t_g0 = now_s();
         if (!initial_basic) {
             // 96 rows and more (knob general_min_rows): the scan runs on the device — whole solves with the host / the blocked device search,
@@ -1377,6 +1445,16 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
         if ((rc = stage_upload(w.rho, rho.data(), (size_t)m * sizeof(int32_t))) != GOMILP_OK) return finish(rc);
         launch_set_binv_perm(w.binv[0], P.ld, m, w.rho, stream_);
     }
+    if (gen_rev) {   // the searched (or supplied) basis' B^-1: in place from the device search, else the host's (the tableau set-up's copy)
+        if (!gen_binv_dev_) {
+            HIP_TRY(hipMemsetAsync(w.binv[0], 0, (size_t)m * P.ld * sizeof(double), stream_));
+            HIP_TRY(hipMemcpy2DAsync(w.binv[0], (size_t)P.ld * sizeof(double), binv_host.data(), (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
+                                     hipMemcpyHostToDevice, stream_));
+            HIP_TRY(sync_stream());   // (pageable source)
+        } else if (P.ld > m) {   // (the K1-K3 rows run over the padding column too)
+            HIP_TRY(hipMemset2DAsync(w.binv[0] + m, (size_t)P.ld * sizeof(double), 0, sizeof(double), m, stream_));
+        }
+    }
     ycur_ = 0;
     if (!use_tab) {   // the duals only exist on the revised-simplex pipelines
         HIP_TRY(hipMemsetAsync(w.yb[0], 0, (size_t)P.ld * sizeof(double), stream_));
@@ -1391,7 +1469,7 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
     // pipeline choice: the explicit tableau moves 16*m*(n-m) bytes per pivot in one launch, the revised form
     // 8*[m(n-m) + 2m^2] in two: the tableau wins while n - m < 2m
     use_bt_ = use_tab && bt_ok;
-    st->pipeline = use_tab ? (use_bt_ ? 3 : 2) : ((fused_ && fused_supported(P.ld)) ? 1 : 0);
+    st->pipeline = use_tab ? (use_bt_ ? 3 : 2) : ((fused_ && fused_supported(P.ld) && !gen_rev) ? 1 : 0);
     int loop_rc = GOMILP_OK;
     if (use_tab) {
         const int ldt = tab_ld(nn_max);
@@ -1437,15 +1515,31 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
         // ---- Phase I (simplex.go:529-606) ----
         st->phase1_used = 1;
         const int64_t minidx = min_idx(xb.data(), m);
-        // a_{n+1} = b - sum_{i != minidx} a_{basic_i}: for unit columns one exact "- 1" per row (floats.Sub, :536-542)
+        // a_{n+1} = b - sum_{i != minidx} a_{basic_i}: for unit columns one exact "- 1" per row (floats.Sub, :536-542); a searched basis
+        // subtracts its full columns, on the device from general_min_rows on (k_gs_art, as solve_tableau)
         std::vector<double> art(P.ld, 0.0);
+        const bool art_on_device = gen_rev && m >= general_min_rows_;
         for (int k = 0; k < m; k++) art[k] = P.hb[k];
-        for (int i = 0; i < m; i++) { if (i == minidx) continue; art[rho[i]] = -1 * 1.0 + art[rho[i]]; }
+        if (unit_basis) {
+            for (int i = 0; i < m; i++) { if (i == minidx) continue; art[rho[i]] = -1 * 1.0 + art[rho[i]]; }
+        } else if (art_on_device) {   // (w.basic holds the searched basis: uploaded for the x_B solve)
+            launch_gs_art(P.dAt, P.ld, m, w.basic, (int)minidx, P.db, P.dAt + (size_t)n * P.ld, stream_);
+            launches_++;
+            HIP_TRY(hipMemcpyAsync(art.data(), P.dAt + (size_t)n * P.ld, (size_t)P.ld * sizeof(double), hipMemcpyDeviceToHost, stream_));
+            HIP_TRY(sync_stream());
+        } else {
+            for (int i = 0; i < m; i++) {
+                if (i == minidx) continue;
+                for (int k = 0; k < m; k++) art[k] = -1 * P.hA[(size_t)k * n + basic[i]] + art[k];
+            }
+        }
         bool art_zero = true;
         for (int k = 0; k < m; k++) if (art[k] != 0) { art_zero = false; break; }
         if (art_zero) { st->wrapped_status = GOMILP_ERR_ZERO_COLUMN; return finish(GOMILP_ERR_PHASE1_WRAPPED); }  // verifyInputs of the recursive call
-        HIP_TRY(hipMemcpyAsync(P.dAt + (size_t)n * P.ld, art.data(), (size_t)P.ld * sizeof(double), hipMemcpyHostToDevice, stream_));
-        HIP_TRY(sync_stream());
+        if (!art_on_device) {
+            HIP_TRY(hipMemcpyAsync(P.dAt + (size_t)n * P.ld, art.data(), (size_t)P.ld * sizeof(double), hipMemcpyHostToDevice, stream_));
+            HIP_TRY(sync_stream());
+        }
         // basis := slack basis with position minidx replaced by the artificial: one forced pivot builds its inverse
         w.st_host->done = 0; w.st_host->status = ST_RUNNING; w.st_host->pivots = 0; w.st_host->max_pivots = 0; w.st_host->rq = 0;
         sync_state_to_device();

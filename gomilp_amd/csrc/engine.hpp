@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -187,8 +188,14 @@ class Engine {
         std::vector<double> diag;        // u_ii by physical row
         LUArgs args;
     } lu_cache_;
-    // one iteration of the reference on fresh solves (engine_tableau.cpp): the decision a degenerate or tied pivot needs
+    // one iteration of the reference on fresh solves (engine_tableau.cpp): the decision a degenerate or tied pivot needs — exact_iter,
+    // shared by the blocked tableau (exact_step) and the three-kernel revised loop of non-slack starts (run_loop)
     int exact_step(const Problem &P, int phase, double tol, int nn, int *q_out, int *p_out, gomilp_lp_stats *st);
+    int exact_iter(const Problem &P, int phase, double tol, int nn, double *y_dev, double *r_dev, int ldr,
+                   const std::function<int(int, int, const std::vector<int32_t> &, const std::vector<double> &)> &check_column, int *q_out,
+                   int *p_out, gomilp_lp_stats *st);
+    int exact_column_check(const Problem &P, const std::vector<int32_t> &basic, const std::vector<double> &dsol, const double *col_dev,
+                           double *binv_dst, bool *rebuilt, gomilp_lp_stats *st);
     int cond_check(const Problem &P, int nn, double *k1, double *kinf);
     int cond_fresh(const Problem &P, const int32_t *basic_host, double *k1, double *kinf);   // from a fresh host inverse of the basis
     int groups_knob(const Problem &P) const;
@@ -234,6 +241,9 @@ class Engine {
     bool badly_scaled_ = false;   // the current problem's entries span more than nine decades (Problem::scale_span): guard on, tableau checked
     bool gen_binv_dev_ = false;   // the searched basis' B^-1 = R^-1 Q^T is resident in the first B^-1 buffer (the device judged the square step): no upload
     bool gen_start_ = false;      // the current solve starts from a searched (non-slack) basis: the degenerate-pivot guard stays on
+    bool gen_revised_ = false;    // ... and runs on the three-kernel revised loop (beyond the tableau's LDS row, or knob tableau = 0)
+    double lp_guard_ = 0.0;       // LPArgs::guard of that loop (0 for every other solve): the exact steps of Engine::run_loop
+    std::vector<double> exact_xb_;   // the fresh x_B of the last exact step (exact_iter)
     bool xchg_timeout_ = false;   // the last pivot loop ended in ST_XCHG_TIMEOUT (Engine::solve repeats the solve once)
     bool shadow_trace_ = false;   // this solve records its pivots for the replay even when the caller did not ask for a trace   // developer knobs of the block kernels (per context: tests force the 1024-thread instance)
     // per-solve state

@@ -275,14 +275,70 @@ int Engine::bt_forced_pivot(const Problem &P, int phase, double tol, int nn, int
     return GOMILP_OK;
 }
 
-// One iteration of the reference on FRESH solves (simplex.go:233-277), for a pivot the block kernel would not decide on its
+// The exact step of the blocked tableau (run_loop_bt, ST_NEED_EXACT): Engine::exact_iter with the tableau's own accuracy check.
+// Accuracy of the resident tableau: its column q against the fresh one.  On badly scaled LPs (entries over 1e19) the updated
+// tableau loses digits within a few hundred pivots, its ratio tests then leave the reference's path and may never end; beyond
+// 1e-6 of the column's size the tableau is rebuilt from a fresh inverse of the basis (B^-1 on the host, T = B^-1 A_N as one
+// device GEMM: the set-up of a general start), up to 1024 rows
+int Engine::exact_step(const Problem &P, int phase, double tol, int nn, int *q_out, int *p_out, gomilp_lp_stats *st) {
+    Work &w = *w_;
+    auto check = [&](int q, int, const std::vector<int32_t> &basic, const std::vector<double> &dsol) -> int {
+        if (P.m > 1024) return GOMILP_OK;
+        launch_tab_column(w.T[tcur_], ldt_, P.m, q, w.xb, w.dvec, w.move, t_tiled_, stream_);
+        launches_++;
+        bool rebuilt = false;
+        const int rc = exact_column_check(P, basic, dsol, w.dvec, w.binv[0], &rebuilt, st);
+        if (rc == GOMILP_OK && rebuilt) {
+            launch_tab_gemm(w.binv[0], P.ld, P.dAt, P.ld, P.m, nn, w.nonbasic, w.T[tcur_], ldt_, t_tiled_, stream_);
+            launches_++;
+        }
+        return rc;
+    };
+    return exact_iter(P, phase, tol, nn, w.dvec, w.R[rcur_], ldt_, check, q_out, p_out, st);
+}
+
+// The running quantities of a pivot loop against the fresh column dsol = ab^-1 a_q of an exact step (bases of up to 1024 rows):
+// col_dev holds the loop's own B^-1 a_q (m doubles).  Beyond 1e-6 of the column's size the basis is inverted afresh on the host
+// into binv_dst (m rows of P.ld doubles) and *rebuilt is set; the caller rebuilds what it derives from B^-1.
+int Engine::exact_column_check(const Problem &P, const std::vector<int32_t> &basic, const std::vector<double> &dsol, const double *col_dev,
+                               double *binv_dst, bool *rebuilt, gomilp_lp_stats *st) {
+    Work &w = *w_;
+    const int m = P.m;
+    *rebuilt = false;
+    if (m > 1024) return GOMILP_OK;
+    HIP_TRY(hipMemcpyAsync(w.h_vec, col_dev, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(sync_stream());
+    double scale = 0, err = 0;
+    for (int i = 0; i < m; i++) { scale = std::max(scale, fabs(dsol[i])); err = std::max(err, fabs(w.h_vec[i] - dsol[i])); }
+    if (err <= 1e-6 * scale) return GOMILP_OK;
+    std::vector<double> cols((size_t)m * P.ld), B((size_t)m * m), inv;
+    for (int p = 0; p < m; p++)
+        HIP_TRY(hipMemcpyAsync(&cols[(size_t)p * P.ld], P.dAt + (size_t)basic[p] * P.ld, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(sync_stream());
+    for (int i = 0; i < m; i++) for (int p = 0; p < m; p++) B[(size_t)i * m + p] = cols[(size_t)p * P.ld + i];
+    if (!general_invert(B, m, inv)) return GOMILP_ERR_LINSOLVE;
+    HIP_TRY(hipMemcpy2DAsync(binv_dst, (size_t)P.ld * sizeof(double), inv.data(), (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
+                             hipMemcpyHostToDevice, stream_));
+    HIP_TRY(sync_stream());   // (pageable source)
+    *rebuilt = true;
+    if (st) st->refreshes++;
+    if (GOMILP_DBG_ENV("GOMILP_DEBUG_LOOP")) fprintf(stderr, "exact step: B^-1 rebuilt (column error %.3g of %.3g, m %d)\n", err, scale, m);
+    return GOMILP_OK;
+}
+
+// One iteration of the reference on FRESH solves (simplex.go:233-277), for a pivot the pivot kernels would not decide on their
 // updated quantities (ST_NEED_EXACT: reduced cost at the stop threshold, tied reduced costs, winning ratio (nearly) zero, tied
 // ratios — the places where the rounding noise of the reference's three LU solves per pivot takes the decision).  Same
 // arithmetic: y from a gonum-order LU of ab^T with right-hand side c_B, r = c_N - an^T y in Dgemv / SubTo order on the device,
-// d and x_B from gonum-order LUs of ab.  Afterwards the fresh r and x_B are resident; returns
-//   0 pivot (q, p) decided — the caller enqueues it as a forced pivot; 1 optimal; 2 unbounded; 3 move[replace] <= 0: the Bland
-//   rule, which the block kernel runs on the fresh r / x_B (exact_once); < 0: -status of a failure.
-int Engine::exact_step(const Problem &P, int phase, double tol, int nn, int *q_out, int *p_out, gomilp_lp_stats *st) {
+// d and x_B from gonum-order LUs of ab.  Shared by the blocked tableau (exact_step) and the three-kernel revised loop (run_loop):
+// the fresh y goes to y_dev (P.ld doubles, zero padded), r to r_dev (ldr doubles, zero beyond nn), x_B to w.xb — resident
+// afterwards; check_column(q, nonbasic[q], basic, d) is the pipeline's accuracy check of its running quantities against the fresh column of the
+// Dantzig choice q (a positive status: failure).  Returns
+//   0 pivot (q, p) decided — the caller enqueues it as a forced pivot; 1 optimal; 2 unbounded; 3 move[replace] <= 0 and no host copy
+//   of A: the Bland rule, which the caller runs on the fresh r / x_B; < 0: -status of a failure.
+int Engine::exact_iter(const Problem &P, int phase, double tol, int nn, double *y_dev, double *r_dev, int ldr,
+                       const std::function<int(int, int, const std::vector<int32_t> &, const std::vector<double> &)> &check_column,
+                       int *q_out, int *p_out, gomilp_lp_stats *st) {
     Work &w = *w_;
     const int m = P.m, n = P.n;
     std::vector<int32_t> basic(m), nonbasic(nn);
@@ -296,7 +352,7 @@ int Engine::exact_step(const Problem &P, int phase, double tol, int nn, int *q_o
     // gonum's guards on the solves of this iteration (mat/lu.go:321: cond > 1e16 -> mat.Condition out of the duals' solve,
     // simplex.go:236-239; lp.ErrLinSolve out of computeMove, :316-318): the tableau of a slack-basis start holds B^-1, so the exact
     // kappa_1 / kappa_inf of the current basis cost three small launches (cond_check) — every exact step measures them
-    if (cond_guard_ && !gen_start_ && m > 64) {   // (Phase I too: the artificial column is a column of the basis like any other)
+    if (cond_guard_ && !gen_start_ && m > 64) {   // (Phase I too: the artificial column is a column of the basis like any other; tableau only: the revised route runs general starts)
         double k1 = 0, kinf = 0;
         int rc0 = cond_check(P, nn, &k1, &kinf);
         if (rc0 != GOMILP_OK) return -rc0;
@@ -321,12 +377,12 @@ int Engine::exact_step(const Problem &P, int phase, double tol, int nn, int *q_o
     {
         std::vector<double> ypad(P.ld, 0.0);
         std::copy(y.begin(), y.begin() + m, ypad.begin());
-        if ((rc = stage_upload(w.dvec, ypad.data(), (size_t)P.ld * sizeof(double))) != GOMILP_OK) return -rc;
+        if ((rc = stage_upload(y_dev, ypad.data(), (size_t)P.ld * sizeof(double))) != GOMILP_OK) return -rc;
     }
-    launch_exact_r(P.dAt, P.ld, m, nn, w.nonbasic, w.dvec, phase == 1 ? P.dc1 : P.dc, w.R[rcur_], ldt_, stream_);
+    launch_exact_r(P.dAt, P.ld, m, nn, w.nonbasic, y_dev, phase == 1 ? P.dc1 : P.dc, r_dev, ldr, stream_);
     launches_++;
     std::vector<double> r(nn);
-    HIP_TRY(hipMemcpyAsync(w.h_vec, w.R[rcur_], (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(w.h_vec, r_dev, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(sync_stream());
     for (int j = 0; j < nn; j++) r[j] = w.h_vec[j];
     // x_B of this iteration (simplex.go:289 of the previous one): resident from here on
@@ -335,6 +391,7 @@ int Engine::exact_step(const Problem &P, int phase, double tol, int nn, int *q_o
     if ((rc = lu_factor(P, &sing, basic.data())) != GOMILP_OK) return -rc;
     if (sing) { if (GOMILP_DBG_ENV("GOMILP_DEBUG_LOOP")) fprintf(stderr, "exact_step: ab singular for x_B (phase %d, m %d)\n", phase, m); return -GOMILP_ERR_LINSOLVE; }
     if ((rc = lu_solve(P, xb)) != GOMILP_OK) return -rc;
+    exact_xb_ = xb;
     {
         std::vector<double> xpad(P.ld, 0.0);
         std::copy(xb.begin(), xb.begin() + m, xpad.begin());
@@ -352,33 +409,7 @@ int Engine::exact_step(const Problem &P, int phase, double tol, int nn, int *q_o
         for (int i = 0; i < m; i++) col[i] = w.h_vec[i];
     }
     if ((rc = lu_solve(P, dsol, col.data())) != GOMILP_OK) return -rc;
-    // Accuracy of the resident tableau: its column q against the fresh one.  On badly scaled LPs (entries over 1e19) the updated
-    // tableau loses digits within a few hundred pivots, its ratio tests then leave the reference's path and may never end; beyond
-    // 1e-6 of the column's size the tableau is rebuilt from a fresh inverse of the basis (B^-1 on the host, T = B^-1 A_N as one
-    // device GEMM: the set-up of a general start), up to 1024 rows
-    if (m <= 1024) {
-        launch_tab_column(w.T[tcur_], ldt_, m, (int)q, w.xb, w.dvec, w.move, t_tiled_, stream_);
-        launches_++;
-        HIP_TRY(hipMemcpyAsync(w.h_vec, w.dvec, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(sync_stream());
-        double scale = 0, err = 0;
-        for (int i = 0; i < m; i++) { scale = std::max(scale, fabs(dsol[i])); err = std::max(err, fabs(w.h_vec[i] - dsol[i])); }
-        if (!(err <= 1e-6 * scale)) {
-            std::vector<double> cols((size_t)m * P.ld), B((size_t)m * m), inv;
-            for (int p = 0; p < m; p++)
-                HIP_TRY(hipMemcpyAsync(&cols[(size_t)p * P.ld], P.dAt + (size_t)basic[p] * P.ld, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
-            HIP_TRY(sync_stream());
-            for (int i = 0; i < m; i++) for (int p = 0; p < m; p++) B[(size_t)i * m + p] = cols[(size_t)p * P.ld + i];
-            if (!general_invert(B, m, inv)) return -GOMILP_ERR_LINSOLVE;
-            HIP_TRY(hipMemcpy2DAsync(w.binv[0], (size_t)P.ld * sizeof(double), inv.data(), (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
-                                     hipMemcpyHostToDevice, stream_));
-            HIP_TRY(sync_stream());   // (pageable source)
-            launch_tab_gemm(w.binv[0], P.ld, P.dAt, P.ld, m, nn, w.nonbasic, w.T[tcur_], ldt_, t_tiled_, stream_);
-            launches_++;
-            if (st) st->refreshes++;
-            if (GOMILP_DBG_ENV("GOMILP_DEBUG_LOOP")) fprintf(stderr, "exact_step: tableau rebuilt (column error %.3g of %.3g, m %d)\n", err, scale, m);
-        }
-    }
+    if ((rc = check_column((int)q, nonbasic[q], basic, dsol)) != GOMILP_OK) return -rc;
     std::vector<double> move(m);
     bool anyneg = false;
     for (int i = 0; i < m; i++) {

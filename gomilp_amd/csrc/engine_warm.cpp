@@ -33,6 +33,8 @@ void Engine::drop_kept(int64_t id) {
 //   tableau pipelines (2, 3) on a slack-basis start: gathered from T = B^-1 A_N — column r of B^-1 is B^-1 a_s for the unit column s of
 //   row r (the slack of the start): T's column of s when s is nonbasic, e_p when s is basic at position p.  T[tcur_] is fully updated
 //   here: the blocked loop applies every block's rank-K terms before it returns (the same state cond_check reads).
+//   A general start (no rho_slack) on the tableau or on the guarded revised loop keeps no B^-1: its children run cold (warm starts
+//   from such parents: not built).  (A warm solve's own state comes without rho_slack too, and is kept from B^-1 as above.)
 void Engine::keep_capture(const Problem &P, int64_t id, int pipeline, const std::vector<int32_t> &basic,
                           const std::vector<int32_t> &basic_start, const std::vector<int32_t> *rho_slack) {
     Work &w = *w_;
@@ -40,7 +42,7 @@ void Engine::keep_capture(const Problem &P, int64_t id, int pipeline, const std:
     Kept k;
     k.m = m; k.ld = P.ld; k.basic = basic;
     const bool tab = pipeline >= 2;
-    if (tab && !rho_slack) { k.no_warm = true; kept_[id] = std::move(k); return; }
+    if (!rho_slack && (tab || gen_revised_)) { k.no_warm = true; kept_[id] = std::move(k); return; }
     const size_t need = (size_t)m * P.ld;
     for (size_t i = 0; i < keep_pool_.size(); i++)
         if (keep_pool_[i].second >= need) {

@@ -96,6 +96,49 @@ __device__ __forceinline__ unsigned int reduce_partials(const unsigned long long
     return i;
 }
 
+// Guard mode of the revised-simplex kernels (LPArgs::guard): the first-index argmin and, beside it, the second smallest key of the
+// same set (an exact tie: the minimum twice).  (k2, i2, s2): the winner and runner-up of another set (~0ull: none).  The same
+// winning index on both sides is the same element (the lanes of a wave carry identical copies of their wave's winner): no tie.
+__device__ __forceinline__ void amin2_take(unsigned long long &k, unsigned int &i, unsigned long long &s, unsigned long long k2,
+                                           unsigned int i2, unsigned long long s2) {
+    s = s2 < s ? s2 : s;
+    if (i2 == i) return;
+    const bool take = k2 < k || (k2 == k && i2 < i);
+    const unsigned long long lose = take ? k : k2;
+    s = lose < s ? lose : s;
+    if (take) { k = k2; i = i2; }
+}
+
+// block_argmin with the runner-up key; result valid in every thread
+__device__ __forceinline__ void block_argmin2(unsigned long long &k, unsigned int &i, unsigned long long &s, unsigned long long *sk,
+                                              unsigned int *si, unsigned long long *ss) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long k2 = __shfl_xor(k, o, 64), s2 = __shfl_xor(s, o, 64);
+        const unsigned int i2 = __shfl_xor(i, o, 64);
+        amin2_take(k, i, s, k2, i2, s2);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sk[w] = k; si[w] = i; ss[w] = s; }
+    __syncthreads();
+    k = sk[0]; i = si[0]; s = ss[0];
+#pragma unroll
+    for (int t = 1; t < kWavesPerBlock; t++) amin2_take(k, i, s, sk[t], si[t], ss[t]);
+    __syncthreads();
+}
+
+// reduce_partials with the runner-up key (pk2: the workgroups' runner-up keys)
+__device__ __forceinline__ unsigned int reduce_partials2(const unsigned long long *pk, const unsigned int *pi, const unsigned long long *pk2,
+                                                         int nparts, unsigned long long *sk, unsigned int *si, unsigned long long *ss,
+                                                         unsigned long long *key_out, unsigned long long *key2_out) {
+    unsigned long long k = ~0ull, s = ~0ull;
+    unsigned int i = 0xFFFFFFFFu;
+    for (int t = threadIdx.x; t < nparts; t += kBlock) amin2_take(k, i, s, pk[t], pi[t], pk2[t]);
+    block_argmin2(k, i, s, sk, si, ss);
+    *key_out = k; *key2_out = s;
+    return i;
+}
+
 // argmin with two payload words travelling with the winner (fused pipeline: saves the dependent
 // global loads that would otherwise follow the reduction)
 struct ArgMinP {
@@ -379,6 +422,14 @@ __device__ __forceinline__ void publish_partials(unsigned long long &bk, unsigne
                                                  unsigned long long *pk, unsigned int *pi) {
     block_argmin(bk, bi, sk, si);
     if (threadIdx.x == 0) { pk[blockIdx.x] = bk; pi[blockIdx.x] = bi; }
+}
+
+// guard mode: the runner-up key too, into pk2 (reduce_partials2)
+__device__ __forceinline__ void publish_partials2(unsigned long long &bk, unsigned int &bi, unsigned long long &b2, unsigned long long *sk,
+                                                  unsigned int *si, unsigned long long *ss, unsigned long long *pk, unsigned int *pi,
+                                                  unsigned long long *pk2) {
+    block_argmin2(bk, bi, b2, sk, si, ss);
+    if (threadIdx.x == 0) { pk[blockIdx.x] = bk; pi[blockIdx.x] = bi; pk2[blockIdx.x] = b2; }
 }
 
 }  // namespace gomilp

@@ -24,6 +24,10 @@ namespace gomilp {
 // per-element work and the commit are the helpers below, so both forms take the same decisions from bit-identical values.
 // The helpers take the pointers they use, not the LPArgs: a reference to the kernel's argument hides from the compiler that those
 // pointers are kernel arguments that nothing in the kernel overwrites, and the kernel loses its scalar loads (rvec[q], nonbasic[q]).
+// Template parameter G (every K1-K3 kernel and helper): the exact-step guard (LPArgs::guard > 0).  G = false is the code of every
+// solve but the non-slack starts of the three-kernel loop; G = true carries each workgroup's runner-up key beside its winner (pk2 =
+// pk + kMaxPartials) and stops with ST_NEED_EXACT where the block kernel of the blocked tableau does (bt_kernels.hip: reduced costs at
+// the stop threshold or tied, a winning ratio at zero or tied, a pivot element of rounding-noise size; every decision when strict).
 // ------------------------------------------------------------------------------------------------
 
 // K1's gate: false once the loop has stopped, and when the pivot budget is spent (ST_MAX_PIVOTS)
@@ -38,20 +42,24 @@ __device__ __forceinline__ bool price_gate(DevState *st) {
 
 // reduced cost of nonbasic position pos (variable j, dot = At[j,:].y): r = cost[j] - dot (simplex.go:242-243) into rvec and the
 // running first-index argmin (:247)
+// (b2: the running runner-up key, G only)
+template <bool G>
 __device__ __forceinline__ void price_elem(const double *cost, double *rvec, int pos, int j, double dot, int lane, unsigned long long &bk,
-                                           unsigned int &bi) {
+                                           unsigned int &bi, unsigned long long &b2) {
     const double r = cost[j] - dot;
     if (lane == 0) rvec[pos] = r;
-    amin_take(bk, bi, ordkey(r), (unsigned int)pos);
+    if constexpr (G) amin2_take(bk, bi, b2, ordkey(r), (unsigned int)pos, ~0ull);
+    else amin_take(bk, bi, ordkey(r), (unsigned int)pos);
 }
 
 // K2's entering variable, into var (wave-uniform).  forced_var >= 0: the variable given; forced_pos = kDualPick: the dual pivot's
 // entering position, from the partials of k_dual_price (dual_kernels.hip); forced_pos >= 0: the position given (Bland / setup);
 // else the first-index argmin of the reduced costs and the optimality test.  false: the loop has stopped or stops here.
-// (pk / pi: the pricing partials; rvec, nonbasic, tol as in LPArgs)
+// (pk / pi: the pricing partials; rvec, nonbasic, tol, guard as in LPArgs; ss: block scratch of the runner-up keys, G only)
+template <bool G>
 __device__ __forceinline__ bool pick_entering(DevState *st, const unsigned long long *pk, const unsigned int *pi, int nparts_price,
-                                              const double *rvec, const int32_t *nonbasic, double tol, int forced_pos, int forced_var,
-                                              unsigned long long *sk, unsigned int *si, int &var) {
+                                              const double *rvec, const int32_t *nonbasic, double tol, double guard, int forced_pos,
+                                              int forced_var, unsigned long long *sk, unsigned int *si, unsigned long long *ss, int &var) {
     if (st->done) return false;
     int q = forced_pos;
     if (forced_var >= 0) {
@@ -67,8 +75,19 @@ __device__ __forceinline__ bool pick_entering(DevState *st, const unsigned long 
         var = nonbasic[q];
     } else {
         if (q < 0) {
-            q = (int)reduce_partials(pk, pi, nparts_price, sk, si, nullptr);
+            unsigned long long key, key2;
+            q = G ? (int)reduce_partials2(pk, pi, pk + kMaxPartials, nparts_price, sk, si, ss, &key, &key2)
+                  : (int)reduce_partials(pk, pi, nparts_price, sk, si, nullptr);
             const double rq = rvec[q];
+            if constexpr (G) {
+                // bt_kernels.hip's test: at the stop threshold only the drift of the updated reduced costs matters (1e-12); a tie
+                // matters only when the loop goes on; an infinite guard (strict) stops in front of every decision, the stop test too
+                const double r2 = orddecode(key2);
+                if (guard == __builtin_inf() || fabs(rq + tol) <= 1e-12 || (!(rq >= -tol) && r2 - rq <= guard * fmax(1.0, fabs(rq)))) {
+                    if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_NEED_EXACT; st->q = q; st->rq = rq; }
+                    return false;
+                }
+            }
             if (rq >= -tol) {  // simplex.go:248 — optimal
                 if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_OPTIMAL; st->q = q; st->rq = rq; }
                 return false;
@@ -84,28 +103,43 @@ __device__ __forceinline__ bool pick_entering(DevState *st, const unsigned long 
 
 // row i of the FTRAN (dp = B^-1[i,:].a_q): d = -d'_i, the ratio move_i = x_B[i]/|d_i| for d_i < 0 (simplex.go:306-342) into dvec /
 // move and the running first-index argmin of move (:268)
+template <bool G>
 __device__ __forceinline__ void ratio_elem(const double *xb, double *dvec, double *move, int i, double dp, int lane, unsigned long long &bk,
-                                           unsigned int &bi) {
+                                           unsigned int &bi, unsigned long long &b2) {
     double d = -dp;                       // simplex.go:319
     if (fabs(d) < 1e-13) d = 0;           // dRoundTol, :321-325
     const double mv = (d >= 0) ? __builtin_inf() : xb[i] / fabs(d);  // :334-340
     if (lane == 0) { dvec[i] = dp; move[i] = mv; }
-    amin_take(bk, bi, ordkey(mv), (unsigned int)i);
+    if constexpr (G) amin2_take(bk, bi, b2, ordkey(mv), (unsigned int)i, ~0ull);
+    else amin_take(bk, bi, ordkey(mv), (unsigned int)i);
 }
 
 // K3's leaving row, into p (wave-uniform).  forced_p >= 0: the row given; kDualPick: the one k_dual_leave chose (DevState::p); else
 // the first-index argmin of the ratios.  false: the loop has stopped or stops here (unbounded, or a degenerate step for Bland).
-// (pk / pi: the ratio partials)
+// (pk / pi: the ratio partials; dvec, guard as in LPArgs; ss as in pick_entering)
+template <bool G>
 __device__ __forceinline__ bool pick_leaving(DevState *st, const unsigned long long *pk, const unsigned int *pi, int nparts_ratio,
-                                             const double *move, int forced_p, unsigned long long *sk, unsigned int *si, int &p) {
+                                             const double *move, const double *dvec, double guard, int forced_p, unsigned long long *sk,
+                                             unsigned int *si, unsigned long long *ss, int &p) {
     if (st->done) return false;
     p = forced_p == kDualPick ? st->p : forced_p;
     if (p < 0) {
-        p = (int)reduce_partials(pk, pi, nparts_ratio, sk, si, nullptr);
+        unsigned long long key, key2;
+        p = G ? (int)reduce_partials2(pk, pi, pk + kMaxPartials, nparts_ratio, sk, si, ss, &key, &key2)
+              : (int)reduce_partials(pk, pi, nparts_ratio, sk, si, nullptr);
         const double mv = move[p];
         if (mv == __builtin_inf()) {  // no d_i < 0: unbounded (simplex.go:328-330)
             if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_UNBOUNDED; st->p = p; st->mv = mv; }
             return false;
+        }
+        if constexpr (G) {
+            // bt_kernels.hip's test, in front of the Bland stop: a winning ratio at zero, two rows within the guard of each other, or a
+            // pivot element of rounding-noise size — decided on a fresh gonum-order x_B, never by the host Bland branch on updated values
+            const double mv2 = orddecode(key2);
+            if (mv <= guard || mv2 - mv <= guard * fmax(1.0, fabs(mv)) || fabs(dvec[p]) <= guard) {
+                if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_NEED_EXACT; st->p = p; st->mv = mv; }
+                return false;
+            }
         }
         if (mv <= 0) {  // degenerate step -> Bland rule (simplex.go:269)
             if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_NEED_BLAND; st->p = p; st->mv = mv; }
@@ -170,35 +204,47 @@ __device__ __forceinline__ void commit_pivot(DevState *st, double *xb, double *y
 // K1  pricing:  r[pos] = cost[j] - At[j,:].y   (simplex.go:242-243), fused first-index argmin (:247)
 //     algorithmic traffic: m*(n-m)*8 bytes read (A_N once)
 // ------------------------------------------------------------------------------------------------
+// the workgroup's winner (and, G, its runner-up) into the partials
+template <bool G>
+__device__ __forceinline__ void publish(unsigned long long &bk, unsigned int &bi, unsigned long long &b2, unsigned long long *sk,
+                                        unsigned int *si, unsigned long long *ss, unsigned long long *pk, unsigned int *pi) {
+    if constexpr (G) publish_partials2(bk, bi, b2, sk, si, ss, pk, pi, pk + kMaxPartials);
+    else publish_partials(bk, bi, sk, si, pk, pi);
+}
+
+template <bool G>
 __global__ __launch_bounds__(kBlock) void k_price(LPArgs a) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
     if (!price_gate(a.st)) return;
     const int ld2 = a.ld >> 1;
     stage_vec(svec, a.y, ld2);
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
-    unsigned long long bk = ~0ull;
+    unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
     for (int pos = wave; pos < a.nn; pos += nwaves) {
         const int j = a.nonbasic[pos];
-        price_elem(a.cost, a.rvec, pos, j, wave_dot_row(a.At + (size_t)j * a.ld, svec, ld2, lane), lane, bk, bi);
+        price_elem<G>(a.cost, a.rvec, pos, j, wave_dot_row(a.At + (size_t)j * a.ld, svec, ld2, lane), lane, bk, bi, b2);
     }
-    publish_partials(bk, bi, sk, si, a.pk_price, a.pi_price);
+    publish<G>(bk, bi, b2, sk, si, ss, a.pk_price, a.pi_price);
 }
 
+template <bool G>
 __global__ __launch_bounds__(kBlock) void k_price_ck(LPArgs a, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
     if (!price_gate(a.st)) return;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
     const int kmax = (a.nn + nwaves - 1) / nwaves;
-    unsigned long long bk = ~0ull;
+    unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
     for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
         double dot[kCkRows][1];
@@ -206,10 +252,10 @@ __global__ __launch_bounds__(kBlock) void k_price_ck(LPArgs a, int ck2) {
 #pragma unroll
         for (int r = 0; r < kCkRows; r++) {
             const int pos = wave + (k0 + r) * nwaves;
-            if (pos < a.nn) price_elem(a.cost, a.rvec, pos, a.nonbasic[pos], dot[r][0], lane, bk, bi);
+            if (pos < a.nn) price_elem<G>(a.cost, a.rvec, pos, a.nonbasic[pos], dot[r][0], lane, bk, bi, b2);
         }
     }
-    publish_partials(bk, bi, sk, si, a.pk_price, a.pi_price);
+    publish<G>(bk, bi, b2, sk, si, ss, a.pk_price, a.pi_price);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -217,34 +263,38 @@ __global__ __launch_bounds__(kBlock) void k_price_ck(LPArgs a, int ck2) {
 //     fused first-index argmin of move (:268).   traffic: m*m*8 bytes read (B^-1 once)
 //     entering variable: pick_entering
 // ------------------------------------------------------------------------------------------------
+template <bool G>
 __global__ __launch_bounds__(kBlock) void k_ftran(LPArgs a, int nparts_price, int forced_pos, int forced_var) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
     int var;
-    if (!pick_entering(a.st, a.pk_price, a.pi_price, nparts_price, a.rvec, a.nonbasic, a.tol, forced_pos, forced_var, sk, si, var)) return;
+    if (!pick_entering<G>(a.st, a.pk_price, a.pi_price, nparts_price, a.rvec, a.nonbasic, a.tol, a.guard, forced_pos, forced_var, sk, si, ss, var)) return;
     const int ld2 = a.ld >> 1;
     stage_vec(svec, a.At + (size_t)var * a.ld, ld2);
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
-    unsigned long long bk = ~0ull;
+    unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
-    for (int i = wave; i < a.m; i += nwaves) ratio_elem(a.xb, a.dvec, a.move, i, wave_dot_row(a.binv_cur + (size_t)i * a.ld, svec, ld2, lane), lane, bk, bi);
-    publish_partials(bk, bi, sk, si, a.pk_ratio, a.pi_ratio);
+    for (int i = wave; i < a.m; i += nwaves) ratio_elem<G>(a.xb, a.dvec, a.move, i, wave_dot_row(a.binv_cur + (size_t)i * a.ld, svec, ld2, lane), lane, bk, bi, b2);
+    publish<G>(bk, bi, b2, sk, si, ss, a.pk_ratio, a.pi_ratio);
 }
 
+template <bool G>
 __global__ __launch_bounds__(kBlock) void k_ftran_ck(LPArgs a, int nparts_price, int forced_pos, int forced_var, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
     int var;
-    if (!pick_entering(a.st, a.pk_price, a.pi_price, nparts_price, a.rvec, a.nonbasic, a.tol, forced_pos, forced_var, sk, si, var)) return;
+    if (!pick_entering<G>(a.st, a.pk_price, a.pi_price, nparts_price, a.rvec, a.nonbasic, a.tol, a.guard, forced_pos, forced_var, sk, si, ss, var)) return;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
     const int kmax = (a.m + nwaves - 1) / nwaves;
-    unsigned long long bk = ~0ull;
+    unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
     for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
         double dot[kCkRows][1];
@@ -252,10 +302,10 @@ __global__ __launch_bounds__(kBlock) void k_ftran_ck(LPArgs a, int nparts_price,
 #pragma unroll
         for (int r = 0; r < kCkRows; r++) {
             const int i = wave + (k0 + r) * nwaves;
-            if (i < a.m) ratio_elem(a.xb, a.dvec, a.move, i, dot[r][0], lane, bk, bi);
+            if (i < a.m) ratio_elem<G>(a.xb, a.dvec, a.move, i, dot[r][0], lane, bk, bi, b2);
         }
     }
-    publish_partials(bk, bi, sk, si, a.pk_ratio, a.pi_ratio);
+    publish<G>(bk, bi, b2, sk, si, ss, a.pk_ratio, a.pi_ratio);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -263,12 +313,14 @@ __global__ __launch_bounds__(kBlock) void k_ftran_ck(LPArgs a, int nparts_price,
 //     the three fresh LU factorizations).   traffic: m*m*8 read + m*m*8 written
 //     leaving row: pick_leaving.  no_swap: setup pivot (indices managed by the host).
 // ------------------------------------------------------------------------------------------------
+template <bool G>
 __global__ __launch_bounds__(kBlock) void k_update(LPArgs a, int nparts_ratio, int forced_p, int no_swap, int bland) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
     int p;
-    if (!pick_leaving(a.st, a.pk_ratio, a.pi_ratio, nparts_ratio, a.move, forced_p, sk, si, p)) return;
+    if (!pick_leaving<G>(a.st, a.pk_ratio, a.pi_ratio, nparts_ratio, a.move, a.dvec, a.guard, forced_p, sk, si, ss, p)) return;
     const double dpv = a.dvec[p];
     const int ld2 = a.ld >> 1;
     stage_vec(svec, a.binv_cur + (size_t)p * a.ld, ld2);  // old row p
@@ -282,12 +334,14 @@ __global__ __launch_bounds__(kBlock) void k_update(LPArgs a, int nparts_ratio, i
 }
 
 // elementwise: its chunks are only bounds
+template <bool G>
 __global__ __launch_bounds__(kBlock) void k_update_ck(LPArgs a, int nparts_ratio, int forced_p, int no_swap, int bland, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
     int p;
-    if (!pick_leaving(a.st, a.pk_ratio, a.pi_ratio, nparts_ratio, a.move, forced_p, sk, si, p)) return;
+    if (!pick_leaving<G>(a.st, a.pk_ratio, a.pi_ratio, nparts_ratio, a.move, a.dvec, a.guard, forced_p, sk, si, ss, p)) return;
     const double dpv = a.dvec[p];
     const int ld2 = a.ld >> 1;
     const double *rowp_g = a.binv_cur + (size_t)p * a.ld;   // old row p (binv_cur is only read here)
@@ -564,32 +618,50 @@ __global__ __launch_bounds__(kBlock) void k_lu_step(LUArgs a, int k, int nparts)
 // host-callable launch wrappers (the engine is plain C++; only this file is device code)
 // ------------------------------------------------------------------------------------------------
 
+// (LPArgs::guard > 0: the guard instances)
+template <bool G>
+static void launch_price_t(const LPArgs &a, int g, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    if (a.row_chunk2 > 0) hipExtLaunchKernelGGL(k_price_ck<G>, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, a.row_chunk2);
+    else hipExtLaunchKernelGGL(k_price<G>, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a);
+}
 int launch_price(const LPArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const int g = grid_for_rows(a.nn);
-    if (a.row_chunk2 > 0) hipExtLaunchKernelGGL(k_price_ck, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, a.row_chunk2);
-    else hipExtLaunchKernelGGL(k_price, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a);
+    if (a.guard > 0) launch_price_t<true>(a, g, s, e0, e1);
+    else launch_price_t<false>(a, g, s, e0, e1);
     return g;
+}
+template <bool G>
+static void launch_ftran_t(const LPArgs &a, int g, int nparts_price, int forced_pos, int forced_var, hipStream_t s, hipEvent_t e0,
+                           hipEvent_t e1) {
+    if (a.row_chunk2 > 0)
+        hipExtLaunchKernelGGL(k_ftran_ck<G>, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, nparts_price,
+                              forced_pos, forced_var, a.row_chunk2);
+    else
+        hipExtLaunchKernelGGL(k_ftran<G>, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a, nparts_price,
+                              forced_pos, forced_var);
 }
 int launch_ftran(const LPArgs &a, int nparts_price, int forced_pos, int forced_var, hipStream_t s, hipEvent_t e0,
                  hipEvent_t e1) {
     const int g = grid_for_rows(a.m);
-    if (a.row_chunk2 > 0)
-        hipExtLaunchKernelGGL(k_ftran_ck, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, nparts_price,
-                              forced_pos, forced_var, a.row_chunk2);
-    else
-        hipExtLaunchKernelGGL(k_ftran, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a, nparts_price,
-                              forced_pos, forced_var);
+    if (a.guard > 0) launch_ftran_t<true>(a, g, nparts_price, forced_pos, forced_var, s, e0, e1);
+    else launch_ftran_t<false>(a, g, nparts_price, forced_pos, forced_var, s, e0, e1);
     return g;
+}
+template <bool G>
+static void launch_update_t(const LPArgs &a, int g, int nparts_ratio, int forced_p, int no_swap, int bland, hipStream_t s, hipEvent_t e0,
+                            hipEvent_t e1) {
+    if (a.row_chunk2 > 0)
+        hipExtLaunchKernelGGL(k_update_ck<G>, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, nparts_ratio,
+                              forced_p, no_swap, bland, a.row_chunk2);
+    else
+        hipExtLaunchKernelGGL(k_update<G>, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a, nparts_ratio,
+                              forced_p, no_swap, bland);
 }
 void launch_update(const LPArgs &a, int nparts_ratio, int forced_p, int no_swap, int bland, hipStream_t s, hipEvent_t e0,
                    hipEvent_t e1) {
     const int g = grid_for_rows(a.m);
-    if (a.row_chunk2 > 0)
-        hipExtLaunchKernelGGL(k_update_ck, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, nparts_ratio,
-                              forced_p, no_swap, bland, a.row_chunk2);
-    else
-        hipExtLaunchKernelGGL(k_update, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a, nparts_ratio,
-                              forced_p, no_swap, bland);
+    if (a.guard > 0) launch_update_t<true>(a, g, nparts_ratio, forced_p, no_swap, bland, s, e0, e1);
+    else launch_update_t<false>(a, g, nparts_ratio, forced_p, no_swap, bland, s, e0, e1);
 }
 void launch_transpose_in(const double *A, int64_t lda, int m, int n, double *At, int ld, hipStream_t s) {
     dim3 grid((n + 31) / 32, (m + 31) / 32), block(32, 8);

@@ -93,7 +93,9 @@ typedef struct gomilp_pivot {
  * initial_basic (nullable, exactly m entries; GoMILP passes nil): a supplied feasible basis skips Phase I
  * (simplex.go:147-160); an index out of range, a singular or an infeasible set return GOMILP_ERR_PANIC (the
  * reference panics); like any non-slack starting basis it needs the host copy of A, kept for m * n <= 2^25
- * (GOMILP_ERR_UNSUPPORTED above): the column search runs on the device from 224 rows on.
+ * (GOMILP_ERR_UNSUPPORTED above): the column search runs on the device from 96 rows on.  Such a start runs on the tableau
+ * pipelines while the tableau row fits the 64 KB LDS window (n - m <= 8191), on the three-kernel revised simplex with the exact-step
+ * guard beyond (up to 8192 rows).
  * ---------------------------------------------------------------------------------------- */
 int gomilp_lp_simplex(const double *c, const double *A, int64_t lda, const double *b, int64_t m, int64_t n,
                       double tol, const int64_t *initial_basic, double *opt_f, double *opt_x, int32_t *has_x,
@@ -125,10 +127,11 @@ int gomilp_ctx_device(const gomilp_ctx *ctx);
  * "exact_degenerate" (0 never, 1 default: bases of up to 256 rows, non-slack starts and badly scaled inputs, 2 always — degenerate,
  * tied and tiny pivots are decided on fresh gonum-order solves; 3 strict: EVERY pivot and the stop test are the
  * reference's iteration on fresh gonum-order solves with its condition guard, simplex.go:233-293 — milliseconds per pivot, the mode that
- * follows the reference wherever the rounding noise of its solves leads).  The exact steps exist on the BLOCKED tableau pipeline only: a
- * wide slack-basis LP (n - m >= 2m) whose mode asks for them takes the blocked tableau instead of the revised pipelines when that
- * pipeline takes the shape; with "tableau" = 0 or "blocked" = 0 modes 1 / 2 run WITHOUT them (A/B knobs), and mode 3 returns
- * GOMILP_ERR_UNSUPPORTED from the solve whenever the blocked tableau does not run.  "cond_guard" (1 default: gonum's
+ * follows the reference wherever the rounding noise of its solves leads).  The exact steps exist on the BLOCKED tableau pipeline and,
+ * for non-slack starts (equality rows, initial_basic) that the tableau does not take (n - m > 8191, or "tableau" = 0), on the
+ * three-kernel revised simplex.  A wide slack-basis LP (n - m >= 2m) whose mode asks for them takes the blocked tableau instead of the
+ * revised pipelines when that pipeline takes the shape; with "tableau" = 0 or "blocked" = 0 a slack-basis start runs modes 1 / 2
+ * WITHOUT them (A/B knobs), and mode 3 returns GOMILP_ERR_UNSUPPORTED from the solve whenever neither of the two runs.  "cond_guard" (1 default: gonum's
  * mat.Condition guard, from a pivot-by-pivot replay up to 64 rows and from the tableau's exact condition numbers beyond — at every exact
  * step (Phase I too), on the final basis, and in front of any pivot whose element is of rounding-noise size).
  * "row_chunk" (doubles; 0 default): the revised-simplex kernels stage one m-long vector per workgroup in LDS — in one pass up to
@@ -136,7 +139,9 @@ int gomilp_ctx_device(const gomilp_ctx *ctx);
  * that many doubles per chunk at every size (tests).
  * Returns GOMILP_OK or GOMILP_ERR_BAD_SHAPE. */
 
-/* Row limit.  Upload accepts m < 2^20 rows; the device memory decides what solves.  Up to 8192 rows every path below applies.
+/* Row limit.  Upload accepts m < 2^20 rows; the device memory decides what solves.  Up to 8192 rows every path below applies,
+ * non-slack starts of any width n included (the three-kernel revised simplex with exact steps where the tableau row does not fit,
+ * while m * n <= 2^25).
  * Beyond 8192 rows ("Beyond 8192 rows") a single context solves SLACK-BASIS starts — every row has its own
  * unit column, GoMILP's inequality form [G | I] — with Phase I where b has negative entries, through gomilp_lp_simplex,
  * gomilp_lp_upload + gomilp_lp_solve_resident, and gomilp_lp_upload_child on such a root; with the statuses, trace, basis and point
