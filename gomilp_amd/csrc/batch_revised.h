@@ -1,0 +1,78 @@
+// Device-batched revised simplex (batch_revised.hip, engine_batch_revised.cpp): the three-kernel revised simplex of
+// simplex_kernels.hip with the relaxation as blockIdx.y.  One RevLP per relaxation of a wave, resident in HBM: it plays the role
+// of LPArgs (the pointers), carries the relaxation's stage and its ping-pong parity, and takes the work orders that the control
+// kernels write for the set-up launches of the next superstep.  The host enqueues a fixed list of launches per superstep and looks
+// at one small record per relaxation afterwards.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "device_types.h"
+
+namespace gomilp {
+
+enum : int32_t {
+    RS_RUN = 0,    // set-up launches or a pivot loop are running
+    RS_DONE = 1,   // terminal: `status` holds the outcome (GOMILP_OK / ERR_BLAND / ERR_UNSUPPORTED after Phase II: basis + x_B ready for the final solve)
+    RS_HOST = 2    // terminal: a branch the schedule leaves to a worker's whole solve (the |x_art| band, the zero-level artificial exchange)
+};
+// RevLP::after: what k_rv_check does behind the set-up launches of a superstep
+enum : int32_t {
+    RA_NONE = 0,
+    RA_P1_LOOP = 1,   // the PANIC test of the Phase-I start, then the Phase-I loop
+    RA_P2_LOOP = 2    // the Phase-II loop
+};
+// RevLP::run: which launches of a superstep work on the relaxation
+enum : int32_t { RR_NONE = 0, RR_LOOP = 1, RR_FORCED = 2 };
+
+struct RevLP {
+    // ---- fixed for the wave (written by the host) ----
+    double *At;              // (n + 1) x ld: row j = column j of the child's A (k_child_assemble), row n = the Phase-I artificial
+    const double *c2;        // Phase-II cost [c0, 0, ...] (at least n + 1 entries)
+    double *c1;              // Phase-I cost: e_n (n + 1 entries, written by k_rv_init)
+    double *b;               // ld, zero padded
+    double *binv[2];         // m x ld each: flip counter & 1 is the current one
+    double *xb, *y, *dvec, *move, *rvec, *yscratch;
+    int32_t *basic, *nonbasic, *inb;
+    unsigned long long *pk_price, *pk_ratio;
+    unsigned int *pi_price, *pi_ratio;
+    DevState *st;
+    const double *b0, *rhs;  // root right-hand side (m0), the child's branch right-hand sides (K)
+    const int32_t *rho0;     // m0: row of the 1 in root column n0 - 1 - pos
+    int32_t m0, n0, K, m, n, ld;
+    int64_t max_pivots;      // pool knob max_pivots (0: none)
+    double tol_user;         // Phase-II tolerance of the call
+    // ---- state (device) ----
+    int32_t stage, run;      // RS_*, RR_*
+    int32_t flips;           // rank-1 updates committed so far (no-swap set-up pivots included): written by K3's committing thread,
+    int32_t flips_k2;        // read by K2 and the refresh kernels; K2's copy for the K3 of the same pivot (no kernel reads what its own launch writes)
+    int32_t phase, nn;
+    double tol;
+    const double *cost;
+    // the Bland rule inside the loop (k_rv_bland in front of every pivot): bl = 1: this pivot is a Bland step on candidate position bl_pos
+    // (K1 is skipped, K2 takes the position, K3 the leaving row by replaceBland's rule); bland_failed: no candidate was left (lp.ErrBland)
+    int32_t bl, bl_pos, bland_failed, pad1;
+    // ---- work orders for the set-up launches of the next superstep (written by k_rv_init / k_rv_ctrl, cleared by k_rv_check) ----
+    int32_t f_var, f_pos, f_p, f_noswap, pad2;      // the forced pivot (run == RR_FORCED)
+    int32_t do_lists;        // 1: basic[f_p] = n, nonbasic = ascending ids of n + 1 columns outside the basis; 2: of n columns
+    int32_t do_refresh;      // 1: x_B = B^-1 b and y = B^-T c_B; 2: y only
+    int32_t after;           // RA_*
+    // ---- outcome ----
+    int32_t status, wrapped, phase1_used, pad0;
+    int64_t piv1, piv2, bland;
+};
+
+// what the host reads of every active relaxation after a superstep
+struct RevOut {
+    int32_t stage, status, wrapped, phase1_used;
+    int64_t piv1, piv2, bland;
+};
+
+// launches (batch_revised.hip).  act: list positions -> relaxation; nact entries.  gp / gr: workgroups per relaxation of the pricing
+// kernel and of the row kernels (grid_for_rows of the wave's largest nn / m); lds: bytes of the largest staged vector.
+void launch_rv_init(RevLP *lps, int count, hipStream_t s);
+void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, hipStream_t s);   // forced pivot, lists, refresh, check: 7 launches
+void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, hipStream_t s);               // Bland step?, K1, K2, K3: 4 launches
+void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s);
+
+}  // namespace gomilp

@@ -1,0 +1,477 @@
+// gfx950 (CDNA4, wave64) kernels of the device-batched revised simplex: K1-K3 of simplex_kernels.hip with the relaxation as
+// blockIdx.y, and the small kernels that run a relaxation's stages on the device (slack start, Phase-I set-up, list rebuilds,
+// refreshes, the Bland rule, the verdicts) so that a wave costs a constant number of host round trips per superstep.
+//
+// The pivot rules, the per-element work and the commit are the helpers of simplex_helpers.h, the code the single-relaxation
+// kernels run: every dot product is one wave over one row (wave_dot_row), the argmins are first-index over per-workgroup
+// partials, so a relaxation's values do not depend on the grid it gets or on the relaxations beside it.  Nothing is reduced
+// across relaxations and no kernel waits for another workgroup: kernels communicate across launch boundaries only.
+// Every field of a RevLP that a kernel reads was written by an earlier launch of the stream (RevLP::flips / flips_k2).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "batch_revised.h"
+#include "device_types.h"
+#include "gomilp_lp.h"
+#include "kernels_common.h"
+#include "simplex_helpers.h"
+
+namespace gomilp {
+
+namespace {
+
+__device__ __forceinline__ unsigned int block_min_u32(unsigned int v, unsigned int *sm) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned int)__shfl_xor((int)v, o, 64));
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) sm[w] = v;
+    __syncthreads();
+    v = sm[0];
+#pragma unroll
+    for (int t = 1; t < kWavesPerBlock; t++) v = min(v, sm[t]);
+    __syncthreads();
+    return v;
+}
+
+// row of the 1 in the child's column n - 1 - pos: the K branch slacks first (descending scan, simplex.go:618-635), then the root's
+__device__ __forceinline__ int child_rho(int pos, int K, int m0, const int32_t *rho0) {
+    return pos < K ? m0 + K - 1 - pos : rho0[pos - K];
+}
+
+__device__ __forceinline__ void start_loop_state(DevState *st, int64_t max_pivots) {
+    st->done = 0; st->status = ST_RUNNING; st->pivots = 0; st->q = -1; st->p = -1; st->rq = 0; st->dp = 0; st->mv = 0;
+    st->max_pivots = max_pivots; st->lu_singular = 0;
+}
+
+__device__ __forceinline__ void clear_orders(RevLP *d) {
+    d->do_lists = 0; d->do_refresh = 0; d->after = RA_NONE;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// start of a relaxation from its slack basis (Engine::solve_locked, unit-basis branch): b' = [b0; h], x_B = b'[rho], B^-1 = the
+// permutation, and either the orders of the Phase-II start or the Phase-I set-up (simplex.go:529-546): the artificial column
+// a_{n+1} = b - sum_{i != minidx} e_{rho_i} (one exact "- 1" per row) into row n of At and the forced no-swap pivot that brings it
+// into position minidx.  (The buffers arrive zeroed.)  One workgroup per relaxation.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_rv_init(RevLP *lps) {
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    RevLP *d = lps + blockIdx.x;
+    const int m = d->m, n = d->n, ld = d->ld, m0 = d->m0, K = d->K;
+    const int32_t *rho0 = d->rho0;
+    double *b = d->b, *xb = d->xb, *binv0 = d->binv[0], *c1 = d->c1;
+    int32_t *basic = d->basic;
+    for (int i = threadIdx.x; i < ld; i += kBlock) b[i] = i < m0 ? d->b0[i] : (i < m ? d->rhs[i - m0] : 0.0);
+    for (int j = threadIdx.x; j <= n; j += kBlock) c1[j] = j == n ? 1.0 : 0.0;
+    __syncthreads();
+    int infeasible = 0;
+    unsigned long long bk = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int pos = threadIdx.x; pos < m; pos += kBlock) {
+        const int r = child_rho(pos, K, m0, rho0);
+        const double v = b[r];
+        xb[pos] = v;
+        basic[pos] = n - 1 - pos;
+        binv0[(size_t)pos * ld + r] = 1.0;
+        if (v < -1e-13) infeasible = 1;
+        amin_take(bk, bi, ordkey(v), (unsigned int)pos);
+    }
+    infeasible = __syncthreads_or(infeasible);
+    if (!infeasible) {
+        if (threadIdx.x == 0) {
+            d->run = RR_NONE; d->do_lists = 2; d->do_refresh = 2; d->after = RA_P2_LOOP;
+        }
+        return;
+    }
+    block_argmin(bk, bi, sk, si);
+    const int minidx = (int)bi;   // floats.MinIdx(xb), simplex.go:531
+    const int rmin = child_rho(minidx, K, m0, rho0);
+    double *art = d->At + (size_t)n * ld;
+    int nonzero = 0;
+    for (int r = threadIdx.x; r < ld; r += kBlock) {
+        double v = 0.0;
+        if (r < m) v = (r == rmin) ? b[r] : -1 * 1.0 + b[r];
+        art[r] = v;
+        if (v != 0) nonzero = 1;
+    }
+    nonzero = __syncthreads_or(nonzero);
+    if (threadIdx.x == 0) {
+        d->phase1_used = 1;
+        if (!nonzero) {   // verifyInputs of the recursive call: an empty column
+            d->status = GOMILP_ERR_PHASE1_WRAPPED; d->wrapped = GOMILP_ERR_ZERO_COLUMN; d->stage = RS_DONE; d->run = RR_NONE;
+        } else {
+            d->f_var = n; d->f_pos = -1; d->f_p = minidx; d->f_noswap = 1;
+            d->run = RR_FORCED; d->do_lists = 1; d->do_refresh = 1; d->after = RA_P1_LOOP;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// K1-K3, relaxation = blockIdx.y.  MODE = RR_LOOP: a pivot of the loop; RR_FORCED: the forced pivot of the Phase-I set-up.
+// The fields of the RevLP go into locals once (simplex_helpers.h: why the helpers take pointers).
+//
+// The Bland rule (Engine::host_bland; replaceBland, simplex.go:347-383) runs inside the loop: k_rv_bland, one small workgroup per
+// relaxation in front of every pivot, looks at a loop that stopped with ST_NEED_BLAND — r rounded at rRoundTol, the first position
+// with r <= -blandNegTol is the candidate — and turns the pivot behind it into the Bland step: K1 is skipped (the reduced costs of the
+// stopped pivot stand), K2 runs the FTRAN of the candidate's column, K3 takes the leaving row by replaceBland's rule and commits with
+// bland = 1.  The candidate's own minimum row always passes the rule's test (bland_leaving), so the first candidate is the last: no
+// cursor over candidates is needed, and a degenerate step costs one pivot's launches and no host round trip.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_rv_bland(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    __shared__ unsigned int sm[kWavesPerBlock];
+    RevLP *d = lps + act[blockIdx.x];
+    if (d->run != RR_LOOP) return;
+    DevState *st = d->st;
+    const bool need = st->done != 0 && st->status == ST_NEED_BLAND && d->bland_failed == 0;   // (uniform: written below behind the barriers)
+    if (!need) {
+        if (threadIdx.x == 0) d->bl = 0;
+        return;
+    }
+    const int nn = d->nn;
+    const double *rvec = d->rvec;
+    unsigned int first = 0xFFFFFFFFu;
+    for (int j = threadIdx.x; j < nn; j += kBlock) {
+        double r = rvec[j];
+        if (fabs(r) < 1e-13) r = 0;   // rRoundTol, :252-256
+        if (r > -1e-14) continue;     // blandNegTol, :352
+        first = (unsigned int)j;
+        break;
+    }
+    first = block_min_u32(first, sm);
+    if (threadIdx.x == 0) {
+        if (first == 0xFFFFFFFFu) { d->bland_failed = 1; d->bl = 0; }   // lp.ErrBland: k_rv_ctrl ends the loop
+        else { st->done = 0; st->status = ST_RUNNING; d->bl = 1; d->bl_pos = (int)first; }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_rv_price(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[1];
+    const RevLP *d = lps + act[blockIdx.y];
+    if (d->run != RR_LOOP || d->bl) return;
+    DevState *st = d->st;
+    if (!price_gate(st)) return;
+    const int ld = d->ld, nn = d->nn;
+    const double *At = d->At, *cost = d->cost, *y = d->y;
+    double *rvec = d->rvec;
+    const int32_t *nonbasic = d->nonbasic;
+    unsigned long long *pk = d->pk_price;
+    unsigned int *pi = d->pi_price;
+    const int ld2 = ld >> 1;
+    stage_vec(svec, y, ld2);
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    unsigned long long bk = ~0ull, b2 = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int pos = wave; pos < nn; pos += nwaves) {
+        const int j = nonbasic[pos];
+        price_elem<false>(cost, rvec, pos, j, wave_dot_row(At + (size_t)j * ld, svec, ld2, lane), lane, bk, bi, b2);
+    }
+    publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_price) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[1];
+    RevLP *d = lps + act[blockIdx.y];
+    if (d->run != MODE) return;
+    DevState *st = d->st;
+    const int m = d->m, ld = d->ld, flips = d->flips;
+    const int forced_pos = MODE == RR_FORCED ? d->f_pos : (d->bl ? d->bl_pos : -1), forced_var = MODE == RR_FORCED ? d->f_var : -1;
+    const double tol = d->tol;
+    const double *At = d->At, *binv_cur = d->binv[flips & 1], *xb = d->xb;
+    double *rvec = d->rvec, *dvec = d->dvec, *move = d->move;
+    const int32_t *nonbasic = d->nonbasic;
+    const unsigned long long *pkp = d->pk_price;
+    const unsigned int *pip = d->pi_price;
+    unsigned long long *pk = d->pk_ratio;
+    unsigned int *pi = d->pi_ratio;
+    int var;
+    if (!pick_entering<false>(st, pkp, pip, nparts_price, rvec, nonbasic, tol, 0.0, forced_pos, forced_var, sk, si, ss, var)) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) d->flips_k2 = flips;   // K3 of this pivot reads the parity K2 worked on
+    const int ld2 = ld >> 1;
+    stage_vec(svec, At + (size_t)var * ld, ld2);
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    unsigned long long bk = ~0ull, b2 = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int i = wave; i < m; i += nwaves) ratio_elem<false>(xb, dvec, move, i, wave_dot_row(binv_cur + (size_t)i * ld, svec, ld2, lane), lane, bk, bi, b2);
+    publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
+}
+
+// replaceBland's leaving row for the candidate whose FTRAN just ran (Engine::host_bland; simplex.go:357-380): the first-index
+// minimum of move; all-infinite: unbounded (computeMove, :328); |move| <= blandZeroTol: the first row with move <= 1e-12 (the
+// minimum's own row satisfies it, so the candidate is always taken).  false: the loop has stopped or stops here.
+__device__ __forceinline__ bool bland_leaving(DevState *st, const unsigned long long *pk, const unsigned int *pi, int nparts_ratio,
+                                              const double *move, int m, unsigned long long *sk, unsigned int *si, int &p) {
+    if (st->done) return false;
+    p = (int)reduce_partials(pk, pi, nparts_ratio, sk, si, nullptr);
+    const double mv = move[p];
+    if (mv == __builtin_inf()) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { st->done = 1; st->status = ST_UNBOUNDED; st->p = p; st->mv = mv; }
+        return false;
+    }
+    if (!(fabs(mv) > 1e-12)) {
+        unsigned int first = 0xFFFFFFFFu;
+        for (int i = threadIdx.x; i < m; i += kBlock)
+            if (!(move[i] > 1e-12)) { first = (unsigned int)i; break; }
+        p = (int)block_min_u32(first, si);
+    }
+    return true;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_rv_update(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_ratio) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[1];
+    RevLP *d = lps + act[blockIdx.y];
+    if (d->run != MODE) return;
+    DevState *st = d->st;
+    const int m = d->m, ld = d->ld, flips = d->flips_k2, phase = d->phase;
+    const int forced_p = MODE == RR_FORCED ? d->f_p : -1, no_swap = MODE == RR_FORCED ? d->f_noswap : 0, bland = MODE == RR_FORCED ? 0 : d->bl;
+    const double *binv_cur = d->binv[flips & 1];
+    double *binv_next = d->binv[(flips + 1) & 1];
+    double *xb = d->xb, *y = d->y, *dvec = d->dvec, *move = d->move;
+    int32_t *basic = d->basic, *nonbasic = d->nonbasic;
+    const unsigned long long *pk = d->pk_ratio;
+    const unsigned int *pi = d->pi_ratio;
+    int p;
+    if (bland) {
+        if (!bland_leaving(st, pk, pi, nparts_ratio, move, m, sk, si, p)) return;
+    } else if (!pick_leaving<false>(st, pk, pi, nparts_ratio, move, dvec, 0.0, forced_p, sk, si, ss, p)) {
+        return;
+    }
+    const double dpv = dvec[p];
+    const int ld2 = ld >> 1;
+    stage_vec(svec, binv_cur + (size_t)p * ld, ld2);  // old row p
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    for (int i = wave; i < m; i += nwaves) update_row(binv_cur, binv_next, ld, dvec, i, p, dpv, svec, 0, ld2, lane);
+    if (blockIdx.x == 0) {
+        commit_pivot(st, xb, y, dvec, move, basic, nonbasic, nullptr, 0, phase, m, ld, p, dpv, reinterpret_cast<const double *>(svec), no_swap, bland);
+        if (threadIdx.x == 0) {
+            d->flips = flips + 1;
+            if (bland) d->bland += 1;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// set-up launches behind the forced pivot: index lists, refreshes, the check that starts the loop
+// ------------------------------------------------------------------------------------------------
+
+// do_lists: the artificial into the basis list (1), and the nonbasic list as the ascending ids outside the basis (simplex.go:174-184)
+__global__ __launch_bounds__(kBlock) void k_rv_lists(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    __shared__ int wtot[kWavesPerBlock];
+    RevLP *d = lps + act[blockIdx.x];
+    const int mode = d->do_lists;
+    if (mode == 0 || d->stage != RS_RUN) return;
+    const int m = d->m, n = d->n, ncols = mode == 1 ? n + 1 : n;
+    int32_t *basic = d->basic, *nonbasic = d->nonbasic, *inb = d->inb;
+    if (mode == 1 && threadIdx.x == 0) basic[d->f_p] = n;
+    for (int j = threadIdx.x; j <= n; j += kBlock) inb[j] = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < m; i += kBlock) inb[basic[i]] = 1;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int off = 0;
+    for (int base = 0; base < ncols; base += kBlock) {
+        const int j = base + threadIdx.x;
+        const bool out = j < ncols && !inb[j];
+        const unsigned long long bal = __ballot(out);
+        if (lane == 0) wtot[w] = __popcll(bal);
+        __syncthreads();
+        int woff = 0, tot = 0;
+#pragma unroll
+        for (int t = 0; t < kWavesPerBlock; t++) { if (t < w) woff += wtot[t]; tot += wtot[t]; }
+        if (out) nonbasic[off + woff + __popcll(bal & ((1ull << lane) - 1ull))] = j;
+        off += tot;
+        __syncthreads();
+    }
+}
+
+// x_B = B^-1 b (k_matvec_rows)
+__global__ __launch_bounds__(kBlock) void k_rv_matvec(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    const RevLP *d = lps + act[blockIdx.y];
+    if (d->do_refresh != 1 || d->stage != RS_RUN) return;
+    const int m = d->m, ld = d->ld;
+    const double *M = d->binv[d->flips & 1], *vec = d->b;
+    double *out = d->xb;
+    const int ld2 = ld >> 1;
+    stage_vec(svec, vec, ld2);
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    for (int i = wave; i < m; i += nwaves) {
+        const double v = wave_dot_row(M + (size_t)i * ld, svec, ld2, lane);
+        if (lane == 0) out[i] = v;
+    }
+}
+
+// y = B^-T c_B in the arithmetic of k_y_partial / k_y_reduce (the chunking of launch_y_from_binv for this relaxation's m);
+// blockIdx.y = chunk, blockIdx.z = list position
+__global__ __launch_bounds__(kBlock) void k_rv_y_partial(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    const RevLP *d = lps + act[blockIdx.z];
+    if (d->do_refresh == 0 || d->stage != RS_RUN) return;
+    const int m = d->m, ld = d->ld;
+    int nchunks = (m + 63) / 64;
+    nchunks = nchunks > 64 ? 64 : nchunks;
+    const int rows_per_chunk = (m + nchunks - 1) / nchunks;
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    const int chunk = blockIdx.y;
+    if (chunk >= nchunks || j >= ld) return;
+    const double *binv = d->binv[d->flips & 1], *cost = d->after == RA_P1_LOOP ? d->c1 : d->c2;
+    const int32_t *basic = d->basic;
+    const int i0 = chunk * rows_per_chunk, i1 = min(m, i0 + rows_per_chunk);
+    double acc = 0;
+    for (int i = i0; i < i1; i++) {
+        const double cb = cost[basic[i]];
+        if (cb != 0) acc += cb * binv[(size_t)i * ld + j];
+    }
+    d->yscratch[(size_t)chunk * ld + j] = acc;
+}
+__global__ __launch_bounds__(kBlock) void k_rv_y_reduce(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    const RevLP *d = lps + act[blockIdx.y];
+    if (d->do_refresh == 0 || d->stage != RS_RUN) return;
+    const int m = d->m, ld = d->ld;
+    int nchunks = (m + 63) / 64;
+    nchunks = nchunks > 64 ? 64 : nchunks;
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= ld) return;
+    const double *scratch = d->yscratch;
+    double acc = 0;
+    for (int c = 0; c < nchunks; c++) acc += scratch[(size_t)c * ld + j];
+    d->y[j] = acc;
+}
+
+// behind the set-up launches: the PANIC test of the Phase-I start (simplex.go:155-158 in the recursive call), the loop's state
+__global__ __launch_bounds__(kBlock) void k_rv_check(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    RevLP *d = lps + act[blockIdx.x];
+    const int after = d->after;
+    if (after == RA_NONE || d->stage != RS_RUN) return;
+    DevState *st = d->st;
+    const int m = d->m, n = d->n;
+    if (after == RA_P1_LOOP) {
+        const double *xb = d->xb;
+        int bad = 0;
+        for (int i = threadIdx.x; i < m; i += kBlock) if (xb[i] < -1e-13) bad = 1;
+        bad = __syncthreads_or(bad);
+        if (bad) {
+            if (threadIdx.x == 0) { d->status = GOMILP_ERR_PANIC; d->stage = RS_DONE; d->run = RR_NONE; clear_orders(d); }
+            return;
+        }
+    }
+    if (threadIdx.x == 0) {
+        if (after == RA_P1_LOOP) {
+            start_loop_state(st, d->max_pivots);
+            d->phase = 1; d->nn = n + 1 - m; d->tol = 1e-10; d->cost = d->c1;
+        } else {
+            start_loop_state(st, d->max_pivots);
+            d->phase = 2; d->nn = n - m; d->tol = d->tol_user; d->cost = d->c2;
+        }
+        d->run = RR_LOOP;
+        clear_orders(d);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// control step behind a chunk of pivots: what a stopped loop means (Engine::run_loop's switch, the Phase-I verdict of
+// Engine::solve_locked), the orders of the next superstep, the record the host reads.  One workgroup per active relaxation.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_rv_ctrl(RevLP *__restrict__ lps, const int *__restrict__ act, RevOut *__restrict__ out) {
+    __shared__ unsigned int sm[kWavesPerBlock];
+    const int id = act[blockIdx.x];
+    RevLP *d = lps + id;
+    DevState *st = d->st;
+    // (a loop that stopped for a Bland step goes on: k_rv_bland takes it in front of the next pivot)
+    const bool stopped = d->stage == RS_RUN && d->run == RR_LOOP && st->done != 0 &&
+                         !(st->status == ST_NEED_BLAND && d->bland_failed == 0);   // (uniform: nothing below writes these before the last barrier)
+    if (stopped) {
+        const int status = st->status, phase = d->phase, m = d->m, n = d->n;
+        if (status == ST_NEED_BLAND) {   // replaceBland ran out of candidates: lp.ErrBland
+            if (threadIdx.x == 0) {
+                if (phase == 1) { d->piv1 = st->pivots; d->status = GOMILP_ERR_PHASE1_WRAPPED; d->wrapped = GOMILP_ERR_BLAND; }
+                else { d->piv2 = st->pivots; d->status = GOMILP_ERR_BLAND; }
+                d->stage = RS_DONE; d->run = RR_NONE;
+            }
+        } else {
+            const int rc = status == ST_OPTIMAL ? GOMILP_OK : status == ST_UNBOUNDED ? GOMILP_ERR_UNBOUNDED
+                         : status == ST_MAX_PIVOTS ? GOMILP_ERR_UNSUPPORTED : GOMILP_ERR_DEVICE;
+            if (phase == 2) {
+                if (threadIdx.x == 0) { d->piv2 = st->pivots; d->status = rc; d->stage = RS_DONE; d->run = RR_NONE; }
+            } else if (rc != GOMILP_OK) {
+                if (threadIdx.x == 0) {
+                    d->piv1 = st->pivots; d->stage = RS_DONE; d->run = RR_NONE;
+                    if (rc == GOMILP_ERR_DEVICE) d->status = rc;
+                    else { d->status = GOMILP_ERR_PHASE1_WRAPPED; d->wrapped = rc; }   // simplex.go:557-559
+                }
+            } else {
+                // Phase I ended at its optimum: where is the artificial, and at what level (simplex.go:561-565)
+                const int32_t *basic = d->basic;
+                unsigned int added = 0xFFFFFFFFu;
+                for (int i = threadIdx.x; i < m; i += kBlock) if (basic[i] == n) added = (unsigned int)i;
+                added = block_min_u32(added, sm);
+                if (threadIdx.x == 0) {
+                    d->piv1 = st->pivots;
+                    const double xart = added != 0xFFFFFFFFu ? d->xb[added] : 0.0;
+                    if (added != 0xFFFFFFFFu && fabs(xart) > 1e-13 && fabs(xart) < 1e-11) {
+                        d->stage = RS_HOST; d->run = RR_NONE;   // too close to phaseIZeroTol: the verdict needs a fresh gonum-order solve
+                    } else if (fabs(xart) > 1e-12) {
+                        d->status = GOMILP_ERR_INFEASIBLE; d->stage = RS_DONE; d->run = RR_NONE;
+                    } else if (added != 0xFFFFFFFFu) {
+                        d->stage = RS_HOST; d->run = RR_NONE;   // the artificial stayed basic at level zero: the exchange of simplex.go:581-606
+                    } else {
+                        d->run = RR_NONE; d->do_lists = 2; d->do_refresh = 1; d->after = RA_P2_LOOP;
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        RevOut o;
+        o.stage = d->stage; o.status = d->status; o.wrapped = d->wrapped; o.phase1_used = d->phase1_used;
+        o.piv1 = d->piv1; o.piv2 = d->piv2; o.bland = d->bland;
+        out[id] = o;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host-callable launch wrappers
+// ------------------------------------------------------------------------------------------------
+void launch_rv_init(RevLP *lps, int count, hipStream_t s) {
+    hipLaunchKernelGGL(k_rv_init, dim3(count), dim3(kBlock), 0, s, lps);
+}
+void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(k_rv_ftran<RR_FORCED>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, 0);
+    hipLaunchKernelGGL(k_rv_update<RR_FORCED>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
+    hipLaunchKernelGGL(k_rv_lists, dim3(nact), dim3(kBlock), 0, s, lps, act);
+    hipLaunchKernelGGL(k_rv_matvec, dim3(gr, nact), dim3(kBlock), lds, s, lps, act);
+    hipLaunchKernelGGL(k_rv_y_partial, dim3((ld_max + kBlock - 1) / kBlock, 64, nact), dim3(kBlock), 0, s, lps, act);
+    hipLaunchKernelGGL(k_rv_y_reduce, dim3((ld_max + kBlock - 1) / kBlock, nact), dim3(kBlock), 0, s, lps, act);
+    hipLaunchKernelGGL(k_rv_check, dim3(nact), dim3(kBlock), 0, s, lps, act);
+}
+void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(k_rv_bland, dim3(nact), dim3(kBlock), 0, s, lps, act);
+    hipLaunchKernelGGL(k_rv_price, dim3(gp, nact), dim3(kBlock), lds, s, lps, act);
+    hipLaunchKernelGGL(k_rv_ftran<RR_LOOP>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp);
+    hipLaunchKernelGGL(k_rv_update<RR_LOOP>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
+}
+void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s) {
+    hipLaunchKernelGGL(k_rv_ctrl, dim3(nact), dim3(kBlock), 0, s, lps, act, out);
+}
+
+}  // namespace gomilp

@@ -19,9 +19,11 @@
 
 #include "engine.hpp"
 #include "engine_batch.hpp"
+#include "engine_batch_revised.hpp"
 
 using gomilp::BatchEngine;
 using gomilp::Engine;
+using gomilp::RevBatchEngine;
 
 struct gomilp_ctx {
     std::unique_ptr<Engine> eng;
@@ -50,6 +52,10 @@ struct gomilp_pool {
                                 // time, each with its pivot workgroups on an XCD of its own) instead of the batched launch pairs.  Off:
                                 // measured 342 k pivots/s for 4 metric LPs against 391 k batched — four updates streaming at once
                                 // raise the latency of every chain's agent-scope reads and polls
+    int batch_revised = 1;      // knob: wide waves (n - m >= 2m) that the workers would run on the unguarded revised pipelines take the
+                                // device-batched revised simplex (engine_batch_revised.hpp); 0: every such wave on the workers
+    int64_t refresh = 0, max_pivots = 0;   // the workers' knobs of these names, as the batched revised simplex needs them
+    std::unique_ptr<RevBatchEngine> rev;   // created on first use
     gomilp::WarmStore warm;     // final states kept for warm starts (gomilp_frontier_solve_warm), shared by both schedules
     Engine::RootView view;      // of eng[0]'s root (all workers hold the same data)
     // further roots (gomilp_pool_add_root): resident in worker 0's engine only, read in place by the others
@@ -214,6 +220,7 @@ int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value) {
     if (!pool || !key) return GOMILP_ERR_BAD_SHAPE;
     std::lock_guard<std::mutex> g(pool->call_mu);
     if (std::string(key) == "batched") { pool->batched = value ? 1 : 0; return GOMILP_OK; }
+    if (std::string(key) == "batch_revised") { pool->batch_revised = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "split_large") { pool->split_large = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "split_phase") { pool->split_phase = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "batch_virt") {   // wide waves on virtual tableaus for their first block (default 1)
@@ -262,6 +269,8 @@ int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value) {
     }
     int rc = GOMILP_OK;
     for (auto &e : pool->eng) { const int r = e->set(key, value); if (r != GOMILP_OK) rc = r; }
+    if (rc == GOMILP_OK && std::string(key) == "refresh") pool->refresh = value;
+    if (rc == GOMILP_OK && std::string(key) == "max_pivots") pool->max_pivots = value < 0 ? 0 : value;
     return rc;
 }
 
@@ -272,6 +281,7 @@ int gomilp_pool_set_root(gomilp_pool *pool, const double *c0, const double *A0, 
     for (auto id : pool->extra_root) pool->eng[0]->free_problem(id);
     pool->extra_root.clear(); pool->extra_view.clear();
     pool->warm.clear();
+    if (pool->rev) pool->rev->release();
     for (size_t w = 0; w < pool->eng.size(); w++) {
         if (pool->root[w] >= 0) pool->eng[w]->free_problem(pool->root[w]);
         int64_t id = pool->eng[w]->upload(c0, A0, lda, b0, m0, n0);
@@ -404,7 +414,46 @@ static int frontier_solve_impl(gomilp_pool *pool, int64_t count, const int32_t *
         const int need = std::max(m_big, gomilp::batch_ldt(nn_big));
         if (use_batch && pool->large_loop && need > 1024 && need <= 2048) use_batch = false;
     }
-    if (use_batch) {
+    // Wide waves: the device-batched revised simplex, where every relaxation of the wave is one that a worker's Engine::solve runs on the
+    // revised pipelines without the exact-step guard (one root, cold, slack starts; a periodic refresh stays on the workers)
+    bool use_rev = false;
+    if (!use_batch && pool->batched && pool->batch_revised && count > 0 && !wa && nroots == 1 && pool->refresh == 0) {
+        int K_min = K_max;
+        for (int64_t i = 0; i < count; i++) K_min = std::min<int>(K_min, (int)(koff[i + 1] - koff[i]));
+        use_rev = RevBatchEngine::eligible(pool->view, K_min, K_max, pool->exact_degenerate, pool->cond_guard);
+        // (a branch row on one of the root's slack columns: the child has no slack basis)
+        const int64_t first_slack = (int64_t)pool->view.n - pool->view.m;
+        for (int64_t k = koff[0]; k < koff[count] && use_rev; k++) if (var[k] < 0 || var[k] >= first_slack) use_rev = false;
+    }
+    if (use_rev) {
+        if (!pool->rev) pool->rev.reset(new RevBatchEngine(pool->device));
+        auto on_done = [&](int64_t i, const BatchEngine::Outcome &o, const int32_t *basic, const double *xb) {   // (called on this thread)
+            if (o.stage != gomilp::BS_DONE) {   // the |x_art| band, the zero-level artificial exchange
+                agg.host_fallbacks++;
+                pool->submit([&full_solve, i](int w) { full_solve(w, i); });
+                return;
+            }
+            agg.relaxations++; agg.batched_relaxations++;
+            agg.pivots_phase1 += o.piv1; agg.pivots_phase2 += o.piv2; agg.bland_steps += o.bland; agg.phase1_runs += o.phase1_used;
+            if (basic) {
+                const int rc0 = o.status;
+                pool->submit([&finish, i, basic, xb, rc0](int w) { finish(w, i, basic, xb, rc0); });
+            } else {
+                status_out[i] = o.status;
+                if (o.status == GOMILP_ERR_UNBOUNDED) z_out[i] = -INFINITY;   // simplex.go:261-263
+            }
+        };
+        RevBatchEngine::Stats rs;
+        bool fits = true;
+        const int rc = pool->rev->run(pool->view, count, koff, var, sign, rhs, tol, pool->max_pivots, on_done, &rs, &fits);
+        pool->drain();
+        if (rc != GOMILP_OK) return rc;
+        if (fits) { bs.launches = rs.launches; bs.supersteps = rs.supersteps; bs.seconds_total = rs.seconds_total; }
+        else use_rev = false;   // the wave's buffers do not fit the free device memory: the workers take it, whole
+    }
+    if (use_rev) {
+        // (done above)
+    } else if (use_batch) {
         std::mutex agg_mu;
         std::vector<int64_t> cold_again;   // warm starts that spent their dual-pivot budget: solved cold by this same call
         auto on_done_at = [&](int64_t i, const BatchEngine::Outcome &o, const int32_t *basic, const double *xb) {

@@ -1,0 +1,247 @@
+// Host side of the device-batched revised simplex (engine_batch_revised.hpp): buffers, the fixed launch list of a superstep, the
+// hand-over of finished relaxations.
+#include "engine_batch_revised.hpp"
+
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#include "batch_revised.h"
+#include "kernels_common.h"
+
+namespace gomilp {
+
+#define RV_TRY(expr) do { if ((expr) != hipSuccess) return GOMILP_ERR_DEVICE; } while (0)
+
+namespace {
+constexpr int kFirstChunk = 8, kChunk = 32;   // pivots per superstep: most children of a frontier leave Phase I within a few pivots
+size_t even(size_t v) { return (v + 1) & ~(size_t)1; }
+}  // namespace
+
+struct RevBatchEngine::Buf {
+    double *d_at = nullptr, *d_work = nullptr;       // the children's At (assembled, never cleared) / everything else (cleared per wave)
+    size_t cap_at = 0, cap_work = 0;                 // in doubles
+    RevLP *d_lps = nullptr;
+    RevOut *d_out = nullptr;
+    int *d_act = nullptr;
+    size_t cap_lp = 0;
+    double *d_k = nullptr;                           // sign | rhs | b0 | c2 (doubles), then var | rho0 (ints)
+    size_t cap_k = 0;
+    RevOut *h_out = nullptr;
+    int *h_act = nullptr;
+    int32_t *h_basic = nullptr;
+    double *h_xb = nullptr;
+    size_t cap_h = 0;
+    void free_all() {
+        for (void *p : {(void *)d_at, (void *)d_work, (void *)d_lps, (void *)d_out, (void *)d_act, (void *)d_k}) if (p) hipFree(p);
+        for (void *p : {(void *)h_out, (void *)h_act, (void *)h_basic, (void *)h_xb}) if (p) hipHostFree(p);
+        d_at = d_work = d_k = nullptr; d_lps = nullptr; d_out = nullptr; d_act = nullptr;
+        h_out = nullptr; h_act = nullptr; h_basic = nullptr; h_xb = nullptr;
+        cap_at = cap_work = cap_lp = cap_k = cap_h = 0;
+    }
+};
+
+RevBatchEngine::RevBatchEngine(int device) : device_(device), b_(new Buf) {}
+
+RevBatchEngine::~RevBatchEngine() {
+    hipSetDevice(device_);
+    if (stream_) hipStreamSynchronize(stream_);
+    b_->free_all();
+    delete b_;
+    if (stream_) hipStreamDestroy(stream_);
+}
+
+void RevBatchEngine::release() {
+    hipSetDevice(device_);
+    if (stream_) hipStreamSynchronize(stream_);
+    b_->free_all();
+}
+
+bool RevBatchEngine::eligible(const Engine::RootView &R, int K_min, int K_max, int exact_degenerate, int cond_guard) {
+    if (R.verify_status != GOMILP_OK || !R.unit_basis) return false;
+    const int m_lo = R.m + K_min, m_hi = R.m + K_max, n_hi = R.n + K_max;
+    if (m_hi >= n_hi || (R.n - R.m) < 2 * m_hi) return false;   // the revised formulation (engine.cpp: use_tab's n - m < 2m rule)
+    // the exact-step guard is off for every shape (exact_wanted): the blocked tableau with exact steps stays on the workers
+    if (!(exact_degenerate == 0 || (exact_degenerate == 1 && m_lo > 256 && !(R.scale_span > 1e9)))) return false;
+    if (cond_guard && m_lo <= 64) return false;                  // the replay of gonum's condition guards runs in Engine::solve only
+    if (((m_hi + 1) & ~1) > kLdsWindowLd) return false;          // pools keep the row limit of one-pass LDS staging
+    return true;
+}
+
+int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t *koff, const int32_t *var, const double *sign,
+                        const double *rhs, double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits) {
+    const auto t0 = std::chrono::steady_clock::now();
+    *fits = true;
+    if (count <= 0) return GOMILP_OK;
+    RV_TRY(hipSetDevice(device_));
+    if (!stream_) RV_TRY(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    Buf &b = *b_;
+    const int m0 = R.m, n0 = R.n, ld0 = R.ld;
+    const int64_t k_base = koff[0], ktot = koff[count] - koff[0];
+    int K_max = 0;
+    for (int64_t i = 0; i < count; i++) K_max = std::max<int>(K_max, (int)(koff[i + 1] - koff[i]));
+    const int m_max = m0 + K_max, n_max = n0 + K_max, ld_max = (m_max + 1) & ~1;
+
+    // ---- layout: per relaxation, offsets into the two arenas (doubles; every buffer 16-byte aligned) ----
+    struct Lay { size_t at, binv0, binv1, xb, y, dvec, move, bb, rvec, c1, ysc, basic, nonbasic, inb, pkp, pkr, pip, pir, st; };
+    std::vector<Lay> lay((size_t)count);
+    size_t at_tot = 0, wk_tot = 0;
+    for (int64_t i = 0; i < count; i++) {
+        const int K = (int)(koff[i + 1] - koff[i]), m = m0 + K, n = n0 + K, ld = (m + 1) & ~1;
+        Lay &L = lay[(size_t)i];
+        L.at = at_tot; at_tot += (size_t)(n + 1) * ld;
+        auto take = [&](size_t doubles) { const size_t o = wk_tot; wk_tot += even(doubles); return o; };
+        L.binv0 = take((size_t)m * ld); L.binv1 = take((size_t)m * ld);
+        L.xb = take(ld); L.y = take(ld); L.dvec = take(ld); L.move = take(ld); L.bb = take(ld);
+        L.rvec = take((size_t)n + 1 - m); L.c1 = take((size_t)n + 1); L.ysc = take((size_t)64 * ld);
+        L.basic = take(((size_t)ld + 1) / 2); L.nonbasic = take(((size_t)n + 2 - m + 1) / 2); L.inb = take(((size_t)n + 2 + 1) / 2);
+        L.pkp = take(kMaxPartials); L.pkr = take(kMaxPartials); L.pip = take(kMaxPartials / 2); L.pir = take(kMaxPartials / 2);
+        L.st = take((sizeof(DevState) + 7) / 8);
+    }
+    const size_t k_doubles = even((size_t)2 * ktot + 2) + even((size_t)m0) + even((size_t)n_max + 2);
+    const size_t k_tot = k_doubles + ((size_t)ktot + 1 + (size_t)m0 + 1) / 2 + 2;
+    // ---- what has to grow must fit the free device memory (with the head-room of Engine::device_fits): else the wave goes to the workers
+    {
+        size_t grow = 0;
+        if (at_tot > b.cap_at) grow += at_tot;
+        if (wk_tot > b.cap_work) grow += wk_tot;
+        if (k_tot > b.cap_k) grow += k_tot;
+        grow *= sizeof(double);
+        if ((size_t)count > b.cap_lp) grow += (size_t)count * (sizeof(RevLP) + sizeof(RevOut) + sizeof(int));
+        if (grow) {
+            size_t avail = 0, total = 0;
+            RV_TRY(hipMemGetInfo(&avail, &total));
+            // (buffers that the re-allocation releases are not counted as free: conservative)
+            if (grow + grow / 16 + ((size_t)256 << 20) > avail) { *fits = false; return GOMILP_OK; }
+        }
+    }
+    auto regrow = [&](double **p, size_t *cap, size_t need) -> hipError_t {
+        if (need <= *cap) return hipSuccess;
+        if (*p) hipFree(*p);
+        *p = nullptr; *cap = 0;
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(p), need * sizeof(double));
+        if (e == hipSuccess) *cap = need;
+        return e;
+    };
+    RV_TRY(hipStreamSynchronize(stream_));
+    RV_TRY(regrow(&b.d_at, &b.cap_at, at_tot));
+    RV_TRY(regrow(&b.d_work, &b.cap_work, wk_tot));
+    RV_TRY(regrow(&b.d_k, &b.cap_k, k_tot));
+    if ((size_t)count > b.cap_lp) {
+        for (void *p : {(void *)b.d_lps, (void *)b.d_out, (void *)b.d_act}) if (p) hipFree(p);
+        for (void *p : {(void *)b.h_out, (void *)b.h_act}) if (p) hipHostFree(p);
+        b.d_lps = nullptr; b.d_out = nullptr; b.d_act = nullptr; b.h_out = nullptr; b.h_act = nullptr; b.cap_lp = 0;
+        RV_TRY(hipMalloc(reinterpret_cast<void **>(&b.d_lps), (size_t)count * sizeof(RevLP)));
+        RV_TRY(hipMalloc(reinterpret_cast<void **>(&b.d_out), (size_t)count * sizeof(RevOut)));
+        RV_TRY(hipMalloc(reinterpret_cast<void **>(&b.d_act), (size_t)count * sizeof(int)));
+        RV_TRY(hipHostMalloc(reinterpret_cast<void **>(&b.h_out), (size_t)count * sizeof(RevOut), hipHostMallocDefault));
+        RV_TRY(hipHostMalloc(reinterpret_cast<void **>(&b.h_act), (size_t)count * sizeof(int), hipHostMallocDefault));
+        b.cap_lp = (size_t)count;
+    }
+    if ((size_t)count * ld_max > b.cap_h) {
+        for (void *p : {(void *)b.h_basic, (void *)b.h_xb}) if (p) hipHostFree(p);
+        b.h_basic = nullptr; b.h_xb = nullptr; b.cap_h = 0;
+        RV_TRY(hipHostMalloc(reinterpret_cast<void **>(&b.h_basic), (size_t)count * ld_max * sizeof(int32_t), hipHostMallocDefault));
+        RV_TRY(hipHostMalloc(reinterpret_cast<void **>(&b.h_xb), (size_t)count * ld_max * sizeof(double), hipHostMallocDefault));
+        b.cap_h = (size_t)count * ld_max;
+    }
+
+    // ---- the wave's shared data: sign | rhs | b0 | c2, var | rho0 ----
+    std::vector<double> hk(k_tot, 0.0);
+    double *h_sign = hk.data(), *h_rhs = h_sign + ktot, *h_b0 = hk.data() + even((size_t)2 * ktot + 2), *h_c2 = h_b0 + even((size_t)m0);
+    int32_t *h_var = reinterpret_cast<int32_t *>(hk.data() + k_doubles), *h_rho = h_var + ktot + 1;
+    for (int64_t k = 0; k < ktot; k++) { h_sign[k] = sign[k_base + k]; h_rhs[k] = rhs[k_base + k]; h_var[k] = var[k_base + k]; }
+    for (int i = 0; i < m0; i++) { h_b0[i] = R.hb[(size_t)i]; h_rho[i] = R.rho0[(size_t)i]; }
+    for (int j = 0; j < n0; j++) h_c2[j] = R.hc[(size_t)j];   // c' = [c, 0] (subproblem.go:110-114)
+    double *d_sign = b.d_k, *d_rhs = d_sign + ktot, *d_b0 = b.d_k + (h_b0 - hk.data()), *d_c2 = b.d_k + (h_c2 - hk.data());
+    int32_t *d_var = reinterpret_cast<int32_t *>(b.d_k + k_doubles), *d_rho = d_var + ktot + 1;
+    RV_TRY(hipMemcpyAsync(b.d_k, hk.data(), k_tot * sizeof(double), hipMemcpyHostToDevice, stream_));
+
+    std::vector<RevLP> lps((size_t)count);
+    for (int64_t i = 0; i < count; i++) {
+        const int K = (int)(koff[i + 1] - koff[i]), m = m0 + K, n = n0 + K, ld = (m + 1) & ~1;
+        const Lay &L = lay[(size_t)i];
+        RevLP &d = lps[(size_t)i];
+        memset(&d, 0, sizeof(d));
+        double *w = b.d_work;
+        d.At = b.d_at + L.at; d.c2 = d_c2; d.c1 = w + L.c1; d.b = w + L.bb;
+        d.binv[0] = w + L.binv0; d.binv[1] = w + L.binv1;
+        d.xb = w + L.xb; d.y = w + L.y; d.dvec = w + L.dvec; d.move = w + L.move; d.rvec = w + L.rvec; d.yscratch = w + L.ysc;
+        d.basic = reinterpret_cast<int32_t *>(w + L.basic); d.nonbasic = reinterpret_cast<int32_t *>(w + L.nonbasic);
+        d.inb = reinterpret_cast<int32_t *>(w + L.inb);
+        d.pk_price = reinterpret_cast<unsigned long long *>(w + L.pkp); d.pk_ratio = reinterpret_cast<unsigned long long *>(w + L.pkr);
+        d.pi_price = reinterpret_cast<unsigned int *>(w + L.pip); d.pi_ratio = reinterpret_cast<unsigned int *>(w + L.pir);
+        d.st = reinterpret_cast<DevState *>(w + L.st);
+        d.b0 = d_b0; d.rhs = d_rhs + (koff[i] - k_base); d.rho0 = d_rho;
+        d.m0 = m0; d.n0 = n0; d.K = K; d.m = m; d.n = n; d.ld = ld;
+        d.max_pivots = max_pivots; d.tol_user = tol;
+        d.stage = RS_RUN; d.run = RR_NONE; d.cost = d_c2; d.f_var = d.f_pos = d.f_p = -1;
+    }
+    RV_TRY(hipMemcpyAsync(b.d_lps, lps.data(), (size_t)count * sizeof(RevLP), hipMemcpyHostToDevice, stream_));
+    RV_TRY(hipMemsetAsync(b.d_work, 0, wk_tot * sizeof(double), stream_));
+    int64_t launches = 0;
+    for (int64_t i = 0; i < count; i++) {
+        const RevLP &d = lps[(size_t)i];
+        launch_child_assemble(R.dAt, ld0, m0, n0, d.At, d.ld, d.K, d_var + (koff[i] - k_base), d_sign + (koff[i] - k_base), stream_);
+    }
+    launch_rv_init(b.d_lps, (int)count, stream_);
+    launches += count + 1;
+    RV_TRY(hipStreamSynchronize(stream_));   // (the pageable staging vectors go out of use here)
+    RV_TRY(hipGetLastError());
+
+    // ---- supersteps ----
+    const int gp = grid_for_rows(n_max + 1 - m0), gr = grid_for_rows(m_max);
+    const size_t lds = (size_t)ld_max * sizeof(double);
+    std::vector<int> act((size_t)count), done_now;
+    for (int64_t i = 0; i < count; i++) act[(size_t)i] = (int)i;
+    int64_t steps = 0;
+    int rc = GOMILP_OK;
+    while (!act.empty()) {
+        const int nact = (int)act.size();
+        memcpy(b.h_act, act.data(), (size_t)nact * sizeof(int));
+        RV_TRY(hipMemcpyAsync(b.d_act, b.h_act, (size_t)nact * sizeof(int), hipMemcpyHostToDevice, stream_));
+        launch_rv_setup(b.d_lps, b.d_act, nact, gr, ld_max, lds, stream_);
+        const int chunk = steps < 2 ? kFirstChunk : kChunk;
+        for (int t = 0; t < chunk; t++) launch_rv_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, stream_);
+        launch_rv_ctrl(b.d_lps, b.d_act, nact, b.d_out, stream_);
+        launches += 7 + 4 * chunk + 1;
+        RV_TRY(hipMemcpyAsync(b.h_out, b.d_out, (size_t)count * sizeof(RevOut), hipMemcpyDeviceToHost, stream_));
+        RV_TRY(hipStreamSynchronize(stream_));
+        RV_TRY(hipGetLastError());
+        steps++;
+        done_now.clear();
+        std::vector<int> next;
+        bool copies = false;
+        for (int id : act) {
+            const RevOut &o = b.h_out[id];
+            if (o.stage == RS_RUN) { next.push_back(id); continue; }
+            done_now.push_back(id);
+            if (o.stage == RS_DONE && (o.status == GOMILP_OK || o.status == GOMILP_ERR_BLAND || o.status == GOMILP_ERR_UNSUPPORTED)) {
+                const RevLP &d = lps[(size_t)id];
+                RV_TRY(hipMemcpyAsync(b.h_basic + (size_t)id * ld_max, d.basic, (size_t)d.m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+                RV_TRY(hipMemcpyAsync(b.h_xb + (size_t)id * ld_max, d.xb, (size_t)d.m * sizeof(double), hipMemcpyDeviceToHost, stream_));
+                copies = true;
+            }
+        }
+        if (copies) RV_TRY(hipStreamSynchronize(stream_));
+        for (int id : done_now) {
+            const RevOut &o = b.h_out[id];
+            BatchEngine::Outcome oc;
+            oc.stage = o.stage == RS_DONE ? BS_DONE : BS_HOST;
+            oc.status = o.status; oc.wrapped = o.wrapped; oc.phase1_used = o.phase1_used;
+            oc.piv1 = o.piv1; oc.piv2 = o.piv2; oc.bland = o.bland;
+            const bool fin = oc.stage == BS_DONE && (o.status == GOMILP_OK || o.status == GOMILP_ERR_BLAND || o.status == GOMILP_ERR_UNSUPPORTED);
+            on_done(id, oc, fin ? b.h_basic + (size_t)id * ld_max : nullptr, fin ? b.h_xb + (size_t)id * ld_max : nullptr);
+        }
+        act.swap(next);
+    }
+    if (stats) {
+        stats->launches = launches; stats->supersteps = steps;
+        stats->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return rc;
+}
+
+}  // namespace gomilp

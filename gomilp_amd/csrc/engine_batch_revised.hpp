@@ -1,0 +1,42 @@
+// Device-batched wave of WIDE relaxations (n - m >= 2m): the three-kernel revised simplex with the relaxation as a grid dimension
+// (batch_revised.hip).  The counterpart of BatchEngine (engine_batch.hpp), which only knows the tableau formulation: one stream, a
+// fixed list of launches per superstep for the whole wave, one host round trip per superstep.  It takes exactly the waves whose
+// relaxations a worker's Engine::solve would run on the revised pipelines without the exact-step guard, and computes what that
+// solve computes: the kernels run the helpers of simplex_helpers.h, the stages follow Engine::solve_locked / run_loop / host_bland.
+#pragma once
+#include <stdint.h>
+
+#include "engine.hpp"
+#include "engine_batch.hpp"
+
+namespace gomilp {
+
+class RevBatchEngine {
+   public:
+    struct Stats {
+        int64_t launches = 0, supersteps = 0;
+        double seconds_total = 0;
+    };
+    explicit RevBatchEngine(int device);
+    ~RevBatchEngine();
+    // do children of this root with K_min..K_max branch rows run on the revised pipelines, unguarded, on a worker with these knobs?
+    // (the predicate of Engine::solve_locked: use_tab / exact_wanted / shadow_trace_)
+    static bool eligible(const Engine::RootView &R, int K_min, int K_max, int exact_degenerate, int cond_guard);
+    // The wave (children of R; relaxation i has rows koff[i]..koff[i+1] of var / sign / rhs).  on_done as BatchEngine::run_roots: stage
+    // BS_DONE with the final status (basic / xb non-null where the status wants the final solve) or BS_HOST.  *fits = false: the wave's
+    // buffers do not fit the free device memory — nothing ran, the caller solves the wave on the workers.
+    int run(const Engine::RootView &R, int64_t count, const int64_t *koff, const int32_t *var, const double *sign, const double *rhs,
+            double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits);
+
+    // gives the wave buffers back (they grow with the largest wave seen: 5 MB per 300 x 1500 relaxation); the pool calls it when the
+    // root changes
+    void release();
+
+   private:
+    struct Buf;
+    int device_;
+    hipStream_t stream_ = nullptr;
+    Buf *b_;
+};
+
+}  // namespace gomilp

@@ -252,8 +252,11 @@ void gomilp_pool_destroy(gomilp_pool *pool);
  * relaxations runs its set-up pivot and its first block of 8 pivots on computed tableau entries and writes out only the tableaus that are
  * still alive behind that block — bit-identical), "batch_res" (default 0, opt-in: narrow waves in the
  * register-resident kernel k_b_res instead of k_b_loop — bit-identical, slower: DESIGN.md section 2.5d), "split_large" (default 1: a wave of >= 4 relaxations beyond 1024 rows runs as two interleaved schedules), "sample_batch" (1: time every batched block launch with HIP events), "batched" (default 1: the pivot loops of a wave run device-batched — grid.x = relaxation, O(1) host round trips per
- * superstep for the whole wave; 0: one host thread + stream per relaxation); any gomilp_ctx_set key is forwarded to the
- * worker contexts. */
+ * superstep for the whole wave; 0: one host thread + stream per relaxation), "batch_revised" (default 1: a WIDE wave, n - m >= 2m, whose
+ * relaxations a worker would run on the unguarded revised-simplex pipelines — slack starts of more than 256 rows at exact_degenerate = 1,
+ * any size above 64 rows at = 0 — runs on the device-batched revised simplex: the three-kernel pipeline with the relaxation as a grid
+ * dimension, Phase I and the Bland rule on the device, bit-identical to the worker path; 0: such waves on the workers, one relaxation per
+ * stream.  DESIGN.md section 2.5e); any gomilp_ctx_set key is forwarded to the worker contexts. */
 int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value);
 /* Upload the root standard form (row-major A0, stride lda) to every worker context of the pool. */
 int gomilp_pool_set_root(gomilp_pool *pool, const double *c0, const double *A0, int64_t lda, const double *b0, int64_t m0,

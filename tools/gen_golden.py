@@ -14,6 +14,9 @@ Files (numpy .npz, all arrays plain data — inputs are regenerated from the see
     milp_C3.npz              FIFO branch-and-bound over the 512x1024 MILP, node budget 127: per node parent, constraints,
                              status, z, decision, x
     milp_C1.npz              the 10-variable / 5-constraint plumbing case (BASELINE config 1), whole tree
+    wide_frontier_<m>_<nv>_<seed>.npz   wide roots (n - m >= 2m) for tests/test_gpu_wide_frontier.py: the root optimum, and per child of the
+                             waves P (2^6 sign patterns) and D (one down branch per fractional integer variable) status, z, x, pivot counts
+    milp_wide260.npz         FIFO branch-and-bound over the 260 x 1040 wide MILP, node budget 63
 """
 from __future__ import annotations
 
@@ -238,6 +241,62 @@ def gen_eqlp():
         log("wrote", fn, "status", r.status, "pivots", len(tr), "%.0f s" % dt)
 
 
+# (m, nv, seed, solve the children too).  The children of the 507 x 1014 root are narrow (n - m = 1014 < 2 (m + K)); those of the 507 x 1100
+# root are wide, and with 5 branch rows have ld = 512 (the fused pipeline on a worker)
+WIDE_ROOTS = [(260, 780, 1, True), (300, 1200, 2, True), (507, 1014, 5, False), (507, 1100, 5, False)]
+
+
+def wide_waves(root_x, mask):
+    """The two waves of tests/test_gpu_wide_frontier.py on a root optimum: P = the 64 sign patterns of 6 branch rows, D = one down branch
+    per fractional integer variable, highest index first."""
+    import math
+    P = synth.frontier_children(root_x, mask, 6)
+    D = [[(j, 1, float(math.floor(root_x[j])))] for j in range(len(mask) - 1, -1, -1) if mask[j] and root_x[j] != math.floor(root_x[j])]
+    return P, D
+
+
+def gen_wide():
+    from concurrent.futures import ThreadPoolExecutor
+    for m, nv, seed, kids in WIDE_ROOTS:
+        c, A, b = synth.dense_lp_standard_form(m, seed, nv)
+        mask = synth.integrality_mask(nv, m)
+        O.set_threads(THREADS)
+        t0 = time.time()
+        root = O.simplex(c, A, b, 0.0, None, fast_initial_basis=True)
+        log("wide root", m, nv, seed, "status", root.status, "%.0f s" % (time.time() - t0))
+        out = dict(m=m, nv=nv, seed=seed, root_x=root.x, root_z=root.z)
+        if kids:
+            n0 = A.shape[1]
+            O.set_threads(1)
+            for name, wave in zip("PD", wide_waves(root.x, mask)):
+                def one(i):
+                    cc, AA, bb = O.child_standard_form(c, A, b, wave[i])
+                    return O.simplex(cc, AA, bb, 0.0, None, fast_initial_basis=True)
+                t0 = time.time()
+                with ThreadPoolExecutor(max_workers=THREADS) as ex:   # ctypes releases the GIL inside the oracle call
+                    res = list(ex.map(one, range(len(wave))))
+                x = np.zeros((len(wave), n0))
+                for i, r in enumerate(res):
+                    if r.x is not None:
+                        x[i] = r.x[:n0]
+                out.update({name + "_status": np.array([r.status for r in res], np.int32), name + "_z": np.array([r.z for r in res]),
+                            name + "_has_x": np.array([r.x is not None for r in res], np.int32), name + "_x": x,
+                            name + "_pivots": np.array([(r.pivots_phase1, r.pivots_phase2, r.bland_steps) for r in res], np.int32)})
+                log("wide", m, "wave", name, len(wave), "children", "%.0f s" % (time.time() - t0))
+        fn = os.path.join(OUT, "wide_frontier_%d_%d_%d.npz" % (m, nv, seed))
+        np.savez_compressed(fn, **out)
+        log("wrote", fn)
+
+
+def gen_wide_tree(budget: int = 63):
+    m, nv, seed = 260, 780, 1
+    c, A, b = synth.dense_lp_standard_form(m, seed, nv)
+    integ = list(synth.integrality_mask(nv, m))
+    O.set_threads(THREADS)
+    res = O.solve_milp(c, A, b, None, None, integ, max_nodes=budget, simplex_fn=lambda cc, AA, bb: O.simplex(cc, AA, bb, 0.0, None, fast_initial_basis=True))
+    dump_tree(os.path.join(OUT, "milp_wide260.npz"), res, nv + m, dict(m=m, nv=nv, seed=seed, budget=budget))
+
+
 def main(argv):
     os.makedirs(OUT, exist_ok=True)
     O.build()
@@ -259,6 +318,10 @@ def main(argv):
             gen_eq()
         elif t == "eqlp":
             gen_eqlp()
+        elif t == "wide":
+            gen_wide()
+        elif t == "wide_tree":
+            gen_wide_tree()
         else:
             raise SystemExit("unknown target " + t)
     return 0
