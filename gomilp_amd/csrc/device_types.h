@@ -295,7 +295,7 @@ struct LUCtl {
     int32_t next[32];
     // look-ahead schedule, control block 0 only: arrival counters of the workgroups that run beside the panel (monotonic over the rounds of
     // a factorization: the update of the next panel's columns / the U-solve tiles), and the flag a wait that ran out of patience raises
-    uint32_t cnt_x, cnt_u, cnt_s;   // (cnt_x: the U-solve of the next panel's columns, one workgroup per round)
+    uint32_t cnt_x, cnt_u, cnt_s;   // (cnt_x: the U-solve of the next panel's columns, one workgroup per round — beside the one-workgroup panel only, luc_role.h)
     int32_t fault;
 };
 

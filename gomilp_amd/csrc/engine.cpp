@@ -99,7 +99,7 @@ int Engine::set(const std::string &key, int64_t v) {
     else if (key == "bt_fault") bt_fault_ = v;   // fault injection, diagnostic flavour only: 1 a workgroup of the block / loop kernels, 2 the U-solve workgroup of the look-ahead LU
 #endif
     else if (key == "general_device") general_device_ = v ? 1 : 0;
-    else if (key == "lu_cross") lu_cross_ = v ? 1 : 0;
+    else if (key == "lu_cross") lu_cross_ = v < 0 ? -1 : (v > 2 ? 2 : v);   // the panel's rows on the workgroups of one XCD (lu_cross.hip): 0 never, 1 sixteen slots in the plain schedule, 2 thirty-two slots in the schedule lu_blocked names, -1 (default) 2 for bases of 1281 .. 2048 rows
     else if (key == "general_block") general_block_ = v ? 1 : 0;
     else if (key == "general_min_rows") general_min_rows_ = v < 2 ? 2 : v;
     else if (key == "bt_groups") { if (v != -1 && v != 0 && v != 2 && v != 4 && v != 8 && v != 16) return GOMILP_ERR_BAD_SHAPE; bt_groups_ = v; }
@@ -920,14 +920,21 @@ int Engine::lu_factor(const Problem &P, bool *singular, const int32_t *basic_hos
         void drop() { if (held) Engine::loop_release(dev, 4, 0); held = false; }
     } look_slot(device_, a.look != 0);
     if (!look_slot.held) a.look = 0;
-    // opt-in: the rows of a panel on the workgroups of one XCD (lu_cross.hip) — the plain schedule with that panel
-    int cross_G = (lu_cross_ && compressed) ? luc_cross_groups(m, 1) : 0;
+    // the rows of a panel on the workgroups of one XCD (lu_cross.hip).  1: sixteen slots, the plain schedule.  2: thirty-two slots (half the
+    // rounds where a round ends because its slots are used up) in the schedule chosen above — the default where the look-ahead runs (a pool's
+    // workers factor side by side and every such panel asks for workgroups of the same XCD: they keep the one-workgroup panel), from
+    // the size at which it measures ahead (final solve, 32 slots against the one-workgroup panel: 1100 rows 1.28 / 1.24 ms, 1280 rows
+    // 1.40 / 1.41, 1536 rows 1.40 / 1.45, 1792 rows 1.74 / 1.81, 2048 rows 2.13 / 2.19; up to 1024 rows a step of 512 threads is cheaper
+    // than the exchange: 1.17 / 1.10 ms)
+    const int cross_mode = lu_cross_ >= 0 ? (int)lu_cross_ : ((m > 1280 && m <= 2048 && lu_look_) ? 2 : 0);
+    int cross_G = (cross_mode && compressed) ? luc_cross_groups(m, 1) : 0;
+    const int cross_slots = cross_mode == 2 ? 32 : 16;
     if (cross_G) {
         if (!w.luxrec) {
             HIP_TRY(dmalloc(&w.luxrec, luc_cross_doubles()));
             HIP_TRY(hipMemsetAsync(w.luxrec, 0, luc_cross_doubles() * sizeof(double), stream_));
         }
-        a.look = 0; look_slot.drop();
+        if (cross_mode != 2) { a.look = 0; look_slot.drop(); }
     }
     a.ctl_prev = a.ctl; a.Lp_prev = a.Lp; a.Up_prev = a.Up;
     a.rowsnap = w.rowstep + w.cap_m; a.rowsnap_prev = a.rowsnap;   // (launch_luc_rounds sets the round's parity)
@@ -977,7 +984,7 @@ int Engine::lu_factor(const Problem &P, bool *singular, const int32_t *basic_hos
             int k_seen = -1;   // steps done when the control block was last read
             const LUCtl *last = w.luctl_host;
             for (;;) {
-                launches_ += cross_G ? launch_luc_rounds_cross(a, w.rho, batch, w.luxrec, cross_G, stream_) : launch_luc_rounds(a, w.rho, batch, enq, stream_);
+                launches_ += cross_G ? launch_luc_rounds_cross(a, w.rho, batch, enq, w.luxrec, cross_G, cross_slots, stream_) : launch_luc_rounds(a, w.rho, batch, enq, stream_);
                 enq += batch;
                 if (oneshot) {
                     launch_luc_pack_small(a, w.Wd, stream_);
@@ -1015,9 +1022,13 @@ int Engine::lu_factor(const Problem &P, bool *singular, const int32_t *basic_hos
             if (!w.luctl_host[0].fault) break;
             // a wait inside a look-ahead launch ran out of patience (its workgroups never became resident together): once more, from the
             // basis, with the whole update behind each panel
-            if (attempt > 0 || !(a.look || cross_G)) return GOMILP_ERR_DEVICE;
-            a.look = 0; cross_G = 0; oneshot = false;
-            lu_look_faults_++; lu_look_fault_ = true;
+            // (the cross-workgroup panel under the look-ahead: first the same panel in the plain schedule — the rounds stay what they were —,
+            // then, should its own exchange give up as well, the one-workgroup panel)
+            if (attempt > 1 || !(a.look || cross_G)) return GOMILP_ERR_DEVICE;
+            if (a.look) a.look = 0; else cross_G = 0;
+            oneshot = false;
+            lu_look_faults_++; lu_look_fault_++;
+            if (w.luxrec) HIP_TRY(hipMemsetAsync(w.luxrec, 0, luc_cross_doubles() * sizeof(double), stream_));   // (a launch that gave up has not recorded how far its sequence numbers went)
             if (GOMILP_DBG_ENV("GOMILP_DEBUG_LOOP")) fprintf(stderr, "final_solve: a look-ahead launch gave up a wait (m %d, rounds enqueued %d, cnt_x %u cnt_u %u cnt_s %u): plain schedule\n", m, enq, w.luctl_host[0].cnt_x, w.luctl_host[0].cnt_u, w.luctl_host[0].cnt_s);
             if (compressed != transpose) launch_luc_gather(P.dAt, P.ld, m, w.basic, w.W, ldw, stream_);
             else {
@@ -1310,11 +1321,11 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
         st->seconds_total = now_s() - t0; st->kernel_launches = launches_;
         st->seconds_final_device = fs_device_; st->seconds_final_host = fs_host_;
         st->lu_dense_steps = lu_dense_; st->lu_rounds = lu_rounds_;
-        if (lu_look_fault_) st->device_retries = 1;   // (the final solve was repeated with the plain LU schedule)
+        if (lu_look_fault_) st->device_retries = lu_look_fault_;   // (the final solve was repeated with the plain LU schedule)
         return code;
     };
     launches_ = 0;
-    fs_device_ = fs_host_ = 0; lu_look_fault_ = false;
+    fs_device_ = fs_host_ = 0; lu_look_fault_ = 0;
     last_trace_.clear();
     last_trace_total_ = 0;
     if (P.verify_status != GOMILP_OK) {  // simplex.go:94-100
@@ -1809,7 +1820,7 @@ int Engine::finish_from_basis(int64_t id, const int32_t *basic_in, const double 
     if (opt_f) *opt_f = std::numeric_limits<double>::quiet_NaN();
     if (id < 0 || (size_t)id >= problems_.size() || !problems_[id] || !opt_f || !opt_x || !has_x || !basic_in || !xb_updated) return GOMILP_ERR_BAD_SHAPE;
     const Problem &P = *problems_[id];
-    launches_ = 0; fs_device_ = fs_host_ = 0; lu_look_fault_ = false;
+    launches_ = 0; fs_device_ = fs_host_ = 0; lu_look_fault_ = 0;
     int rc = ensure_work(P.m, P.n + 1);
     if (rc != GOMILP_OK) return rc;
     std::vector<int32_t> basic(basic_in, basic_in + P.m);
@@ -1819,7 +1830,7 @@ int Engine::finish_from_basis(int64_t id, const int32_t *basic_in, const double 
     st->seconds_total = now_s() - t0; st->kernel_launches = launches_;
     st->seconds_final_device = fs_device_; st->seconds_final_host = fs_host_;
     st->lu_dense_steps = lu_dense_; st->lu_rounds = lu_rounds_;
-    if (lu_look_fault_) st->device_retries = 1;
+    if (lu_look_fault_) st->device_retries = lu_look_fault_;
     return rc;
 }
 

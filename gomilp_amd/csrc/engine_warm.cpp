@@ -155,11 +155,11 @@ int Engine::warm_locked(int64_t id, const Kept &K, int J, int dual_budget, doubl
         st->seconds_total = now_s() - t0; st->kernel_launches = launches_;
         st->seconds_final_device = fs_device_; st->seconds_final_host = fs_host_;
         st->lu_dense_steps = lu_dense_; st->lu_rounds = lu_rounds_;
-        if (lu_look_fault_) st->device_retries = 1;
+        if (lu_look_fault_) st->device_retries = lu_look_fault_;
         return code;
     };
     launches_ = 0;
-    fs_device_ = fs_host_ = 0; lu_look_fault_ = false;
+    fs_device_ = fs_host_ = 0; lu_look_fault_ = 0;
     last_trace_.clear();
     last_trace_total_ = 0;
     const int m = P.m, n = P.n, mp = K.m, Kc = (int)P.kvar.size();

@@ -1,4 +1,4 @@
-// The panel of the compressed gonum-order LU (lu_compressed.hip) with its ROWS on the workgroups of one XCD (round 5, OPT-IN: knob lu_cross).
+// The panel of the compressed gonum-order LU (lu_compressed.hip) with its ROWS on the workgroups of one XCD (knob lu_cross; the default for bases of 1281 .. 2048 rows).
 //
 // k_luc_panel_slots runs a round's dense steps on ONE workgroup of sixteen waves: a dense step is the issue time of those waves on the four
 // SIMDs of one CU (7.7 k cycles, DESIGN.md section 2.3 "Round 5").  Here G workgroups of four waves (one per SIMD) hold 256 rows each, one
@@ -14,20 +14,37 @@
 //     for the elimination came with the same load;
 //   * the owner of the pivot row does the global bookkeeping (rowstep, pivrow, the control block's step list, the U row's stores).
 // Same arithmetic, same step order, same round structure as the one-workgroup panel (k_luc_usolve / k_luc_trail follow unchanged): the
-// schedules are compared bit for bit (tests/test_gpu_parity.py).  Waits are bounded: a workgroup that runs out of patience raises the
-// control block's fault flag, every workgroup leaves, and the host repeats the factorization with the one-workgroup panel.
+// schedules are compared bit for bit (tests/test_gpu_parity.py, tests/test_gpu_lu_cross_look.py).  Waits are bounded: a workgroup that runs
+// out of patience raises the control block's fault flag, every workgroup leaves, and the host repeats the factorization (below).
+// Two widths (knob lu_cross):
+//   1  16 register slots, the plain schedule (three launches per round) — the form of round 5, kept as it was;
+//   2  32 slots in two register tuples of 16 (a uniform dynamic index reaches 16 doubles; no scratch): one compute unit's registers hold 16
+//      slots for 2048 rows, so the one-workgroup panel's rounds end after ~17 of the 32 steps a round may take (every freed slot goes to a
+//      column whose step lies far ahead) — 23 rounds at the metric size; with one row per lane there is room for 32: 12 rounds.  The record
+//      grows to 37 slots (five 16-byte loads per lane and poll).  Under lu_blocked = 3 this panel is the PANEL ROLE of the look-ahead launch
+//      (luc_role.h): blocks 0, 8, .., 8 (G - 1) are the panel, every other block (index remapped) finishes the round before beside it; the
+//      panel hands over what k_luc_panel_slots<.., true> hands over — LUCtl::next / nnext (the scan the next panel runs anyway), the rowstep
+//      snapshot (every lane knows its own row), Lp / Up / control block by round parity — and waits for cnt_u before its column loads.
+//      The legality argument of the look-ahead carries over unchanged: phase T leaves alone the columns the panel
+//      loads and the unit columns of rows still active when the round before ended (the only columns this panel writes: a listed column,
+//      or the unit column of the row a dense step takes), and every read of the round's pivot rows in phase U's columns is behind cnt_s
+//      before workgroup 0 writes their U entries.
+// Fall-backs (engine.cpp lu_factor, one stats.device_retries each): a look-ahead launch that gave up a wait -> the SAME panel in the plain
+// schedule (the rounds stay what they were); an exchange of the panel that gave up -> the one-workgroup panel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bt_loop.h"
 #include "device_types.h"
 #include "kernels_common.h"
+#include "luc_role.h"
 
 namespace gomilp {
 
 namespace {
 
-constexpr int kLxSlots = 24;          // slots per record: 3 header values + up to 16 + 5 spare
+constexpr int kLxSlots = 24;          // slots per record of the 16-slot panel: 4 header values + 16 + the XCC id + 3 spare (three loads per lane and poll)
+constexpr int kLxSlots32 = 40;        // ... of the 32-slot panel: 4 + 32 + 1 + 3 spare (five loads)
 constexpr int kLxHeader = 16;         // doubles in front of the records: [0] = exchanges completed so far
 constexpr int kLxSpinLimit = 400000;  // polls (~1 us each)
 
@@ -39,6 +56,18 @@ __device__ __forceinline__ void lx_load3(const xpair *p0, const xpair *p1, const
 __device__ __forceinline__ void lx_load3_fast(const xpair *p0, const xpair *p1, const xpair *p2, xpair (&v)[3]) {   // (never served by L1: the XCD's L2 is the coherence point of its CUs)
     asm volatile("global_load_dwordx4 %0, %3, off nt\n\tglobal_load_dwordx4 %1, %4, off nt\n\tglobal_load_dwordx4 %2, %5, off nt\n\ts_waitcnt vmcnt(0)"
                  : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]) : "v"(p0), "v"(p1), "v"(p2) : "memory");
+}
+
+// five slots of a record, 128 bytes apart (lane l: slots (l & 7) + 8 r of record l >> 3)
+__device__ __forceinline__ void lx_load5(const xpair *p, xpair (&v)[5]) {
+    asm volatile("global_load_dwordx4 %0, %5, off sc1\n\tglobal_load_dwordx4 %1, %5, off offset:128 sc1\n\tglobal_load_dwordx4 %2, %5, off offset:256 sc1\n\t"
+                 "global_load_dwordx4 %3, %5, off offset:384 sc1\n\tglobal_load_dwordx4 %4, %5, off offset:512 sc1\n\ts_waitcnt vmcnt(0)"
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]) : "v"(p) : "memory");
+}
+__device__ __forceinline__ void lx_load5_fast(const xpair *p, xpair (&v)[5]) {
+    asm volatile("global_load_dwordx4 %0, %5, off nt\n\tglobal_load_dwordx4 %1, %5, off offset:128 nt\n\tglobal_load_dwordx4 %2, %5, off offset:256 nt\n\t"
+                 "global_load_dwordx4 %3, %5, off offset:384 nt\n\tglobal_load_dwordx4 %4, %5, off offset:512 nt\n\ts_waitcnt vmcnt(0)"
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]) : "v"(p) : "memory");
 }
 
 }  // namespace
@@ -58,15 +87,28 @@ __device__ unsigned long long g_lux_stamps[4 * 16];
 #define LUX_STAMP(S) do { } while (0)
 #endif
 
-template <int G, int NB, int SMAX>
+// NB: register slots — 16 (one tuple) or 32 (two tuples of 16 behind a uniform branch: the widest a uniform dynamic index reaches).
+// LK: the panel role of the look-ahead launch (luc_role.h): blocks 0, 8, .., 8 (G - 1) are the panel, every other block finishes the round
+// before beside it.
+template <int G, int NB, int SMAX, bool LK>
 __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restrict__ pivrow, xpair *__restrict__ xrec) {
     constexpr int T = 256, NW = 4, MAXM = 256 * G;
-    static_assert(NB == 16 && SMAX <= 32 && G * kLxSlots <= 192, "16 slots in one register tuple; a poll is three loads per lane");
+    static_assert((NB == 16 || NB == 32) && SMAX <= 32 && G <= 8, "register tuples of 16 slots; lane l polls record l >> 3");
+    constexpr int NH = NB / 16;                              // register tuples
+    constexpr int NSL = NB == 16 ? kLxSlots : kLxSlots32;    // slots per record
+    constexpr int NLD = NSL / 8;                             // loads per lane and poll
+    constexpr int NUSE = 5 + NB;                             // slots a record uses: 4 header values, NB entries, the XCC id
     typedef unsigned short idx_t;
-    typedef double vec __attribute__((ext_vector_type(NB)));
+    typedef double vec __attribute__((ext_vector_type(16)));
     constexpr idx_t NONE = 0xFFFF;
-    if (blockIdx.x & 7) return;   // 8 G blocks are launched: blocks 0, 8, 16, ... land on one XCD (round-robin deal), the rest leave at once
-    const int g = (int)blockIdx.x >> 3;
+    const int bx = (int)blockIdx.x;
+    if ((bx & 7) || (bx >> 3) >= G) {   // blocks 0, 8, 16, ... land on one XCD (round-robin deal): the panel
+        if constexpr (LK) {             // the others: the previous round's U-solve and update (plain launch: they leave at once)
+            if (!a.ctl_base->fault) luc_role<T, SMAX, true>(a, bx - min(G, (bx + 7) >> 3), (int)gridDim.x - G);
+        }
+        return;
+    }
+    const int g = bx >> 3;
     __shared__ idx_t s_lpos[MAXM];
     __shared__ idx_t s_rowat[MAXM];
     __shared__ idx_t s_unit[MAXM];
@@ -76,7 +118,7 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
     __shared__ unsigned int redL[2][NW];
     __shared__ int s_slotcol[NB];
     __shared__ int s_nload, s_stop, s_limit, s_sigma;
-    __shared__ __attribute__((aligned(16))) double s_post[NW][kLxSlots];   // a wave's candidate hands its record to the wave's lanes: one store instruction posts it
+    __shared__ __attribute__((aligned(16))) double s_post[NW][NSL];   // a wave's candidate hands its record to the wave's lanes: one store instruction posts it
     if (a.ctl_base->fault) return;
     LUCtl *ctl = a.ctl;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -87,6 +129,10 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
         if (g == 0 && tid == 0) { ctl->nsteps = 0; ctl->ndrop = 0; ctl->nnext = 0; ctl->k_next = k0; ctl->k0 = k0; ctl->k1 = k0; ctl->rounds = a.ctl_prev->rounds; ctl->ksync = a.ctl_prev->ksync; }
         return;
     }
+#ifdef GOMILP_DEBUG
+    unsigned long long tacc[16] = {}, tprev = 0;   // segments 0 .. 8: the step loop; 9 index maps, 10 the wait for phase U, 11 column loads, 12 what follows the loop
+#endif
+    LUX_STAMP(-1);
     for (int R = tid; R < MAXM; R += T) {
         const bool in = R < m;
         s_lpos[R] = (idx_t)(in ? a.lpos[R] : R);
@@ -132,11 +178,30 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
     bool act = (R < m) && s_active[R < m ? R : 0];
     const idx_t uc0 = s_ucol[R < m ? R : 0];
     const int myucol = (act && uc0 != NONE) ? (int)uc0 : 0x7FFFFFFF;   // the step that retires this row unless a dense step takes it first
-    vec v;
+    LUX_STAMP(9);
+    if constexpr (LK) {
+        // the columns this panel loads are brought up to date by phase U of this launch (luc_role): wait for its workgroups
+        if (tid == 0) s_stop = luc_spin(&a.ctl_base->cnt_u, (uint32_t)(a.round + 1) * (uint32_t)((m + 63) / 64)) ? 1 : 0;
+        __syncthreads();
+        if (!s_stop) {
+            if (tid == 0) {
+                a.ctl_base->fault = 1;
+                if (g == 0) { ctl->nsteps = 0; ctl->ndrop = 0; ctl->nnext = 0; ctl->k_next = k0; ctl->k0 = k0; ctl->k1 = k0; ctl->rounds = a.ctl_prev->rounds; ctl->ksync = a.ctl_prev->ksync; }
+            }
+            return;
+        }
+    }
+    LUX_STAMP(10);
+    vec v[NH];
     {
         const double *src = a.W + (act ? R : 0);
+        if constexpr (LK) {   // the cells come from phase U of this launch: agent scope
 #pragma unroll
-        for (int c = 0; c < NB; c++) v[c] = (act && c < nload) ? src[(size_t)__builtin_amdgcn_readlane(myslotcol, c) * ldw] : 0.0;
+            for (int c = 0; c < NB; c++) v[c / 16][c % 16] = (act && c < nload) ? luc_ld_agent(&src[(size_t)__builtin_amdgcn_readlane(myslotcol, c) * ldw]) : 0.0;
+        } else {
+#pragma unroll
+            for (int c = 0; c < NB; c++) v[c / 16][c % 16] = (act && c < nload) ? src[(size_t)__builtin_amdgcn_readlane(myslotcol, c) * ldw] : 0.0;
+        }
     }
     __syncthreads();
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the column loads are retired in front of the loop (see k_luc_panel_slots)
@@ -144,14 +209,11 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
     unsigned int myxcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(myxcc));
     myxcc &= 0xFu;
-    bool fast = false;   // SAFE (sc1) accesses until an exchange has shown that all G workgroups sit on one XCD (slot 20 of a record: the XCC id)
+    bool fast = false;   // SAFE (sc1) accesses until an exchange has shown that all G workgroups sit on one XCD (slot 4 + NB of a record: the XCC id)
     const double seq0 = xrec[0][0];
-    xpair *recs = xrec + kLxHeader / 2;   // [2 parities][G][kLxSlots]
+    xpair *recs = xrec + kLxHeader / 2;   // [2 parities][G][NSL]
     int nx = 0;
-#ifdef GOMILP_DEBUG
-    unsigned long long tacc[16] = {}, tprev = 0;
-#endif
-    LUX_STAMP(-1);
+    LUX_STAMP(11);
     int kcur = k0, s = 0, k1 = m;
     int ksync = a.ctl_prev->ksync;   // the index maps (lpos / rowat) hold the interchanges of the steps < ksync: the rest waits in the log (pivrow)
     bool fault = false;
@@ -160,7 +222,8 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
         if (w == 0) {
             const unsigned int key = (lane < NB && ((live >> lane) & 1u)) ? (unsigned int)myslotcol : 0x7FFFFFFFu;
             unsigned int mn = row_min_u32(key);
-            mn = (unsigned int)__builtin_amdgcn_readlane((int)mn, 0);
+            if constexpr (NB == 16) mn = (unsigned int)__builtin_amdgcn_readlane((int)mn, 0);
+            else mn = min((unsigned int)__builtin_amdgcn_readlane((int)mn, 0), (unsigned int)__builtin_amdgcn_readlane((int)mn, 16));
             const bool listed = live != 0 && s < SMAX;
             const int limit = listed ? (int)mn : m;
             const unsigned long long hit = __ballot(key == mn && lane < NB);
@@ -195,41 +258,50 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
             double *dst = a.W + R;
 #pragma unroll
             for (int c = 0; c < NB; c++)
-                if ((live >> c) & 1u) dst[(size_t)__builtin_amdgcn_readlane(myslotcol, c) * ldw] = v[c];
+                if ((live >> c) & 1u) dst[(size_t)__builtin_amdgcn_readlane(myslotcol, c) * ldw] = v[c / 16][c % 16];
             act = false;
         }
         if (kstop < limit || live == 0 || s >= SMAX) { k1 = kstop; break; }
         const int k = limit;
         LUX_STAMP(2);
         // ---- dense step k on slot sigma: this workgroup's candidate
-        const double x = v[sigma];
+        double x;
+        if constexpr (NH == 1) x = v[0][sigma];   // uniform index
+        else {   // (the empty asm keeps the uniform branch a branch: see k_luc_panel_slots)
+            if (sigma < 16) { asm volatile(""); x = v[0][sigma & 15]; }
+            else { asm volatile(""); x = v[NH - 1][sigma & 15]; }
+        }
         const double xm = act ? -fabs(x) : __builtin_inf();
         // one exchange: the wave that holds the workgroup's candidate hands the record {h0, h1, row, 1 / a_ik, XCC id | the row's entries in the NB
         // slots} to its lanes (LDS, no barrier: one wave), which post it with ONE store instruction; every wave then polls the G records —
-        // lane l reads the slots (l & 7), + 8, + 16 of record l >> 3
-        xpair rv[3];
+        // lane l reads the slots (l & 7), + 8, + 16 (+ 24, + 32 with 32 slots) of record l >> 3
+        xpair rv[NLD];
         auto exchange = [&](bool poster, double h0, double h1) {
             const double seq = seq0 + (double)(nx + 1);
-            xpair *mine = recs + ((size_t)((nx + 1) & 1) * G + g) * kLxSlots;
+            xpair *mine = recs + ((size_t)((nx + 1) & 1) * G + g) * NSL;
             if (__any(poster)) {   // (uniform per wave)
                 double *sp = s_post[w];
                 if (poster) {
                     sp[0] = h0; sp[1] = h1; sp[2] = (double)R;
                     sp[3] = act ? 1.0 / x : 0.0;   // dgetf2.go:54-56 scales by the reciprocal
 #pragma unroll
-                    for (int c = 0; c < NB; c++) sp[4 + c] = v[c];
-                    sp[20] = (double)myxcc;
+                    for (int c = 0; c < NB; c++) sp[4 + c] = v[c / 16][c % 16];
+                    sp[4 + NB] = (double)myxcc;
                 }
                 __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the candidate's LDS writes have landed (same wave: in order)
-                if (lane < 21) xstore(mine + lane, xpair{seq, sp[lane]}, fast);
+                if (lane < NUSE) xstore(mine + lane, xpair{seq, sp[lane]}, fast);
             }
-            const xpair *base = recs + (size_t)((nx + 1) & 1) * G * kLxSlots;
+            const xpair *base = recs + (size_t)((nx + 1) & 1) * G * NSL;
             const int g2 = lane >> 3, j0 = lane & 7;
             const bool mineok = g2 < G;
-            const xpair *q0 = base + (size_t)(mineok ? g2 : 0) * kLxSlots + j0;
+            const xpair *q0 = base + (size_t)(mineok ? g2 : 0) * NSL + j0;
             for (int it = 0;; it++) {
-                if (fast) lx_load3_fast(q0, q0 + 8, q0 + 16, rv); else lx_load3(q0, q0 + 8, q0 + 16, rv);
-                const bool ok = !mineok || (rv[0][0] == seq && rv[1][0] == seq && (j0 + 16 > 20 || rv[2][0] == seq));   // the slots a record uses: 0 .. 20
+                if constexpr (NLD == 3) { if (fast) lx_load3_fast(q0, q0 + 8, q0 + 16, rv); else lx_load3(q0, q0 + 8, q0 + 16, rv); }
+                else { if (fast) lx_load5_fast(q0, rv); else lx_load5(q0, rv); }
+                bool ok = true;   // the slots a record uses: 0 .. 4 + NB
+#pragma unroll
+                for (int r = 0; r < NLD; r++) ok = ok && (j0 + 8 * r >= NUSE || rv[r][0] == seq);
+                ok = ok || !mineok;
                 if (__all(ok)) break;
                 if (it >= kLxSpinLimit) { fault = true; break; }
                 __builtin_amdgcn_s_sleep(1);
@@ -260,7 +332,7 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
         if (fault) break;
         LUX_STAMP(5);   // local pick + post + poll
         if (!fast) {   // every record carries its workgroup's XCC id: all equal -> the XCD's L2 is the coherence point, plain stores / nt loads from here on
-            const double xc = __shfl(rv[2][1], (lane & ~7) + 4);   // slot 20 = 4 + 16
+            const double xc = __shfl(rv[(4 + NB) >> 3][1], (lane & ~7) + 4);   // slot 4 + NB
             fast = __all(!head || xc == (double)myxcc);
         }
         const double wmL = head ? rv[0][1] : __builtin_inf();
@@ -321,8 +393,12 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
         {
             const int c = lane & (NB - 1);
             const int src = 8 * gw + ((4 + c) & 7), rr = (4 + c) >> 3;
-            const double b0 = __shfl(rv[0][1], src), b1 = __shfl(rv[1][1], src), b2 = __shfl(rv[2][1], src);
-            prl = rr == 0 ? b0 : (rr == 1 ? b1 : b2);
+            prl = __shfl(rv[0][1], src);
+#pragma unroll
+            for (int r = 1; r < NLD; r++) {
+                const double br = __shfl(rv[r][1], src);
+                prl = rr == r ? br : prl;
+            }
         }
         LUX_STAMP(6);   // pick
         const bool owner = act && R == P;
@@ -336,7 +412,7 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
             double *dst = a.W + R;   // the pivot row's U entries (slot sigma holds column k)
 #pragma unroll
             for (int cc = 0; cc < NB; cc++)
-                if ((live >> cc) & 1u) dst[(size_t)__builtin_amdgcn_readlane(myslotcol, cc) * ldw] = v[cc];
+                if ((live >> cc) & 1u) dst[(size_t)__builtin_amdgcn_readlane(myslotcol, cc) * ldw] = v[cc / 16][cc % 16];
         }
         const idx_t uc = (P >= 0 && P < MAXM) ? s_ucol[P] : NONE;
         const int k2 = (uc != NONE && (int)uc > k) ? (int)uc : -1;   // taking row P makes its unit column (if still to come) dense
@@ -359,33 +435,53 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
 #pragma unroll
             for (int c = 0; c < NB; c++) {
                 const double pc = readlane_f64(prz, c);
-                v[c] = __dadd_rn(__dmul_rn(nl, pc), v[c]);
+                v[c / 16][c % 16] = __dadd_rn(__dmul_rn(nl, pc), v[c / 16][c % 16]);
             }
         }
         if (k2 >= 0) {
             const double vn = (act && !singular) ? __dadd_rn(__dmul_rn(nl, 1.0), 0.0) : 0.0;
-            v[sigma] = vn;
+            if constexpr (NH == 1) v[0][sigma] = vn;
+            else {
+                if (sigma < 16) { asm volatile(""); v[0][sigma & 15] = vn; }
+                else { asm volatile(""); v[NH - 1][sigma & 15] = vn; }
+            }
             if (lane == sigma) { myslotcol = k2; myslotin = k; }
         } else live = others;
         s++;
         kcur = k + 1;
         LUX_STAMP(8);   // elimination
     }
-#ifdef GOMILP_DEBUG
-    if (g == 0 && lane == 0) {
-        for (int sg = 0; sg < 9; sg++) atomicAdd(&g_lux_stamps[w * 16 + sg], tacc[sg]);
-        if (w == 0) atomicAdd(&g_lux_stamps[15], (unsigned long long)s);
-    }
-#endif
     if (fault) {
         if (lane == 0) a.ctl_base->fault = 1;
         return;
     }
+    if constexpr (LK) {
+        // rowstep as this round leaves it, for the update workgroups that run beside the next panel: every lane knows its own row (the step
+        // that took it was stored by this lane, or by an earlier launch)
+        if (R < m) a.rowsnap[R] = act ? -1 : a.rowstep[R];
+    }
     if (g != 0) return;
+    __syncthreads();   // the last run's rows have left s_active (the scan below reads it)
     for (int R2 = tid; R2 < m; R2 += T) a.lpos[R2] = s_lpos[R2];
     int ndl = 0;
     if (w == 0) {
-        if (lane == 0) ctl->nnext = 0;
+        if constexpr (LK) {
+            // the columns the next round's panel will load: its own scan (above), run on the state this round leaves
+            int n = 0;
+            for (int base = k1; base < m && n < NB; base += 64) {
+                const int k = base + lane;
+                bool dense = false;
+                if (k < m) {
+                    const idx_t ur = s_unit[k];
+                    dense = ur == NONE || !s_active[ur];
+                }
+                const unsigned long long mask = __ballot(dense);
+                const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+                if (dense && n + rank < NB) ctl->next[n + rank] = k;
+                n += __popcll(mask);
+            }
+            if (lane == 0) ctl->nnext = n < NB ? n : NB;
+        } else if (lane == 0) ctl->nnext = 0;
         const bool on = lane < NB && ((live >> lane) & 1u);
         const unsigned long long msk = __ballot(on);
         ndl = __popcll(msk);
@@ -399,6 +495,13 @@ __global__ __launch_bounds__(256) void k_luc_panel_x(LUArgs a, int32_t *__restri
         ctl->rounds = a.ctl_prev->rounds + 1; ctl->ksync = ksync;
         xrec[0] = xpair{seq0 + (double)nx, 0.0};
     }
+    LUX_STAMP(12);
+#ifdef GOMILP_DEBUG
+    if (lane == 0) {   // (workgroup 0; a launch that gave up a wait is not counted)
+        for (int sg = 0; sg < 13; sg++) atomicAdd(&g_lux_stamps[w * 16 + sg], tacc[sg]);
+        if (w == 0) { atomicAdd(&g_lux_stamps[15], (unsigned long long)s); atomicAdd(&g_lux_stamps[14], 1ull); }
+    }
+#endif
 }
 
 // once every step is done a row's logical position is the step that took it — what the solves and the host read (the panel's maps hold the
@@ -410,21 +513,25 @@ __global__ void k_luc_lpos_final(LUArgs a) {
 void launch_luc_lpos_final(const LUArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_luc_lpos_final, dim3((a.m + 255) / 256), dim3(256), 0, s, a); }
 
 // ---- host side
-size_t luc_cross_doubles() { return (size_t)kLxHeader + 2 * 2 * 8 * kLxSlots; }   // header + two parities of eight records (xpairs = 2 doubles)
+size_t luc_cross_doubles() { return (size_t)kLxHeader + 2 * 2 * 8 * kLxSlots32; }   // header + two parities of eight records (xpairs = 2 doubles) of the wider form
 int luc_cross_groups(int m, int want) {   // workgroups for a basis of m rows (0: not this schedule)
     if (want <= 0 || m < 64) return 0;
     const int need = (m + 255) / 256;
     if (need > 8) return 0;
     return need <= 2 ? 2 : (need <= 4 ? 4 : 8);
 }
+// slots: 16 or 32 register slots; nrole > 0: the look-ahead launch (32 slots) with that many workgroups beside the panel's
 template <int G>
-static void luc_cross_panel(const LUArgs &a, int32_t *pivrow, double *xrec, hipStream_t s) {
-    hipLaunchKernelGGL((k_luc_panel_x<G, 16, 32>), dim3(8 * G), dim3(256), 0, s, a, pivrow, reinterpret_cast<xpair *>(xrec));
+static void luc_cross_panel(const LUArgs &a, int32_t *pivrow, double *xrec, int slots, int nrole, hipStream_t s) {
+    xpair *xr = reinterpret_cast<xpair *>(xrec);
+    if (slots != 32) hipLaunchKernelGGL((k_luc_panel_x<G, 16, 32, false>), dim3(8 * G), dim3(256), 0, s, a, pivrow, xr);
+    else if (nrole <= 0) hipLaunchKernelGGL((k_luc_panel_x<G, 32, 32, false>), dim3(8 * G), dim3(256), 0, s, a, pivrow, xr);
+    else if constexpr (G >= 4) hipLaunchKernelGGL((k_luc_panel_x<G, 32, 32, true>), dim3(G + (nrole > 8 * G ? nrole : 8 * G)), dim3(256), 0, s, a, pivrow, xr);   // (every panel block 8 g lies inside the grid)
 }
-void launch_luc_cross_panel(const LUArgs &a, int32_t *pivrow, double *xrec, int G, hipStream_t s) {
-    if (G == 2) luc_cross_panel<2>(a, pivrow, xrec, s);
-    else if (G == 4) luc_cross_panel<4>(a, pivrow, xrec, s);
-    else luc_cross_panel<8>(a, pivrow, xrec, s);
+void launch_luc_cross_panel(const LUArgs &a, int32_t *pivrow, double *xrec, int G, int slots, int nrole, hipStream_t s) {
+    if (G == 2) luc_cross_panel<2>(a, pivrow, xrec, slots, 0, s);   // (bases of up to 512 rows: below the look-ahead's range)
+    else if (G == 4) luc_cross_panel<4>(a, pivrow, xrec, slots, nrole, s);
+    else luc_cross_panel<8>(a, pivrow, xrec, slots, nrole, s);
 }
 #ifdef GOMILP_DEBUG
 void lux_stamps_read(unsigned long long *out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lux_stamps), sizeof(unsigned long long) * 64); }
