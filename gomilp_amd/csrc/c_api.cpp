@@ -205,6 +205,9 @@ gomilp_pool *gomilp_pool_create(int device, int workers, int *status) {
         // the workers finish the relaxations of a wave side by side, next to the batched schedule's own persistent launches: their final
         // solves keep the LU schedule that waits for nobody (lu_compressed.hip: look-ahead launches wait for their own workgroups)
         p->eng.back()->set("lu_look", 0);
+        // ... and for the same reason never the eight-workgroup LU panel of the bases beyond 4096 rows (knob lu_large: every such panel wants
+        // 8 CUs of one XCD with nearly all of their LDS; side by side they would hold each other off until the bounded polls give up)
+        p->eng.back()->set("lu_large", 0);
         // pools (frontier waves, batched schedules, warm starts) keep the row limit of one-pass LDS staging: roots and children
         // beyond 8192 rows are refused as GOMILP_ERR_UNSUPPORTED
         p->eng.back()->limit_rows_to_lds_window();
@@ -245,6 +248,7 @@ int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value) {
         return GOMILP_OK;
     }
     if (std::string(key) == "large_loop") { pool->large_loop = value ? 1 : 0; return GOMILP_OK; }
+    if (std::string(key) == "lu_large") return GOMILP_OK;   // accepted, and left at 0 on the workers (gomilp_pool_create)
     if (std::string(key) == "sample_batch") {
         pool->sample_batch = value != 0;
         pool->batch->set_sampling(value != 0);

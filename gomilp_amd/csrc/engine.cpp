@@ -89,6 +89,7 @@ int Engine::set(const std::string &key, int64_t v) {
     else if (key == "sample_events") sample_events_ = v < 0 ? 0 : v;
     else if (key == "fused") fused_ = v ? 1 : 0;
     else if (key == "lu_look") lu_look_ = v ? 1 : 0;
+    else if (key == "lu_large") lu_large_ = v ? 1 : 0;
     else if (key == "lu_blocked") lu_blocked_ = v < 0 ? 0 : (v > 2 ? 3 : v);  // 0 per column, 1 blocked panels, 2 compressed rounds (slot panel), 3 the same with the look-ahead schedule (default; lu_compressed.hip)
     else if (key == "tableau") tableau_ = v ? 1 : 0;
     else if (key == "blocked") blocked_ = v ? 1 : 0;
@@ -874,7 +875,8 @@ int Engine::lu_factor(const Problem &P, bool *singular, const int32_t *basic_hos
     const double tf0 = now_s();
     const int m = P.m, ldw = P.ld;
     int nonunit = 0;
-    const bool compressed = lu_blocked_ >= 2 && lu_compressed_supported(m);
+    bool compressed = lu_blocked_ >= 2 && lu_compressed_supported(m, lu_large_ != 0);
+    const bool large = compressed && luc_large_rpt(m) > 0;   // knob lu_large: the compressed rounds beyond 4096 rows
     lu_cache_.valid = false;
     // the compressed schedule keeps L/U column-major (lu_compressed.hip), the other two row-major
     if (compressed != transpose) launch_luc_gather(P.dAt, P.ld, m, w.basic, w.W, ldw, stream_);
@@ -903,7 +905,7 @@ int Engine::lu_factor(const Problem &P, bool *singular, const int32_t *basic_hos
     for (int t = 0; t < 2; t++) { a.pk[t] = w.lpk[t]; a.pl[t] = w.lpl[t]; a.pr[t] = w.lpr[t]; }
     a.st = w.st;
     a.unit_row = w.unitrow;
-    const bool blocked = compressed || (lu_blocked_ && lu_blocked_supported(m));
+    bool blocked = compressed || (lu_blocked_ && lu_blocked_supported(m));
     a.dense_flag = blocked ? w.denseflag : nullptr;
     a.ctl = w.luctl; a.Lp = w.luLp; a.Up = w.luUp;
     // look-ahead schedule: where a factorization takes many rounds (measured: 2048 rows 23 rounds 2.20 -> 2.05 ms, 1000 rows 12 rounds
@@ -912,7 +914,7 @@ int Engine::lu_factor(const Problem &P, bool *singular, const int32_t *basic_hos
     // kernel, can hold each other's workgroups off the CUs until a wait gives up (measured: four metric LPs finishing together, two of
     // four factorizations fell back after ~50 ms).  So it runs only while this engine holds the device's loop slots, all of them, and
     // only if they are free right now; a pool's workers never ask (knob lu_look).
-    a.slots = 1; a.look = (lu_blocked_ >= 3 && lu_look_ && m > 768 && compressed) ? 1 : 0;
+    a.slots = 1; a.look = (lu_blocked_ >= 3 && lu_look_ && m > 768 && compressed && !large) ? 1 : 0;   // (beyond 4096 rows: the plain schedule, no loop slots taken)
     struct LookSlot {
         int dev; bool held;
         LookSlot(int d, bool want) : dev(d), held(want && Engine::loop_try_acquire_all(d)) {}
@@ -927,14 +929,17 @@ int Engine::lu_factor(const Problem &P, bool *singular, const int32_t *basic_hos
     // 1.40 / 1.41, 1536 rows 1.40 / 1.45, 1792 rows 1.74 / 1.81, 2048 rows 2.13 / 2.19; up to 1024 rows a step of 512 threads is cheaper
     // than the exchange: 1.17 / 1.10 ms)
     const int cross_mode = lu_cross_ >= 0 ? (int)lu_cross_ : ((m > 1280 && m <= 2048 && lu_look_) ? 2 : 0);
-    int cross_G = (cross_mode && compressed) ? luc_cross_groups(m, 1) : 0;
-    const int cross_slots = cross_mode == 2 ? 32 : 16;
+    // beyond 4096 rows (knob lu_large) that panel, several rows per lane on 8 workgroups, is the only one; lu_cross = 1 / 2 there name 16 / 32
+    // slots for the four-row instance (default 16 — measured at 4097 rows, 137 dense steps, 5 rounds either way: 1.4 ms against 2.1 ms with
+    // 32)
+    int cross_G = large ? 8 : ((cross_mode && compressed) ? luc_cross_groups(m, 1) : 0);
+    const int cross_slots = large ? (lu_cross_ == 2 ? 32 : 16) : (cross_mode == 2 ? 32 : 16);
     if (cross_G) {
         if (!w.luxrec) {
             HIP_TRY(dmalloc(&w.luxrec, luc_cross_doubles()));
             HIP_TRY(hipMemsetAsync(w.luxrec, 0, luc_cross_doubles() * sizeof(double), stream_));
         }
-        if (cross_mode != 2) { a.look = 0; look_slot.drop(); }
+        if (cross_mode != 2 || large) { a.look = 0; look_slot.drop(); }
     }
     a.ctl_prev = a.ctl; a.Lp_prev = a.Lp; a.Up_prev = a.Up;
     a.rowsnap = w.rowstep + w.cap_m; a.rowsnap_prev = a.rowsnap;   // (launch_luc_rounds sets the round's parity)
@@ -1024,8 +1029,10 @@ int Engine::lu_factor(const Problem &P, bool *singular, const int32_t *basic_hos
             // basis, with the whole update behind each panel
             // (the cross-workgroup panel under the look-ahead: first the same panel in the plain schedule — the rounds stay what they were —,
             // then, should its own exchange give up as well, the one-workgroup panel)
+            // (beyond 4096 rows there is no one-workgroup panel: one launch per column from the basis, in this call)
             if (attempt > 1 || !(a.look || cross_G)) return GOMILP_ERR_DEVICE;
             if (a.look) a.look = 0; else cross_G = 0;
+            if (large) { compressed = blocked = false; a.dense_flag = nullptr; }
             oneshot = false;
             lu_look_faults_++; lu_look_fault_++;
             if (w.luxrec) HIP_TRY(hipMemsetAsync(w.luxrec, 0, luc_cross_doubles() * sizeof(double), stream_));   // (a launch that gave up has not recorded how far its sequence numbers went)
@@ -1035,6 +1042,7 @@ int Engine::lu_factor(const Problem &P, bool *singular, const int32_t *basic_hos
                 if (transpose) HIP_TRY(hipMemsetAsync(w.W, 0, (size_t)m * ldw * sizeof(double), stream_));
                 launch_gather_w(P.dAt, P.ld, m, w.basic, w.W, ldw, stream_);
             }
+            if (!compressed) { lu_rounds_ = 0; sync_state_to_device(); launch_lu(a, stream_); launches_ += m + 2; break; }
         }
     } else if (blocked) launches_ += launch_lu_blocked(a, w.rho, stream_) + 1;
     else { launch_lu(a, stream_); launches_ += m + 2; }

@@ -224,6 +224,7 @@ class Engine {
     int64_t lu_look_faults_ = 0;   // final solves repeated with the plain schedule after a look-ahead launch gave up a wait
     int lu_look_fault_ = 0;        // ... in the running solve, one per fall-back (stats.device_retries)
     int64_t lu_look_ = 1;          // knob lu_look: 0 = never the look-ahead schedule (the workers of a pool)
+    int64_t lu_large_ = 0;         // knob lu_large: 1 = bases of 4097 .. 16384 rows take the compressed rounds on the eight-workgroup panel with several rows per lane (lu_cross.hip); 0 (default, and the workers of a pool) = one launch per column there
     int64_t chunk_ = 32, refresh_ = 0, trace_on_ = 0, max_pivots_ = 0, sample_events_ = 0, fused_ = 1, lu_blocked_ = 3, tableau_ = 1, blocked_ = 1, block_k_ = 0,  // block_k_ 0 = auto
             bt_nt_ = 0, bt_old_ = 0, bt_stamps_ = 0, bt_upd_valu_ = 0, bt_fault_ = 0, general_device_ = 1, general_block_ = 1, general_min_rows_ = 96, lu_cross_ = -1, bt_groups_ = 0,   // bt_groups_: -1 never, 0 by shape, 2 / 4 / 8 forced
             bt_lag_ = 1,       // persistent loop kernel where the multi-workgroup block kernel runs (0: block kernel + update launches)
@@ -324,6 +325,7 @@ int launch_luc_rounds_cross(const LUArgs &base, int32_t *pivrow, int nrounds, in
 size_t luc_cross_doubles();
 void launch_luc_lpos_final(const LUArgs &a, hipStream_t s);
 int luc_cross_groups(int m, int want);
+int luc_large_rpt(int m);   // rows per lane of the lu_large panel (0: m is outside 4097 .. 16384)
 int gs_scratch_rows();
 int gs_block_width(int m);
 int gs_block_scratch_rows();
@@ -399,7 +401,7 @@ void launch_lu(const LUArgs &a, hipStream_t s);
 bool lu_blocked_supported(int m);
 int launch_lu_blocked(const LUArgs &a, int32_t *pivrow, hipStream_t s);
 // lu_compressed.hip
-bool lu_compressed_supported(int m);
+bool lu_compressed_supported(int m, bool large);   // large: knob lu_large (4097 .. 16384 rows: lu_cross.hip luc_large_rpt)
 int lu_compressed_nb(int m, bool slots);
 void launch_luc_init(const LUArgs &a, hipStream_t s);
 int launch_luc_rounds(const LUArgs &a, int32_t *pivrow, int nrounds, int round_base, hipStream_t s);

@@ -705,14 +705,18 @@ static void luc_rounds_slots(const LUArgs &base, int32_t *pivrow, int nrounds, i
 
 // the rows of a round's panel on G workgroups of one XCD (lu_cross.hip, knob lu_cross) with 16 or 32 register slots: the plain schedule
 // with that panel, or (base.look, 32 slots) the look-ahead schedule with it — one launch per round, parities as in luc_rounds_slots
+// (bases beyond 4096 rows, knob lu_large: the eight-workgroup panel with several rows per lane, plain schedule only)
 void launch_luc_cross_panel(const LUArgs &a, int32_t *pivrow, double *xrec, int G, int slots, int nrole, hipStream_t s);
+void launch_luc_large_panel(const LUArgs &a, int32_t *pivrow, double *xrec, int slots, hipStream_t s);
+int luc_large_rpt(int m);
 int launch_luc_rounds_cross(const LUArgs &base, int32_t *pivrow, int nrounds, int round_base, double *xrec, int G, int slots, hipStream_t s) {
     const int m = base.m, nt = (m + 63) / 64;
     if (!base.look) {
         LUArgs a = base;
         a.ctl_prev = a.ctl; a.Lp_prev = a.Lp; a.Up_prev = a.Up; a.rowsnap_prev = a.rowsnap;
         for (int r = 0; r < nrounds; r++) {
-            launch_luc_cross_panel(a, pivrow, xrec, G, slots, 0, s);
+            if (luc_large_rpt(m)) launch_luc_large_panel(a, pivrow, xrec, slots, s);
+            else launch_luc_cross_panel(a, pivrow, xrec, G, slots, 0, s);
             hipLaunchKernelGGL((k_luc_usolve<kLucSlotSteps>), dim3(nt), dim3(256), 0, s, a);
             hipLaunchKernelGGL((k_luc_trail<kLucSlotSteps>), dim3(nt, nt), dim3(256), 0, s, a);
         }
@@ -736,7 +740,7 @@ int launch_luc_rounds_cross(const LUArgs &base, int32_t *pivrow, int nrounds, in
     return 3 * nrounds;
 }
 
-bool lu_compressed_supported(int m) { return m <= 4096; }
+bool lu_compressed_supported(int m, bool large) { return m <= 4096 || (large && luc_large_rpt(m) > 0); }   // (large: knob lu_large)
 // dense steps a round can take (the host sizes its batches of rounds with it)
 int lu_compressed_nb(int, bool) { return kLucSlotSteps; }
 

@@ -121,7 +121,11 @@ int gomilp_ctx_device(const gomilp_ctx *ctx);
  * per pivot — bit-identical pivots, measured slower: DESIGN.md section 2.1d); of the bit-exact final solve: "lu_blocked" (3 default: compressed rounds
  * in the look-ahead schedule — one launch per round, the panel beside the previous round's update — for bases beyond 768 rows while the
  * engine holds the device's loop slots, 2: compressed rounds with the whole update behind each panel, 1: blocked panels, 0: one launch per
- * column — all bit-identical), "lu_look" (0: never the look-ahead schedule; a pool sets it on its workers).  The
+ * column — all bit-identical), "lu_look" (0: never the look-ahead schedule; a pool sets it on its workers), "lu_large" (default 0;
+ * any non-zero value is 1: with "lu_blocked" >= 2 the bases of 4097 .. 16384 rows take the compressed rounds as well, in the plain schedule
+ * — three launches per round — on a panel of eight workgroups of one XCD with four (up to 8192 rows) or eight rows per lane, bit-identical
+ * to one launch per column; a panel exchange that gives up a wait falls back to one launch per column in the same call,
+ * stats.device_retries + 1; a pool accepts the knob and keeps it at 0 on its workers).  The
  * diagnostic flavour of the library (libgomilp_hip_debug.so, GOMILP_DEBUG_BUILD=1) adds "bt_fault" and the GOMILP_DEBUG_* / GOMILP_LUC_*
  * environment hooks; the product library has none of them.  Knobs that DO change what is decided, and how faithfully:
  * "exact_degenerate" (0 never, 1 default: bases of up to 256 rows, non-slack starts and badly scaled inputs, 2 always — degenerate,
@@ -150,7 +154,8 @@ int gomilp_ctx_device(const gomilp_ctx *ctx);
  * Warm starts on a context (gomilp_lp_solve_warm) work there too: the dual loop runs on the same chunked revised-simplex kernels.
  * Still GOMILP_ERR_UNSUPPORTED beyond 8192 rows: non-slack starts (equality rows, a supplied initial_basic, m >= n), frontier pools
  * (gomilp_pool_set_root, their waves and their warm starts), and exact_degenerate = 3 (the blocked tableau does not run there).  The final
- * solve of those bases takes the one-launch-per-column LU (k_lu_step): seconds, not milliseconds. */
+ * solve of the bases beyond 4096 rows takes the one-launch-per-column LU (k_lu_step): seconds, not milliseconds — unless "lu_large" is
+ * set, which gives the bases of 4097 .. 16384 rows the compressed rounds (beyond 16384 rows the knob changes nothing). */
 int gomilp_ctx_set(gomilp_ctx *ctx, const char *key, int64_t value);
 
 /* Upload a standard-form LP (row-major A, stride lda) and keep it resident.  Returns a problem id >= 0, or
