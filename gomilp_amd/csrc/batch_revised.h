@@ -14,16 +14,18 @@ namespace gomilp {
 enum : int32_t {
     RS_RUN = 0,    // set-up launches or a pivot loop are running
     RS_DONE = 1,   // terminal: `status` holds the outcome (GOMILP_OK / ERR_BLAND / ERR_UNSUPPORTED after Phase II: basis + x_B ready for the final solve)
-    RS_HOST = 2    // terminal: a branch the schedule leaves to a worker's whole solve (the |x_art| band, the zero-level artificial exchange)
+    RS_HOST = 2,   // terminal: a branch the schedule leaves to a worker's whole solve (the |x_art| band, the zero-level artificial exchange)
+    RS_COLD = 3    // a warm start that spent its dual-pivot budget: the host re-initialises the slot and the same run solves it cold
 };
 // RevLP::after: what k_rv_check does behind the set-up launches of a superstep
 enum : int32_t {
     RA_NONE = 0,
     RA_P1_LOOP = 1,   // the PANIC test of the Phase-I start, then the Phase-I loop
-    RA_P2_LOOP = 2    // the Phase-II loop
+    RA_P2_LOOP = 2,   // the Phase-II loop
+    RA_DUAL_LOOP = 3  // the dual loop of a warm start (DevState::max_pivots = the dual-pivot budget)
 };
 // RevLP::run: which launches of a superstep work on the relaxation
-enum : int32_t { RR_NONE = 0, RR_LOOP = 1, RR_FORCED = 2 };
+enum : int32_t { RR_NONE = 0, RR_LOOP = 1, RR_FORCED = 2, RR_DUAL = 3 };
 
 struct RevLP {
     // ---- fixed for the wave (written by the host) ----
@@ -60,12 +62,21 @@ struct RevLP {
     // ---- outcome ----
     int32_t status, wrapped, phase1_used, pad0;
     int64_t piv1, piv2, bland;
+    // ---- warm start (written by the host; behind the fields above, whose offsets the cold kernels' code keeps) ----
+    // warm != 0: the parent's kept state (mp x ldp B^-1, mp basis positions), the parent position of each of the J new rows' variables
+    // (-1: nonbasic there) and the rows' signs; k_rv_warm_binv builds the start, k_rv_init leaves the relaxation alone
+    const double *wbinv, *wsign;
+    const int32_t *wbasic, *wkpos;
+    int32_t warm, wJ, wmp, wldp;
+    int64_t dual_budget;
+    int64_t pivd;            // outcome: dual pivots
 };
 
 // what the host reads of every active relaxation after a superstep
 struct RevOut {
     int32_t stage, status, wrapped, phase1_used;
-    int64_t piv1, piv2, bland;
+    int64_t piv1, piv2, bland, pivd;
+    int32_t flips, dual;   // parity of the current B^-1 (the host keeps it for the children); 1: the dual loop runs or is ordered
 };
 
 // launches (batch_revised.hip).  act: list positions -> relaxation; nact entries.  gp / gr: workgroups per relaxation of the pricing
@@ -74,5 +85,11 @@ void launch_rv_init(RevLP *lps, int count, hipStream_t s);
 void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, hipStream_t s);   // forced pivot, lists, refresh, check: 7 launches
 void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, hipStream_t s);               // Bland step?, K1, K2, K3: 4 launches
 void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s);
+// warm starts: B^-1, basis list, b and the orders of every relaxation with warm != 0 (one launch for the wave, grid rows x count);
+// a dual pivot of the relaxations in the dual loop: leaving row, dual pricing, K2 / K3 in their kDualPick form (4 launches;
+// lds2: bytes of the TWO staged vectors of the pricing kernel, ld_max <= kRevDualLd)
+constexpr int kRevDualLd = 4096;
+void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s);
+void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, hipStream_t s);
 
 }  // namespace gomilp

@@ -59,6 +59,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_init(RevLP *lps) {
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
     RevLP *d = lps + blockIdx.x;
+    if (d->warm) return;   // k_rv_warm_binv starts it
     const int m = d->m, n = d->n, ld = d->ld, m0 = d->m0, K = d->K;
     const int32_t *rho0 = d->rho0;
     double *b = d->b, *xb = d->xb, *binv0 = d->binv[0], *c1 = d->c1;
@@ -109,7 +110,44 @@ __global__ __launch_bounds__(kBlock) void k_rv_init(RevLP *lps) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// K1-K3, relaxation = blockIdx.y.  MODE = RR_LOOP: a pivot of the loop; RR_FORCED: the forced pivot of the Phase-I set-up.
+// start of a warm relaxation from its parent's kept state (k_warm_binv of dual_kernels.hip per relaxation, Engine::warm_locked):
+//   B^-1 = [[B_p^-1, 0], [R, I_J]],  R[k, :] = -sign_k * B_p^-1[kpos_k, :] where var_k is basic at parent position kpos_k, else 0,
+// padding columns zero (the parent's ldp may differ from ld); the basis list is the parent's positions, then the slacks of the J new
+// rows (the last J columns); b' as k_rv_init; the orders: ascending nonbasic list of the n columns, x_B = B^-1 b and y = B^-T c_B
+// (the parent's y, zeros appended: dual feasible), then the dual loop.  grid: (rows of the tallest relaxation, relaxations).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_rv_warm_binv(RevLP *lps) {
+    RevLP *d = lps + blockIdx.y;
+    if (!d->warm) return;
+    const int i = blockIdx.x, m = d->m, n = d->n, ld = d->ld, mp = d->wmp, ldp = d->wldp, J = d->wJ;
+    if (i >= m) return;
+    const double *Bp = d->wbinv;
+    double *dst = d->binv[0] + (size_t)i * ld;
+    if (i < mp) {
+        const double *src = Bp + (size_t)i * ldp;
+        for (int c = threadIdx.x; c < ld; c += kBlock) dst[c] = c < mp ? src[c] : 0.0;
+    } else {
+        const int k = i - mp, pos = d->wkpos[k];
+        const double s = -d->wsign[k];
+        const double *src = pos >= 0 ? Bp + (size_t)pos * ldp : nullptr;
+        for (int c = threadIdx.x; c < ld; c += kBlock) dst[c] = c < mp ? (src ? s * src[c] : 0.0) : (c == i ? 1.0 : 0.0);
+    }
+    if (i != 0) return;
+    const int m0 = d->m0;
+    double *b = d->b;
+    int32_t *basic = d->basic;
+    const int32_t *wbasic = d->wbasic;
+    for (int r = threadIdx.x; r < ld; r += kBlock) b[r] = r < m0 ? d->b0[r] : (r < m ? d->rhs[r - m0] : 0.0);
+    for (int pos = threadIdx.x; pos < m; pos += kBlock) basic[pos] = pos < mp ? wbasic[pos] : n - J + (pos - mp);
+    if (threadIdx.x == 0) {
+        d->run = RR_NONE; d->do_lists = 2; d->do_refresh = 1; d->after = RA_DUAL_LOOP;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// K1-K3, relaxation = blockIdx.y.  MODE = RR_LOOP: a pivot of the loop; RR_FORCED: the forced pivot of the Phase-I set-up;
+// RR_DUAL (K2 / K3 only): a dual pivot of a warm start — the entering position from the partials of k_rv_dual_price, the leaving
+// row from the state (kDualPick).
 // The fields of the RevLP go into locals once (simplex_helpers.h: why the helpers take pointers).
 //
 // The Bland rule (Engine::host_bland; replaceBland, simplex.go:347-383) runs inside the loop: k_rv_bland, one small workgroup per
@@ -185,7 +223,9 @@ __global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, co
     if (d->run != MODE) return;
     DevState *st = d->st;
     const int m = d->m, ld = d->ld, flips = d->flips;
-    const int forced_pos = MODE == RR_FORCED ? d->f_pos : (d->bl ? d->bl_pos : -1), forced_var = MODE == RR_FORCED ? d->f_var : -1;
+    int forced_pos, forced_var;
+    if constexpr (MODE == RR_DUAL) { forced_pos = kDualPick; forced_var = -1; }
+    else { forced_pos = MODE == RR_FORCED ? d->f_pos : (d->bl ? d->bl_pos : -1); forced_var = MODE == RR_FORCED ? d->f_var : -1; }
     const double tol = d->tol;
     const double *At = d->At, *binv_cur = d->binv[flips & 1], *xb = d->xb;
     double *rvec = d->rvec, *dvec = d->dvec, *move = d->move;
@@ -239,7 +279,9 @@ __global__ __launch_bounds__(kBlock) void k_rv_update(RevLP *__restrict__ lps, c
     if (d->run != MODE) return;
     DevState *st = d->st;
     const int m = d->m, ld = d->ld, flips = d->flips_k2, phase = d->phase;
-    const int forced_p = MODE == RR_FORCED ? d->f_p : -1, no_swap = MODE == RR_FORCED ? d->f_noswap : 0, bland = MODE == RR_FORCED ? 0 : d->bl;
+    int forced_p, no_swap, bland;
+    if constexpr (MODE == RR_DUAL) { forced_p = kDualPick; no_swap = 0; bland = 0; }
+    else { forced_p = MODE == RR_FORCED ? d->f_p : -1; no_swap = MODE == RR_FORCED ? d->f_noswap : 0; bland = MODE == RR_FORCED ? 0 : d->bl; }
     const double *binv_cur = d->binv[flips & 1];
     double *binv_next = d->binv[(flips + 1) & 1];
     double *xb = d->xb, *y = d->y, *dvec = d->dvec, *move = d->move;
@@ -266,6 +308,73 @@ __global__ __launch_bounds__(kBlock) void k_rv_update(RevLP *__restrict__ lps, c
             if (bland) d->bland += 1;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// the dual loop of a warm start: k_dual_leave / k_dual_price of dual_kernels.hip with the relaxation as a grid dimension, in front of
+// k_rv_ftran<RR_DUAL> / k_rv_update<RR_DUAL>.  DevState::max_pivots holds the dual-pivot budget (k_rv_check).
+// ------------------------------------------------------------------------------------------------
+
+// leaving row: first index of min x_B, stop at >= -1e-13 (kDualFeasTol of engine_warm.cpp).  One workgroup per relaxation.
+__global__ __launch_bounds__(kBlock) void k_rv_dual_leave(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    const RevLP *d = lps + act[blockIdx.x];
+    if (d->run != RR_DUAL) return;
+    DevState *st = d->st;
+    if (st->done) return;
+    const int m = d->m;
+    const double *xb = d->xb;
+    unsigned long long bk = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int i = threadIdx.x; i < m; i += kBlock) amin_take(bk, bi, ordkey(xb[i]), (unsigned int)i);
+    block_argmin(bk, bi, sk, si);
+    if (threadIdx.x == 0) {
+        const double xmin = orddecode(bk);
+        if (!(xmin < -1e-13) || bi >= (unsigned int)m) { st->done = 1; st->status = ST_OPTIMAL; }
+        else if (st->max_pivots > 0 && st->pivots >= st->max_pivots) { st->done = 1; st->status = ST_MAX_PIVOTS; }
+        else st->p = (int)bi;
+    }
+}
+
+// dual pricing: per nonbasic column a_j.y and a_j.rho (rho = row p of B^-1), the row of At read once for both; r_pos = cost[j] - a_j.y
+// into rvec, the ratio r_j / -alpha_pj over alpha_pj < -1e-13 as a first-index argmin (k_dual_price's rule).  y and rho staged whole:
+// 2 * ld doubles of LDS, ld <= kRevDualLd.
+__global__ __launch_bounds__(kBlock) void k_rv_dual_price(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    const RevLP *d = lps + act[blockIdx.y];
+    if (d->run != RR_DUAL) return;
+    const DevState *st = d->st;
+    if (st->done) return;
+    const int ld = d->ld, nn = d->nn;
+    const double *At = d->At, *cost = d->cost;
+    double *rvec = d->rvec;
+    const int32_t *nonbasic = d->nonbasic;
+    unsigned long long *pk = d->pk_price;
+    unsigned int *pi = d->pi_price;
+    const int ld2 = ld >> 1;
+    double2 *sy = svec, *sr = svec + ld2;
+    const double2 *y2 = reinterpret_cast<const double2 *>(d->y);
+    const double2 *rho2 = reinterpret_cast<const double2 *>(d->binv[d->flips & 1] + (size_t)st->p * ld);
+    for (int c = threadIdx.x; c < ld2; c += kBlock) { sy[c] = y2[c]; sr[c] = rho2[c]; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    unsigned long long bk = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int pos = wave; pos < nn; pos += nwaves) {
+        const int j = nonbasic[pos];
+        DotAcc acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        wave_dot_chunk<2>(At + (size_t)j * ld, svec, ld2, 0, ld2, ld2, lane, acc);
+        const double dy = wave_dot_finish(acc[0]), da = wave_dot_finish(acc[1]);
+        const double r = cost[j] - dy;
+        if (lane == 0) rvec[pos] = r;
+        amin_take(bk, bi, ordkey(da < -1e-13 ? r / (-da) : __builtin_inf()), (unsigned int)pos);
+    }
+    publish_partials(bk, bi, sk, si, pk, pi);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -378,11 +487,14 @@ __global__ __launch_bounds__(kBlock) void k_rv_check(RevLP *__restrict__ lps, co
         if (after == RA_P1_LOOP) {
             start_loop_state(st, d->max_pivots);
             d->phase = 1; d->nn = n + 1 - m; d->tol = 1e-10; d->cost = d->c1;
+        } else if (after == RA_DUAL_LOOP) {
+            start_loop_state(st, d->dual_budget);
+            d->phase = 3; d->nn = n - m; d->tol = d->tol_user; d->cost = d->c2;
         } else {
             start_loop_state(st, d->max_pivots);
             d->phase = 2; d->nn = n - m; d->tol = d->tol_user; d->cost = d->c2;
         }
-        d->run = RR_LOOP;
+        d->run = after == RA_DUAL_LOOP ? RR_DUAL : RR_LOOP;
         clear_orders(d);
     }
 }
@@ -440,11 +552,23 @@ __global__ __launch_bounds__(kBlock) void k_rv_ctrl(RevLP *__restrict__ lps, con
             }
         }
     }
+    // a dual loop that stopped (Engine::run_dual_loop's verdicts): primal feasible — the orders of a Phase-II start (ascending list,
+    // fresh x_B / y: the "finish" of Engine::warm_locked); no ratio in the leaving row — the LP is infeasible, no x; the budget spent —
+    // RS_COLD: the host re-initialises the slot and this run solves it cold
+    if (d->stage == RS_RUN && d->run == RR_DUAL && st->done != 0 && threadIdx.x == 0) {
+        const int status = st->status;
+        d->pivd = st->pivots; d->run = RR_NONE;
+        if (status == ST_OPTIMAL) { d->do_lists = 2; d->do_refresh = 1; d->after = RA_P2_LOOP; }
+        else if (status == ST_DUAL_INFEASIBLE) { d->status = GOMILP_ERR_INFEASIBLE; d->stage = RS_DONE; }
+        else if (status == ST_MAX_PIVOTS) d->stage = RS_COLD;
+        else { d->status = GOMILP_ERR_DEVICE; d->stage = RS_DONE; }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         RevOut o;
         o.stage = d->stage; o.status = d->status; o.wrapped = d->wrapped; o.phase1_used = d->phase1_used;
-        o.piv1 = d->piv1; o.piv2 = d->piv2; o.bland = d->bland;
+        o.piv1 = d->piv1; o.piv2 = d->piv2; o.bland = d->bland; o.pivd = d->pivd;
+        o.flips = d->flips; o.dual = (d->run == RR_DUAL || d->after == RA_DUAL_LOOP) ? 1 : 0;
         out[id] = o;
     }
 }
@@ -472,6 +596,15 @@ void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_
 }
 void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_ctrl, dim3(nact), dim3(kBlock), 0, s, lps, act, out);
+}
+void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s) {
+    hipLaunchKernelGGL(k_rv_warm_binv, dim3(m_max, count), dim3(kBlock), 0, s, lps);
+}
+void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, hipStream_t s) {
+    hipLaunchKernelGGL(k_rv_dual_leave, dim3(nact), dim3(kBlock), 0, s, lps, act);
+    hipLaunchKernelGGL(k_rv_dual_price, dim3(gp, nact), dim3(kBlock), lds2, s, lps, act);
+    hipLaunchKernelGGL(k_rv_ftran<RR_DUAL>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp);
+    hipLaunchKernelGGL(k_rv_update<RR_DUAL>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
 }
 
 }  // namespace gomilp

@@ -54,6 +54,8 @@ struct gomilp_pool {
                                 // raise the latency of every chain's agent-scope reads and polls
     int batch_revised = 1;      // knob: wide waves (n - m >= 2m) that the workers would run on the unguarded revised pipelines take the
                                 // device-batched revised simplex (engine_batch_revised.hpp); 0: every such wave on the workers
+    int warm_revised = 0;       // knob (opt-in): a gomilp_frontier_solve_warm call whose wave passes the wide routing test runs on the batched
+                                // revised simplex too, with warm starts and keeping; 0: such a call goes to the workers, cold
     int64_t refresh = 0, max_pivots = 0;   // the workers' knobs of these names, as the batched revised simplex needs them
     std::unique_ptr<RevBatchEngine> rev;   // created on first use
     gomilp::WarmStore warm;     // final states kept for warm starts (gomilp_frontier_solve_warm), shared by both schedules
@@ -224,6 +226,7 @@ int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value) {
     std::lock_guard<std::mutex> g(pool->call_mu);
     if (std::string(key) == "batched") { pool->batched = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "batch_revised") { pool->batch_revised = value ? 1 : 0; return GOMILP_OK; }
+    if (std::string(key) == "warm_revised") { pool->warm_revised = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "split_large") { pool->split_large = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "split_phase") { pool->split_phase = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "batch_virt") {   // wide waves on virtual tableaus for their first block (default 1)
@@ -419,9 +422,10 @@ static int frontier_solve_impl(gomilp_pool *pool, int64_t count, const int32_t *
         if (use_batch && pool->large_loop && need > 1024 && need <= 2048) use_batch = false;
     }
     // Wide waves: the device-batched revised simplex, where every relaxation of the wave is one that a worker's Engine::solve runs on the
-    // revised pipelines without the exact-step guard (one root, cold, slack starts; a periodic refresh stays on the workers)
+    // revised pipelines without the exact-step guard (one root, slack starts; a periodic refresh stays on the workers).  Cold calls, and
+    // with the knob warm_revised the warm call: relaxations whose parent's kept state is of this schedule start from it (section 2.6b)
     bool use_rev = false;
-    if (!use_batch && pool->batched && pool->batch_revised && count > 0 && !wa && nroots == 1 && pool->refresh == 0) {
+    if (!use_batch && pool->batched && pool->batch_revised && count > 0 && (!wa || pool->warm_revised) && nroots == 1 && pool->refresh == 0) {
         int K_min = K_max;
         for (int64_t i = 0; i < count; i++) K_min = std::min<int>(K_min, (int)(koff[i + 1] - koff[i]));
         use_rev = RevBatchEngine::eligible(pool->view, K_min, K_max, pool->exact_degenerate, pool->cond_guard);
@@ -432,6 +436,8 @@ static int frontier_solve_impl(gomilp_pool *pool, int64_t count, const int32_t *
     if (use_rev) {
         if (!pool->rev) pool->rev.reset(new RevBatchEngine(pool->device));
         auto on_done = [&](int64_t i, const BatchEngine::Outcome &o, const int32_t *basic, const double *xb) {   // (called on this thread)
+            if (o.warm) { agg.warm_started++; agg.pivots_dual += o.pivd; }
+            if (o.stage == gomilp::BS_COLD) { agg.warm_fallbacks++; return; }   // (the schedule solves it cold in the same run and reports it again)
             if (o.stage != gomilp::BS_DONE) {   // the |x_art| band, the zero-level artificial exchange
                 agg.host_fallbacks++;
                 pool->submit([&full_solve, i](int w) { full_solve(w, i); });
@@ -449,10 +455,14 @@ static int frontier_solve_impl(gomilp_pool *pool, int64_t count, const int32_t *
         };
         RevBatchEngine::Stats rs;
         bool fits = true;
-        const int rc = pool->rev->run(pool->view, count, koff, var, sign, rhs, tol, pool->max_pivots, on_done, &rs, &fits);
+        gomilp::WarmSpec wspec;
+        if (wa) {
+            wspec.store = &pool->warm; wspec.parent = wa->parent; wspec.tag = wa->tag; wspec.keep = wa->keep; wspec.dual_budget = wa->budget;
+        }
+        const int rc = pool->rev->run(pool->view, count, koff, var, sign, rhs, tol, pool->max_pivots, on_done, &rs, &fits, wa ? &wspec : nullptr);
         pool->drain();
         if (rc != GOMILP_OK) return rc;
-        if (fits) { bs.launches = rs.launches; bs.supersteps = rs.supersteps; bs.seconds_total = rs.seconds_total; }
+        if (fits) { bs.launches = rs.launches; bs.supersteps = rs.supersteps; bs.seconds_total = rs.seconds_total; bs.warm_kept = rs.warm_kept; }
         else use_rev = false;   // the wave's buffers do not fit the free device memory: the workers take it, whole
     }
     if (use_rev) {
@@ -548,7 +558,7 @@ static int frontier_solve_impl(gomilp_pool *pool, int64_t count, const int32_t *
         if (wa) {
             std::vector<int64_t> warm_idx;
             for (int64_t i = 0; i < count; i++) {
-                const bool w = wa->parent && wa->parent[i] >= 0 && koff[i + 1] - koff[i] >= 1 && pool->warm.find(wa->parent[i]) != nullptr;
+                const bool w = wa->parent && wa->parent[i] >= 0 && koff[i + 1] - koff[i] >= 1 && [&] { auto e = pool->warm.find(wa->parent[i]); return e && e->kind == gomilp::WK_TABLEAU; }();
                 (w ? warm_idx : cold_idx).push_back(i);
             }
             subset = true;

@@ -58,6 +58,30 @@ std::shared_ptr<WarmEntry> WarmStore::acquire(int m4, int ldt, int m, int nn, in
         bmalloc(&e->nonbasic, e->cap_nn) != hipSuccess || bmalloc(&e->posvar, e->cap_n) != hipSuccess) return nullptr;
     return e;
 }
+std::shared_ptr<WarmEntry> WarmStore::acquire_revised(int m, int ld) {
+    const size_t need_t = (size_t)m * ld;
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        for (size_t i = 0; i < free_.size(); i++) {
+            WarmEntry &e = *free_[i];
+            if (e.cap_t >= need_t && e.cap_m >= (size_t)m) {
+                auto r = free_[i];
+                free_[i] = free_.back();
+                free_.pop_back();
+                return r;
+            }
+        }
+    }
+    std::shared_ptr<WarmEntry> e(new WarmEntry);
+    // head-room as in acquire: a few levels of taller children fit a recycled entry
+    const size_t cap_t = (size_t)(m + 32) * (size_t)(ld + 32), cap_m = (size_t)m + 32;
+    const size_t grow = cap_t * sizeof(double) + cap_m * sizeof(int32_t);
+    size_t avail = 0, total = 0;
+    if (hipMemGetInfo(&avail, &total) != hipSuccess || grow + grow / 16 + ((size_t)256 << 20) > avail) return nullptr;
+    if (bmalloc(&e->T, cap_t) != hipSuccess || bmalloc(&e->basic, cap_m) != hipSuccess) return nullptr;
+    e->cap_t = cap_t; e->cap_m = cap_m;
+    return e;
+}
 void WarmStore::put(int64_t tag, std::shared_ptr<WarmEntry> e) {
     std::lock_guard<std::mutex> g(mu_);
     auto it = by_tag_.find(tag);
@@ -327,7 +351,7 @@ int BatchEngine::run_roots(const Engine::RootView *const *roots, int nroots, con
         if (warm && warm->store && warm->start_warm && warm->parent && warm->parent[i] >= 0 && K >= 1 && R.unit_basis && !lp.gen && kb == 8) {
             std::shared_ptr<WarmEntry> e = warm->store->find(warm->parent[i]);
             // the parent must be this relaxation minus its last branch row, solved on the same root data
-            if (e && e->m + 1 == lp.m && e->n + 1 == lp.n && e->K + 1 == K && e->root_serial == R.serial && e->ldt == batch_ldt(lp.n - lp.m)) {
+            if (e && e->kind == WK_TABLEAU && e->m + 1 == lp.m && e->n + 1 == lp.n && e->K + 1 == K && e->root_serial == R.serial && e->ldt == batch_ldt(lp.n - lp.m)) {
                 lp.warm = 1; lp.wm = e->m;
                 lp.wT = e->T; lp.wxb = e->xb; lp.wbasic = e->basic; lp.wnonbasic = e->nonbasic; lp.wposvar = e->posvar;
                 lp.dual_budget = warm->dual_budget > 0 ? warm->dual_budget : 64;
@@ -492,6 +516,7 @@ int BatchEngine::run_roots(const Engine::RootView *const *roots, int nroots, con
                     const int nn_i = hl.n - hl.m, ldt_i = batch_ldt(nn_i), m4_i = (hl.m + 3) & ~3;
                     std::shared_ptr<WarmEntry> e = warm->store->acquire(m4_i, ldt_i, hl.m, nn_i, hl.n);
                     if (e) {
+                        e->kind = WK_TABLEAU;
                         e->m = hl.m; e->n = hl.n; e->nn = nn_i; e->ldt = ldt_i; e->K = hl.K;
                         e->root_serial = roots[root_of ? root_of[i] : 0]->serial;
                         const double *Tsrc = (lp.tcur & 1) ? hl.T[1] : hl.T[0];

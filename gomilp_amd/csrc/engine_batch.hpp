@@ -17,8 +17,16 @@ namespace gomilp {
 // initialBasic, simplex.go:147-161): final states of relaxations the caller asked to keep, by caller-chosen tag (the B&B node id).  A
 // later relaxation that names such a tag as its parent and carries ONE more branch row starts from that basis (batch_kernels.hip
 // k_b_setup_warm).  Shared by the schedules of a pool; entries are recycled through a free list.
+// Two kinds, and each schedule starts only from its own: WK_TABLEAU (BatchEngine: the final tableau, x_B, the index lists) and WK_REVISED
+// (RevBatchEngine, DESIGN.md §2.6b: T holds the final B^-1, m x ld, basic the positional basis list, on the host too; the K branch
+// triples of the relaxation, for the prefix test of a descendant).  A parent of the other kind is no parent: the relaxation starts cold.
+enum : int { WK_TABLEAU = 0, WK_REVISED = 1 };
 struct WarmEntry {
+    int kind = WK_TABLEAU;
     int m = 0, n = 0, nn = 0, ldt = 0, K = 0;
+    int ld = 0;                                                      // WK_REVISED: row stride of B^-1
+    std::vector<int32_t> hbasic, kvar;                               // WK_REVISED: basic on the host, the branch triples
+    std::vector<double> ksign, krhs;
     uint64_t root_serial = 0;
     double *T = nullptr, *xb = nullptr;                              // tableau (4x4 tiles, m4 x ldt), updated x_B
     int32_t *basic = nullptr, *nonbasic = nullptr, *posvar = nullptr;
@@ -30,6 +38,9 @@ class WarmStore {
     std::shared_ptr<WarmEntry> find(int64_t tag);
     // an entry with room for the given shape (recycled or new; nullptr: out of device memory)
     std::shared_ptr<WarmEntry> acquire(int m4, int ldt, int m, int nn, int n);
+    // a WK_REVISED entry with room for an m x ld B^-1 and m basis positions (recycled, or new where the device memory has the head-room
+    // of RevBatchEngine::run; nullptr: the state is not kept)
+    std::shared_ptr<WarmEntry> acquire_revised(int m, int ld);
     void put(int64_t tag, std::shared_ptr<WarmEntry> e);
     void release(int64_t tag);
     void clear();

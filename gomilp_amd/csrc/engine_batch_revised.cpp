@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <vector>
 
 #include "batch_revised.h"
@@ -71,7 +72,8 @@ bool RevBatchEngine::eligible(const Engine::RootView &R, int K_min, int K_max, i
 }
 
 int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t *koff, const int32_t *var, const double *sign,
-                        const double *rhs, double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits) {
+                        const double *rhs, double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits,
+                        const WarmSpec *warm) {
     const auto t0 = std::chrono::steady_clock::now();
     *fits = true;
     if (count <= 0) return GOMILP_OK;
@@ -84,8 +86,33 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
     for (int64_t i = 0; i < count; i++) K_max = std::max<int>(K_max, (int)(koff[i + 1] - koff[i]));
     const int m_max = m0 + K_max, n_max = n0 + K_max, ld_max = (m_max + 1) & ~1;
 
+    // ---- warm starts: the kept WK_REVISED state that parent[i] names, where this relaxation's rows extend its rows (bitwise prefix) by J >= 1
+    struct Plan { std::shared_ptr<WarmEntry> e; int J = 0; size_t kp = 0; };
+    std::vector<Plan> plan((size_t)count);
+    size_t wj_tot = 0;
+    int64_t nwarm = 0;
+    if (warm && warm->store && warm->start_warm && warm->parent && ld_max <= kRevDualLd) {
+        for (int64_t i = 0; i < count; i++) {
+            const int K = (int)(koff[i + 1] - koff[i]);
+            if (warm->parent[i] < 0 || K < 1) continue;
+            std::shared_ptr<WarmEntry> e = warm->store->find(warm->parent[i]);
+            if (!e || e->kind != WK_REVISED || e->root_serial != R.serial || e->K >= K || e->m != m0 + e->K || e->n != n0 + e->K ||
+                (int)e->hbasic.size() != e->m || (int)e->kvar.size() != e->K) continue;
+            const int64_t k0 = koff[i];
+            bool prefix = true;
+            for (int k = 0; k < e->K && prefix; k++)
+                prefix = var[k0 + k] == e->kvar[(size_t)k] && memcmp(&sign[k0 + k], &e->ksign[(size_t)k], sizeof(double)) == 0 &&
+                         memcmp(&rhs[k0 + k], &e->krhs[(size_t)k], sizeof(double)) == 0;
+            if (!prefix) continue;
+            Plan &P = plan[(size_t)i];
+            P.e = e; P.J = K - e->K; P.kp = wj_tot;
+            wj_tot += (size_t)P.J;
+            nwarm++;
+        }
+    }
+
     // ---- layout: per relaxation, offsets into the two arenas (doubles; every buffer 16-byte aligned) ----
-    struct Lay { size_t at, binv0, binv1, xb, y, dvec, move, bb, rvec, c1, ysc, basic, nonbasic, inb, pkp, pkr, pip, pir, st; };
+    struct Lay { size_t wk0, wk1; size_t at, binv0, binv1, xb, y, dvec, move, bb, rvec, c1, ysc, basic, nonbasic, inb, pkp, pkr, pip, pir, st; };
     std::vector<Lay> lay((size_t)count);
     size_t at_tot = 0, wk_tot = 0;
     for (int64_t i = 0; i < count; i++) {
@@ -93,15 +120,17 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
         Lay &L = lay[(size_t)i];
         L.at = at_tot; at_tot += (size_t)(n + 1) * ld;
         auto take = [&](size_t doubles) { const size_t o = wk_tot; wk_tot += even(doubles); return o; };
+        L.wk0 = wk_tot;
         L.binv0 = take((size_t)m * ld); L.binv1 = take((size_t)m * ld);
         L.xb = take(ld); L.y = take(ld); L.dvec = take(ld); L.move = take(ld); L.bb = take(ld);
         L.rvec = take((size_t)n + 1 - m); L.c1 = take((size_t)n + 1); L.ysc = take((size_t)64 * ld);
         L.basic = take(((size_t)ld + 1) / 2); L.nonbasic = take(((size_t)n + 2 - m + 1) / 2); L.inb = take(((size_t)n + 2 + 1) / 2);
         L.pkp = take(kMaxPartials); L.pkr = take(kMaxPartials); L.pip = take(kMaxPartials / 2); L.pir = take(kMaxPartials / 2);
         L.st = take((sizeof(DevState) + 7) / 8);
+        L.wk1 = wk_tot;
     }
     const size_t k_doubles = even((size_t)2 * ktot + 2) + even((size_t)m0) + even((size_t)n_max + 2);
-    const size_t k_tot = k_doubles + ((size_t)ktot + 1 + (size_t)m0 + 1) / 2 + 2;
+    const size_t k_tot = k_doubles + ((size_t)ktot + 1 + (size_t)m0 + 1 + wj_tot + 1) / 2 + 2;
     // ---- what has to grow must fit the free device memory (with the head-room of Engine::device_fits): else the wave goes to the workers
     {
         size_t grow = 0;
@@ -148,15 +177,26 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
         b.cap_h = (size_t)count * ld_max;
     }
 
-    // ---- the wave's shared data: sign | rhs | b0 | c2, var | rho0 ----
+    // ---- the wave's shared data: sign | rhs | b0 | c2, var | rho0 | kpos (parent position of each new row's variable, warm starts) ----
     std::vector<double> hk(k_tot, 0.0);
     double *h_sign = hk.data(), *h_rhs = h_sign + ktot, *h_b0 = hk.data() + even((size_t)2 * ktot + 2), *h_c2 = h_b0 + even((size_t)m0);
-    int32_t *h_var = reinterpret_cast<int32_t *>(hk.data() + k_doubles), *h_rho = h_var + ktot + 1;
+    int32_t *h_var = reinterpret_cast<int32_t *>(hk.data() + k_doubles), *h_rho = h_var + ktot + 1, *h_kpos = h_rho + m0 + 1;
     for (int64_t k = 0; k < ktot; k++) { h_sign[k] = sign[k_base + k]; h_rhs[k] = rhs[k_base + k]; h_var[k] = var[k_base + k]; }
     for (int i = 0; i < m0; i++) { h_b0[i] = R.hb[(size_t)i]; h_rho[i] = R.rho0[(size_t)i]; }
     for (int j = 0; j < n0; j++) h_c2[j] = R.hc[(size_t)j];   // c' = [c, 0] (subproblem.go:110-114)
+    for (int64_t i = 0; i < count && nwarm; i++) {
+        const Plan &P = plan[(size_t)i];
+        if (!P.e) continue;
+        const int K = (int)(koff[i + 1] - koff[i]);
+        for (int k = 0; k < P.J; k++) {
+            const int32_t v = var[koff[i] + K - P.J + k];
+            int32_t pos = -1;
+            for (int q = 0; q < P.e->m; q++) if (P.e->hbasic[(size_t)q] == v) { pos = q; break; }
+            h_kpos[P.kp + (size_t)k] = pos;
+        }
+    }
     double *d_sign = b.d_k, *d_rhs = d_sign + ktot, *d_b0 = b.d_k + (h_b0 - hk.data()), *d_c2 = b.d_k + (h_c2 - hk.data());
-    int32_t *d_var = reinterpret_cast<int32_t *>(b.d_k + k_doubles), *d_rho = d_var + ktot + 1;
+    int32_t *d_var = reinterpret_cast<int32_t *>(b.d_k + k_doubles), *d_rho = d_var + ktot + 1, *d_kpos = d_rho + m0 + 1;
     RV_TRY(hipMemcpyAsync(b.d_k, hk.data(), k_tot * sizeof(double), hipMemcpyHostToDevice, stream_));
 
     std::vector<RevLP> lps((size_t)count);
@@ -178,6 +218,12 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
         d.m0 = m0; d.n0 = n0; d.K = K; d.m = m; d.n = n; d.ld = ld;
         d.max_pivots = max_pivots; d.tol_user = tol;
         d.stage = RS_RUN; d.run = RR_NONE; d.cost = d_c2; d.f_var = d.f_pos = d.f_p = -1;
+        const Plan &P = plan[(size_t)i];
+        if (P.e) {
+            d.warm = 1; d.wJ = P.J; d.wmp = P.e->m; d.wldp = P.e->ld;
+            d.wbinv = P.e->T; d.wbasic = P.e->basic; d.wkpos = d_kpos + P.kp; d.wsign = d_sign + (koff[i] - k_base) + (K - P.J);
+            d.dual_budget = warm->dual_budget > 0 ? warm->dual_budget : 64;
+        }
     }
     RV_TRY(hipMemcpyAsync(b.d_lps, lps.data(), (size_t)count * sizeof(RevLP), hipMemcpyHostToDevice, stream_));
     RV_TRY(hipMemsetAsync(b.d_work, 0, wk_tot * sizeof(double), stream_));
@@ -188,6 +234,7 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
     }
     launch_rv_init(b.d_lps, (int)count, stream_);
     launches += count + 1;
+    if (nwarm) { launch_rv_warm_binv(b.d_lps, (int)count, m_max, stream_); launches++; }
     RV_TRY(hipStreamSynchronize(stream_));   // (the pageable staging vectors go out of use here)
     RV_TRY(hipGetLastError());
 
@@ -195,18 +242,28 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
     const int gp = grid_for_rows(n_max + 1 - m0), gr = grid_for_rows(m_max);
     const size_t lds = (size_t)ld_max * sizeof(double);
     std::vector<int> act((size_t)count), done_now;
-    for (int64_t i = 0; i < count; i++) act[(size_t)i] = (int)i;
+    std::vector<char> is_warm((size_t)count, 0), in_dual((size_t)count, 0);   // started warm (and still is) / the dual loop runs or is ordered
+    for (int64_t i = 0; i < count; i++) { act[(size_t)i] = (int)i; is_warm[(size_t)i] = in_dual[(size_t)i] = plan[(size_t)i].e ? 1 : 0; }
+    struct Keep { int id; std::shared_ptr<WarmEntry> e; };
+    std::vector<Keep> keeps;
+    int64_t kept = 0;
     int64_t steps = 0;
     int rc = GOMILP_OK;
     while (!act.empty()) {
         const int nact = (int)act.size();
         memcpy(b.h_act, act.data(), (size_t)nact * sizeof(int));
         RV_TRY(hipMemcpyAsync(b.d_act, b.h_act, (size_t)nact * sizeof(int), hipMemcpyHostToDevice, stream_));
+        // (the dual launches only while some active relaxation is in the dual stage: a cold wave's list is setup, chunk x pivot, ctrl)
+        bool any_dual = false, any_primal = false;
+        for (int id : act) (in_dual[(size_t)id] ? any_dual : any_primal) = true;
         launch_rv_setup(b.d_lps, b.d_act, nact, gr, ld_max, lds, stream_);
         const int chunk = steps < 2 ? kFirstChunk : kChunk;
-        for (int t = 0; t < chunk; t++) launch_rv_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, stream_);
+        for (int t = 0; t < chunk; t++) {
+            if (any_dual) launch_rv_dual_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, 2 * lds, stream_);
+            if (any_primal) launch_rv_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, stream_);
+        }
         launch_rv_ctrl(b.d_lps, b.d_act, nact, b.d_out, stream_);
-        launches += 7 + 4 * chunk + 1;
+        launches += 7 + 4 * chunk * ((any_dual ? 1 : 0) + (any_primal ? 1 : 0)) + 1;
         RV_TRY(hipMemcpyAsync(b.h_out, b.d_out, (size_t)count * sizeof(RevOut), hipMemcpyDeviceToHost, stream_));
         RV_TRY(hipStreamSynchronize(stream_));
         RV_TRY(hipGetLastError());
@@ -214,31 +271,71 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
         done_now.clear();
         std::vector<int> next;
         bool copies = false;
+        keeps.clear();
         for (int id : act) {
             const RevOut &o = b.h_out[id];
+            in_dual[(size_t)id] = o.dual ? 1 : 0;
             if (o.stage == RS_RUN) { next.push_back(id); continue; }
+            if (o.stage == RS_COLD) {
+                // the dual budget is spent: reported as a fallback, then the slot starts again from its slack basis — its work area zeroed, its
+                // RevLP as the wave's first upload but cold, its assembled At as it is — and runs through the following supersteps
+                BatchEngine::Outcome oc;
+                oc.stage = BS_COLD; oc.warm = 1; oc.pivd = o.pivd;
+                on_done(id, oc, nullptr, nullptr);
+                RevLP &d = lps[(size_t)id];
+                const Lay &L = lay[(size_t)id];
+                d.warm = 0;
+                is_warm[(size_t)id] = 0; in_dual[(size_t)id] = 0;
+                RV_TRY(hipMemsetAsync(b.d_work + L.wk0, 0, (L.wk1 - L.wk0) * sizeof(double), stream_));
+                RV_TRY(hipMemcpyAsync(b.d_lps + id, &d, sizeof(RevLP), hipMemcpyHostToDevice, stream_));
+                launch_rv_init(b.d_lps + id, 1, stream_);
+                launches++;
+                next.push_back(id);
+                continue;
+            }
             done_now.push_back(id);
             if (o.stage == RS_DONE && (o.status == GOMILP_OK || o.status == GOMILP_ERR_BLAND || o.status == GOMILP_ERR_UNSUPPORTED)) {
                 const RevLP &d = lps[(size_t)id];
                 RV_TRY(hipMemcpyAsync(b.h_basic + (size_t)id * ld_max, d.basic, (size_t)d.m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
                 RV_TRY(hipMemcpyAsync(b.h_xb + (size_t)id * ld_max, d.xb, (size_t)d.m * sizeof(double), hipMemcpyDeviceToHost, stream_));
                 copies = true;
+                if (o.status == GOMILP_OK && warm && warm->store && warm->keep && warm->tag && warm->keep[id] && warm->tag[id] >= 0) {
+                    // kept for its children: the current B^-1 and the basis list, device to device on this stream (the slot is terminal:
+                    // nothing writes its buffers before the next run, which starts behind this stream)
+                    std::shared_ptr<WarmEntry> e = warm->store->acquire_revised(d.m, d.ld);
+                    if (e) {
+                        RV_TRY(hipMemcpyAsync(e->T, d.binv[o.flips & 1], (size_t)d.m * d.ld * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+                        RV_TRY(hipMemcpyAsync(e->basic, d.basic, (size_t)d.m * sizeof(int32_t), hipMemcpyDeviceToDevice, stream_));
+                        keeps.push_back({id, e});
+                    }
+                }
             }
         }
         if (copies) RV_TRY(hipStreamSynchronize(stream_));
+        for (const Keep &kp : keeps) {
+            const RevLP &d = lps[(size_t)kp.id];
+            WarmEntry &e = *kp.e;
+            const int64_t k0 = koff[kp.id];
+            e.kind = WK_REVISED; e.m = d.m; e.n = d.n; e.ld = d.ld; e.K = d.K; e.nn = 0; e.ldt = 0;
+            e.root_serial = R.serial;
+            e.hbasic.assign(b.h_basic + (size_t)kp.id * ld_max, b.h_basic + (size_t)kp.id * ld_max + d.m);
+            e.kvar.assign(var + k0, var + k0 + d.K); e.ksign.assign(sign + k0, sign + k0 + d.K); e.krhs.assign(rhs + k0, rhs + k0 + d.K);
+            warm->store->put(warm->tag[kp.id], kp.e);
+            kept++;
+        }
         for (int id : done_now) {
             const RevOut &o = b.h_out[id];
             BatchEngine::Outcome oc;
             oc.stage = o.stage == RS_DONE ? BS_DONE : BS_HOST;
             oc.status = o.status; oc.wrapped = o.wrapped; oc.phase1_used = o.phase1_used;
-            oc.piv1 = o.piv1; oc.piv2 = o.piv2; oc.bland = o.bland;
+            oc.piv1 = o.piv1; oc.piv2 = o.piv2; oc.bland = o.bland; oc.pivd = o.pivd; oc.warm = is_warm[(size_t)id];
             const bool fin = oc.stage == BS_DONE && (o.status == GOMILP_OK || o.status == GOMILP_ERR_BLAND || o.status == GOMILP_ERR_UNSUPPORTED);
             on_done(id, oc, fin ? b.h_basic + (size_t)id * ld_max : nullptr, fin ? b.h_xb + (size_t)id * ld_max : nullptr);
         }
         act.swap(next);
     }
     if (stats) {
-        stats->launches = launches; stats->supersteps = steps;
+        stats->launches = launches; stats->supersteps = steps; stats->warm_kept = kept;
         stats->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
     return rc;

@@ -14,7 +14,7 @@ namespace gomilp {
 class RevBatchEngine {
    public:
     struct Stats {
-        int64_t launches = 0, supersteps = 0;
+        int64_t launches = 0, supersteps = 0, warm_kept = 0;
         double seconds_total = 0;
     };
     explicit RevBatchEngine(int device);
@@ -25,8 +25,14 @@ class RevBatchEngine {
     // The wave (children of R; relaxation i has rows koff[i]..koff[i+1] of var / sign / rhs).  on_done as BatchEngine::run_roots: stage
     // BS_DONE with the final status (basic / xb non-null where the status wants the final solve) or BS_HOST.  *fits = false: the wave's
     // buffers do not fit the free device memory — nothing ran, the caller solves the wave on the workers.
+    // warm (pool knob warm_revised; nullptr: a cold wave): relaxation i starts from the kept WK_REVISED state that
+    // parent[i] names when its branch rows extend that state's rows (a bitwise prefix) by J >= 1 — B^-1 = [[B_p^-1, 0], [R, I_J]], the
+    // dual loop, then Phase II — and cold otherwise, in the same run; a relaxation with keep[i] that ends BS_DONE with GOMILP_OK leaves
+    // its B^-1 and basis list in the store under tag[i].  A warm start that spends its dual budget is reported once with stage BS_COLD
+    // (warm = 1, pivd), re-initialised in place and solved cold by the same run: its second report has warm = 0.  Waves with
+    // ld_max > kRevDualLd run cold, with keeping.
     int run(const Engine::RootView &R, int64_t count, const int64_t *koff, const int32_t *var, const double *sign, const double *rhs,
-            double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits);
+            double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits, const WarmSpec *warm = nullptr);
 
     // gives the wave buffers back (they grow with the largest wave seen: 5 MB per 300 x 1500 relaxation); the pool calls it when the
     // root changes

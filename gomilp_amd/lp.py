@@ -349,7 +349,9 @@ class FrontierPool:
             self.set(k, v)
 
     def set(self, key: str, value: int) -> None:
-        """"batched" (1: device-batched pivot loops, 0: one worker thread + stream per relaxation) or any Context knob."""
+        """"batched" (1: device-batched pivot loops, 0: one worker thread + stream per relaxation), "warm_revised" (1: solve_warm on wide
+        waves runs on the batched revised simplex with warm starts; default 0), the other pool knobs of include/gomilp_lp.h, or any
+        Context knob."""
         rc = lib().gomilp_pool_set(self._h, key.encode(), int(value))
         if rc != OK:
             raise ValueError("bad knob %s=%s" % (key, value))
@@ -408,7 +410,9 @@ class FrontierPool:
 
     def solve_warm(self, children, parents=None, tags=None, keep=None, dual_budget: int = 0, tol: float = 0.0) -> FrontierResult:
         """gomilp_frontier_solve_warm (opt-in warm start, include/gomilp_lp.h): children of the set_root problem; parents[i] = tag of a kept
-        relaxation that is child i minus its last constraint (or -1), tags[i] = the id child i is kept under when keep[i]."""
+        relaxation that is child i minus its last constraint (or -1), tags[i] = the id child i is kept under when keep[i].  Wide waves
+        (n - m >= 2m) start warm only with the pool knob warm_revised = 1: there the parent's rows may be any proper prefix of the child's
+        (J >= 1 new rows), and a relaxation without a usable parent starts cold in the same run."""
         count = len(children)
         koff = np.zeros(count + 1, dtype=np.int64)
         for i, ch in enumerate(children):

@@ -261,7 +261,10 @@ void gomilp_pool_destroy(gomilp_pool *pool);
  * relaxations a worker would run on the unguarded revised-simplex pipelines — slack starts of more than 256 rows at exact_degenerate = 1,
  * any size above 64 rows at = 0 — runs on the device-batched revised simplex: the three-kernel pipeline with the relaxation as a grid
  * dimension, Phase I and the Bland rule on the device, bit-identical to the worker path; 0: such waves on the workers, one relaxation per
- * stream.  DESIGN.md section 2.5e); any gomilp_ctx_set key is forwarded to the worker contexts. */
+ * stream.  DESIGN.md section 2.5e), "warm_revised" (default 0, opt-in: a gomilp_frontier_solve_warm call whose wave passes the routing
+ * test of "batch_revised" runs on that schedule too — relaxations whose parent was kept by it start from the parent's B^-1 with a batched
+ * dual simplex, the others cold in the same run, final states are kept as B^-1 + basis list; 0: such a call runs on the workers, cold, and
+ * keeps nothing.  Cold calls never look at it.  DESIGN.md section 2.6b); any gomilp_ctx_set key is forwarded to the worker contexts. */
 int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value);
 /* Upload the root standard form (row-major A0, stride lda) to every worker context of the pool. */
 int gomilp_pool_set_root(gomilp_pool *pool, const double *c0, const double *A0, int64_t lda, const double *b0, int64_t m0,
@@ -312,7 +315,17 @@ int gomilp_pool_solve_root(gomilp_pool *pool, double tol, double *opt_f, double 
  *              cold path of this same call (the reference's Phase I), so the worst case is cold + budget.
  * Parity in this mode (it does not follow the reference's pivot path): status, branching / pruning decisions and |z - z_ref| <= 1e-9
  * max(1, |z_ref|); x is the gonum-order solve of the final basis, as always — the same vertex reached through another basis order can
- * differ in the last bits.  Without parents (parent == NULL or all < 0) the call is gomilp_frontier_solve + keeping. */
+ * differ in the last bits.  Without parents (parent == NULL or all < 0) the call is gomilp_frontier_solve + keeping.
+ * WIDE waves (n - m >= 2m; the waves of pool knob "batch_revised"): with pool knob "warm_revised" = 1 the call runs on the device-batched
+ * revised simplex.  A kept state is the final B^-1 (m x ld doubles: 0.6 MB per 270-row relaxation), the positional basis list and the
+ * relaxation's branch triples.  Relaxation i starts warm when parent[i] names a state kept by this schedule for the current root and its
+ * (var, sign, rhs) rows extend that parent's rows — a bitwise prefix of its own, the rule of gomilp_lp_solve_warm — by J >= 1 rows:
+ * B^-1 = [[B_p^-1, 0], [R, I_J]], a dual simplex on the batched revised-simplex kernels, then Phase II.  Everything else in the wave (no
+ * parent, an unknown tag, a state kept by the tableau schedule, not a prefix) starts cold in the same run, and so does a narrow relaxation
+ * whose parent was kept here: neither is an error.  A warm start that spends dual_budget is re-initialised in place and solved cold by
+ * the same call, bit for bit what the cold call returns (warm_fallbacks).  Relaxations handed to a worker keep nothing; waves with more
+ * than 4096 rows run on this schedule cold, with keeping.  With the knob at 0 (default) a wide warm call runs on the workers, cold,
+ * warm_started = 0.  Same parity contract. */
 int gomilp_frontier_solve_warm(gomilp_pool *pool, int64_t count, const int64_t *koff, const int32_t *var, const double *sign,
                                const double *rhs, const int64_t *parent, const int64_t *tag, const int32_t *keep, int32_t dual_budget,
                                double tol, double *z_out, double *x_out, int32_t *status_out, int32_t *has_x_out,
