@@ -14,7 +14,8 @@ namespace gomilp {
 enum : int32_t {
     RS_RUN = 0,    // set-up launches or a pivot loop are running
     RS_DONE = 1,   // terminal: `status` holds the outcome (GOMILP_OK / ERR_BLAND / ERR_UNSUPPORTED after Phase II: basis + x_B ready for the final solve)
-    RS_HOST = 2,   // terminal: a branch the schedule leaves to a worker's whole solve (the |x_art| band, the zero-level artificial exchange)
+    RS_HOST = 2,   // terminal: a branch the schedule leaves to a worker's whole solve: the |x_art| band (1e-13 < |x_art| < 1e-11: the verdict
+                   // needs a fresh gonum-order solve), and the zero-level artificial exchange where the wave runs without it (rev_exchange = 0)
     RS_COLD = 3    // a warm start that spent its dual-pivot budget: the host re-initialises the slot and the same run solves it cold
 };
 // RevLP::after: what k_rv_check does behind the set-up launches of a superstep
@@ -25,7 +26,9 @@ enum : int32_t {
     RA_DUAL_LOOP = 3  // the dual loop of a warm start (DevState::max_pivots = the dual-pivot budget)
 };
 // RevLP::run: which launches of a superstep work on the relaxation
-enum : int32_t { RR_NONE = 0, RR_LOOP = 1, RR_FORCED = 2, RR_DUAL = 3 };
+// (RR_EXCH: Phase I ended with the artificial basic at level zero — the candidate scan k_rv_exch / k_rv_exch_pick in front of the set-up
+// launches of the next superstep looks for the column that takes its place, simplex.go:581-606)
+enum : int32_t { RR_NONE = 0, RR_LOOP = 1, RR_FORCED = 2, RR_DUAL = 3, RR_EXCH = 4 };
 
 struct RevLP {
     // ---- fixed for the wave (written by the host) ----
@@ -56,7 +59,8 @@ struct RevLP {
     int32_t bl, bl_pos, bland_failed, pad1;
     // ---- work orders for the set-up launches of the next superstep (written by k_rv_init / k_rv_ctrl, cleared by k_rv_check) ----
     int32_t f_var, f_pos, f_p, f_noswap, pad2;      // the forced pivot (run == RR_FORCED)
-    int32_t do_lists;        // 1: basic[f_p] = n, nonbasic = ascending ids of n + 1 columns outside the basis; 2: of n columns
+    int32_t do_lists;        // 1: basic[f_p] = n, nonbasic = ascending ids of n + 1 columns outside the basis; 2: of n columns;
+                             // 3: basic[f_p] = f_var (the exchange), then as 2
     int32_t do_refresh;      // 1: x_B = B^-1 b and y = B^-T c_B; 2: y only
     int32_t after;           // RA_*
     // ---- outcome ----
@@ -70,6 +74,12 @@ struct RevLP {
     int32_t warm, wJ, wmp, wldp;
     int64_t dual_budget;
     int64_t pivd;            // outcome: dual pivots
+    // ---- the zero-level artificial exchange (behind the warm fields, for the same reason) ----
+    // exch_on: the wave runs with it (written by the host); x_added: the artificial's basis position (k_rv_ctrl); x_best: the smallest
+    // candidate id that passed the scan so far (atomic min of k_rv_exch, 0xFFFFFFFF: none); exch: outcome, exchanges done
+    int32_t exch_on, x_added;
+    unsigned int x_best;
+    int32_t exch;
 };
 
 // what the host reads of every active relaxation after a superstep
@@ -77,6 +87,7 @@ struct RevOut {
     int32_t stage, status, wrapped, phase1_used;
     int64_t piv1, piv2, bland, pivd;
     int32_t flips, dual;   // parity of the current B^-1 (the host keeps it for the children); 1: the dual loop runs or is ordered
+    int32_t scan, exch;    // 1: the candidate scan of the exchange is ordered (run == RR_EXCH); exchanges done
 };
 
 // launches (batch_revised.hip).  act: list positions -> relaxation; nact entries.  gp / gr: workgroups per relaxation of the pricing
@@ -85,6 +96,9 @@ void launch_rv_init(RevLP *lps, int count, hipStream_t s);
 void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, hipStream_t s);   // forced pivot, lists, refresh, check: 7 launches
 void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, hipStream_t s);               // Bland step?, K1, K2, K3: 4 launches
 void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s);
+// the candidate scan of the relaxations with run == RR_EXCH, in front of launch_rv_setup: one workgroup per nonbasic position (nn_max: the
+// wave's largest n + 1 - m), then the verdict and the orders of the forced pivot (2 launches)
+void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, hipStream_t s);
 // warm starts: B^-1, basis list, b and the orders of every relaxation with warm != 0 (one launch for the wave, grid rows x count);
 // a dual pivot of the relaxations in the dual loop: leaving row, dual pricing, K2 / K3 in their kDualPick form (4 launches;
 // lds2: bytes of the TWO staged vectors of the pricing kernel, ld_max <= kRevDualLd)

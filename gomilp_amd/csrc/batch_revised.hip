@@ -1,12 +1,13 @@
 // gfx950 (CDNA4, wave64) kernels of the device-batched revised simplex: K1-K3 of simplex_kernels.hip with the relaxation as
 // blockIdx.y, and the small kernels that run a relaxation's stages on the device (slack start, Phase-I set-up, list rebuilds,
-// refreshes, the Bland rule, the verdicts) so that a wave costs a constant number of host round trips per superstep.
+// refreshes, the Bland rule, the zero-level artificial exchange, the verdicts) so that a wave costs a constant number of host round trips per superstep.
 //
 // The pivot rules, the per-element work and the commit are the helpers of simplex_helpers.h, the code the single-relaxation
 // kernels run: every dot product is one wave over one row (wave_dot_row), the argmins are first-index over per-workgroup
 // partials, so a relaxation's values do not depend on the grid it gets or on the relaxations beside it.  Nothing is reduced
 // across relaxations and no kernel waits for another workgroup: kernels communicate across launch boundaries only.
-// Every field of a RevLP that a kernel reads was written by an earlier launch of the stream (RevLP::flips / flips_k2).
+// Every field of a RevLP that a kernel reads was written by an earlier launch of the stream (RevLP::flips / flips_k2); the one
+// exception, RevLP::x_best in k_rv_exch, only saves work.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -381,7 +382,8 @@ __global__ __launch_bounds__(kBlock) void k_rv_dual_price(RevLP *__restrict__ lp
 // set-up launches behind the forced pivot: index lists, refreshes, the check that starts the loop
 // ------------------------------------------------------------------------------------------------
 
-// do_lists: the artificial into the basis list (1), and the nonbasic list as the ascending ids outside the basis (simplex.go:174-184)
+// do_lists: the artificial (1) or the exchanged column f_var (3) into the basis list, and the nonbasic list as the ascending ids outside
+// the basis (simplex.go:174-184)
 __global__ __launch_bounds__(kBlock) void k_rv_lists(RevLP *__restrict__ lps, const int *__restrict__ act) {
     __shared__ int wtot[kWavesPerBlock];
     RevLP *d = lps + act[blockIdx.x];
@@ -389,7 +391,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_lists(RevLP *__restrict__ lps, co
     if (mode == 0 || d->stage != RS_RUN) return;
     const int m = d->m, n = d->n, ncols = mode == 1 ? n + 1 : n;
     int32_t *basic = d->basic, *nonbasic = d->nonbasic, *inb = d->inb;
-    if (mode == 1 && threadIdx.x == 0) basic[d->f_p] = n;
+    if (mode != 2 && threadIdx.x == 0) basic[d->f_p] = mode == 1 ? n : d->f_var;
     for (int j = threadIdx.x; j <= n; j += kBlock) inb[j] = 0;
     __syncthreads();
     for (int i = threadIdx.x; i < m; i += kBlock) inb[basic[i]] = 1;
@@ -544,7 +546,10 @@ __global__ __launch_bounds__(kBlock) void k_rv_ctrl(RevLP *__restrict__ lps, con
                     } else if (fabs(xart) > 1e-12) {
                         d->status = GOMILP_ERR_INFEASIBLE; d->stage = RS_DONE; d->run = RR_NONE;
                     } else if (added != 0xFFFFFFFFu) {
-                        d->stage = RS_HOST; d->run = RR_NONE;   // the artificial stayed basic at level zero: the exchange of simplex.go:581-606
+                        // the artificial stayed basic at level zero: the exchange of simplex.go:581-606 — the candidate scan in front of
+                        // the next superstep's set-up launches, or (rev_exchange = 0) a worker's whole solve
+                        if (d->exch_on) { d->run = RR_EXCH; d->x_added = (int)added; d->x_best = 0xFFFFFFFFu; }
+                        else { d->stage = RS_HOST; d->run = RR_NONE; }
                     } else {
                         d->run = RR_NONE; d->do_lists = 2; d->do_refresh = 1; d->after = RA_P2_LOOP;
                     }
@@ -569,8 +574,80 @@ __global__ __launch_bounds__(kBlock) void k_rv_ctrl(RevLP *__restrict__ lps, con
         o.stage = d->stage; o.status = d->status; o.wrapped = d->wrapped; o.phase1_used = d->phase1_used;
         o.piv1 = d->piv1; o.piv2 = d->piv2; o.bland = d->bland; o.pivd = d->pivd;
         o.flips = d->flips; o.dual = (d->run == RR_DUAL || d->after == RA_DUAL_LOOP) ? 1 : 0;
+        o.scan = d->run == RR_EXCH ? 1 : 0; o.exch = d->exch;
         out[id] = o;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The zero-level artificial exchange (Engine::solve_locked behind the Phase-I verdict; simplex.go:581-606): the artificial stayed basic
+// at position `added` with x_B[added] = 0, and the first column j < n outside the basis, in ascending id, takes its place for which
+//   d = B^-1 a_j,  |d_added| > 1e-9 max(1, max_i |d_i|)   and no   v_i < -1e-13,  v_added = theta = x_B[added] / d_added, v_i = x_B[i] - theta d_i.
+// A worker tries the columns one after the other, one FTRAN and one round trip each; here every candidate is tried at once, one
+// workgroup each, and the smallest id that passes wins an atomic min: the same column.  The candidates are the entries of the Phase-I
+// loop's nonbasic list (n + 1 - m ids, every column outside the basis; the artificial is basic and not among them), in whatever order
+// the loop's swaps left them: the minimum does not depend on it.  Every d_i is the dot product k_rv_ftran<RR_FORCED> computes for that
+// column — a_j staged in LDS, one wave per row of the current B^-1 — so the verdicts at the two thresholds are the worker's, and the
+// comparisons are written as the worker writes them (a NaN rejects through d_added only; its std::max skips a NaN in max_i |d_i|).
+// d_added comes first: |d_added| <= 1e-9 fails whatever the maximum is, and such a candidate costs one row, not m.
+// x_best is the one word a kernel of this file reads while its own launch writes it: a workgroup whose id is above a passing id it
+// happens to see ends early.  That changes the work done, never the minimum.
+// Dynamic LDS: ld doubles, as K2.  grid: (nonbasic positions of the widest relaxation, list positions).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_rv_exch(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ double smax[kWavesPerBlock];
+    RevLP *d = lps + act[blockIdx.y];
+    if (d->run != RR_EXCH) return;
+    const int m = d->m, n = d->n, ld = d->ld, added = d->x_added, pos = blockIdx.x;
+    if (pos >= d->nn) return;
+    const int j = d->nonbasic[pos];
+    if (j < 0 || j >= n) return;   // (row n of At is the artificial: never a candidate)
+    __shared__ unsigned int seen;
+    if (threadIdx.x == 0) seen = __atomic_load_n(&d->x_best, __ATOMIC_RELAXED);
+    __syncthreads();
+    if (seen < (unsigned int)j) return;   // (workgroup-uniform)
+    const double *binv_cur = d->binv[d->flips & 1], *xb = d->xb;
+    const int ld2 = ld >> 1;
+    stage_vec(svec, d->At + (size_t)j * ld, ld2);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const double dpv = wave_dot_row(binv_cur + (size_t)added * ld, svec, ld2, lane);   // (every wave: the same bits, workgroup-uniform)
+    if (!(fabs(dpv) > 1e-9)) return;
+    const double theta = xb[added] / dpv;
+    double dmax = 0;
+    int bad = 0;
+    for (int i = w; i < m; i += kWavesPerBlock) {
+        const double di = wave_dot_row(binv_cur + (size_t)i * ld, svec, ld2, lane);
+        const double a = fabs(di);
+        if (dmax < a) dmax = a;
+        const double v = (i == added) ? theta : xb[i] - theta * di;
+        if (v < -1e-13) bad = 1;
+    }
+    if (lane == 0) smax[w] = dmax;
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x != 0 || bad) return;
+#pragma unroll
+    for (int t = 0; t < kWavesPerBlock; t++) if (dmax < smax[t]) dmax = smax[t];
+    if (!(fabs(dpv) > 1e-9 * (1.0 < dmax ? dmax : 1.0))) return;
+    atomicMin(&d->x_best, (unsigned int)j);
+}
+
+// the scan's verdict: the forced pivot of the exchange — the worker's launch_ftran(column j) / launch_update(row added, no swap) on a
+// loop state that runs again — with j into the basis list (do_lists = 3), then the orders of the Phase-II start; no candidate passed:
+// infeasible, no x (simplex.go:606).  The exchange is a pivot of neither phase: piv1 stands as k_rv_ctrl took it.
+__global__ void k_rv_exch_pick(RevLP *__restrict__ lps, const int *__restrict__ act) {
+    RevLP *d = lps + act[blockIdx.x];
+    if (threadIdx.x != 0 || d->run != RR_EXCH) return;
+    const unsigned int best = d->x_best;
+    if (best == 0xFFFFFFFFu) {
+        d->status = GOMILP_ERR_INFEASIBLE; d->stage = RS_DONE; d->run = RR_NONE;
+        return;
+    }
+    DevState *st = d->st;
+    st->done = 0; st->status = ST_RUNNING; st->rq = 0;
+    d->f_var = (int)best; d->f_pos = -1; d->f_p = d->x_added; d->f_noswap = 1;
+    d->run = RR_FORCED; d->do_lists = 3; d->do_refresh = 1; d->after = RA_P2_LOOP;
+    d->exch += 1;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -596,6 +673,10 @@ void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_
 }
 void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_ctrl, dim3(nact), dim3(kBlock), 0, s, lps, act, out);
+}
+void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(k_rv_exch, dim3(nn_max, nact), dim3(kBlock), lds, s, lps, act);
+    hipLaunchKernelGGL(k_rv_exch_pick, dim3(nact), dim3(64), 0, s, lps, act);
 }
 void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_warm_binv, dim3(m_max, count), dim3(kBlock), 0, s, lps);

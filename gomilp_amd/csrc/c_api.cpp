@@ -56,6 +56,9 @@ struct gomilp_pool {
                                 // device-batched revised simplex (engine_batch_revised.hpp); 0: every such wave on the workers
     int warm_revised = 0;       // knob (opt-in): a gomilp_frontier_solve_warm call whose wave passes the wide routing test runs on the batched
                                 // revised simplex too, with warm starts and keeping; 0: such a call goes to the workers, cold
+    int rev_exchange = 1;       // knob: on the batched revised simplex a relaxation whose Phase I ends with the artificial basic at level zero
+                                // exchanges it on the device (batch_revised.hip: k_rv_exch) instead of going to a worker's whole solve — the same
+                                // column, bit-identical results; 0: the hand-over (host_fallbacks)
     int64_t refresh = 0, max_pivots = 0;   // the workers' knobs of these names, as the batched revised simplex needs them
     std::unique_ptr<RevBatchEngine> rev;   // created on first use
     gomilp::WarmStore warm;     // final states kept for warm starts (gomilp_frontier_solve_warm), shared by both schedules
@@ -227,6 +230,7 @@ int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value) {
     if (std::string(key) == "batched") { pool->batched = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "batch_revised") { pool->batch_revised = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "warm_revised") { pool->warm_revised = value ? 1 : 0; return GOMILP_OK; }
+    if (std::string(key) == "rev_exchange") { pool->rev_exchange = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "split_large") { pool->split_large = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "split_phase") { pool->split_phase = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "batch_virt") {   // wide waves on virtual tableaus for their first block (default 1)
@@ -438,13 +442,14 @@ static int frontier_solve_impl(gomilp_pool *pool, int64_t count, const int32_t *
         auto on_done = [&](int64_t i, const BatchEngine::Outcome &o, const int32_t *basic, const double *xb) {   // (called on this thread)
             if (o.warm) { agg.warm_started++; agg.pivots_dual += o.pivd; }
             if (o.stage == gomilp::BS_COLD) { agg.warm_fallbacks++; return; }   // (the schedule solves it cold in the same run and reports it again)
-            if (o.stage != gomilp::BS_DONE) {   // the |x_art| band, the zero-level artificial exchange
+            if (o.stage != gomilp::BS_DONE) {   // the |x_art| band; with rev_exchange = 0 the zero-level artificial exchange
                 agg.host_fallbacks++;
                 pool->submit([&full_solve, i](int w) { full_solve(w, i); });
                 return;
             }
             agg.relaxations++; agg.batched_relaxations++;
             agg.pivots_phase1 += o.piv1; agg.pivots_phase2 += o.piv2; agg.bland_steps += o.bland; agg.phase1_runs += o.phase1_used;
+            agg.art_exchanges += o.art_exchanges;
             if (basic) {
                 const int rc0 = o.status;
                 pool->submit([&finish, i, basic, xb, rc0](int w) { finish(w, i, basic, xb, rc0); });
@@ -455,6 +460,7 @@ static int frontier_solve_impl(gomilp_pool *pool, int64_t count, const int32_t *
         };
         RevBatchEngine::Stats rs;
         bool fits = true;
+        pool->rev->set_exchange(pool->rev_exchange != 0);
         gomilp::WarmSpec wspec;
         if (wa) {
             wspec.store = &pool->warm; wspec.parent = wa->parent; wspec.tag = wa->tag; wspec.keep = wa->keep; wspec.dual_budget = wa->budget;

@@ -68,6 +68,7 @@ class BatchEngine {
         int status = 0, wrapped = 0, phase1_used = 0;
         int64_t piv1 = 0, piv2 = 0, bland = 0, pivd = 0;   // (pivd: dual pivots of a warm start)
         int warm = 0;                                      // started from its parent's basis
+        int art_exchanges = 0;                             // zero-level artificial exchanges done on the device (RevBatchEngine)
     };
     struct Stats {
         int64_t launches = 0, supersteps = 0, blocks = 0, loop_launches = 0, res_launches = 0, virt_blocks = 0, warm_started = 0, warm_kept = 0;

@@ -218,6 +218,7 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
         d.m0 = m0; d.n0 = n0; d.K = K; d.m = m; d.n = n; d.ld = ld;
         d.max_pivots = max_pivots; d.tol_user = tol;
         d.stage = RS_RUN; d.run = RR_NONE; d.cost = d_c2; d.f_var = d.f_pos = d.f_p = -1;
+        d.exch_on = exchange_ ? 1 : 0; d.x_added = -1; d.x_best = 0xFFFFFFFFu;
         const Plan &P = plan[(size_t)i];
         if (P.e) {
             d.warm = 1; d.wJ = P.J; d.wmp = P.e->m; d.wldp = P.e->ld;
@@ -240,9 +241,11 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
 
     // ---- supersteps ----
     const int gp = grid_for_rows(n_max + 1 - m0), gr = grid_for_rows(m_max);
+    const int nn_max = n0 + 1 - m0;   // nonbasic positions of a Phase-I loop (n + 1 - m, the same for every K)
     const size_t lds = (size_t)ld_max * sizeof(double);
     std::vector<int> act((size_t)count), done_now;
     std::vector<char> is_warm((size_t)count, 0), in_dual((size_t)count, 0);   // started warm (and still is) / the dual loop runs or is ordered
+    std::vector<char> in_scan((size_t)count, 0);                              // the candidate scan of the artificial exchange is ordered
     for (int64_t i = 0; i < count; i++) { act[(size_t)i] = (int)i; is_warm[(size_t)i] = in_dual[(size_t)i] = plan[(size_t)i].e ? 1 : 0; }
     struct Keep { int id; std::shared_ptr<WarmEntry> e; };
     std::vector<Keep> keeps;
@@ -254,8 +257,10 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
         memcpy(b.h_act, act.data(), (size_t)nact * sizeof(int));
         RV_TRY(hipMemcpyAsync(b.d_act, b.h_act, (size_t)nact * sizeof(int), hipMemcpyHostToDevice, stream_));
         // (the dual launches only while some active relaxation is in the dual stage: a cold wave's list is setup, chunk x pivot, ctrl)
-        bool any_dual = false, any_primal = false;
-        for (int id : act) (in_dual[(size_t)id] ? any_dual : any_primal) = true;
+        bool any_dual = false, any_primal = false, any_scan = false;
+        for (int id : act) { (in_dual[(size_t)id] ? any_dual : any_primal) = true; if (in_scan[(size_t)id]) any_scan = true; }
+        // (the scan's verdict orders the forced pivot that the set-up launches behind it run: an exchange costs no superstep of its own)
+        if (any_scan) { launch_rv_exchange(b.d_lps, b.d_act, nact, nn_max, lds, stream_); launches += 2; }
         launch_rv_setup(b.d_lps, b.d_act, nact, gr, ld_max, lds, stream_);
         const int chunk = steps < 2 ? kFirstChunk : kChunk;
         for (int t = 0; t < chunk; t++) {
@@ -275,6 +280,7 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
         for (int id : act) {
             const RevOut &o = b.h_out[id];
             in_dual[(size_t)id] = o.dual ? 1 : 0;
+            in_scan[(size_t)id] = o.scan ? 1 : 0;
             if (o.stage == RS_RUN) { next.push_back(id); continue; }
             if (o.stage == RS_COLD) {
                 // the dual budget is spent: reported as a fallback, then the slot starts again from its slack basis — its work area zeroed, its
@@ -285,7 +291,7 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
                 RevLP &d = lps[(size_t)id];
                 const Lay &L = lay[(size_t)id];
                 d.warm = 0;
-                is_warm[(size_t)id] = 0; in_dual[(size_t)id] = 0;
+                is_warm[(size_t)id] = 0; in_dual[(size_t)id] = 0; in_scan[(size_t)id] = 0;
                 RV_TRY(hipMemsetAsync(b.d_work + L.wk0, 0, (L.wk1 - L.wk0) * sizeof(double), stream_));
                 RV_TRY(hipMemcpyAsync(b.d_lps + id, &d, sizeof(RevLP), hipMemcpyHostToDevice, stream_));
                 launch_rv_init(b.d_lps + id, 1, stream_);
@@ -329,6 +335,7 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
             oc.stage = o.stage == RS_DONE ? BS_DONE : BS_HOST;
             oc.status = o.status; oc.wrapped = o.wrapped; oc.phase1_used = o.phase1_used;
             oc.piv1 = o.piv1; oc.piv2 = o.piv2; oc.bland = o.bland; oc.pivd = o.pivd; oc.warm = is_warm[(size_t)id];
+            oc.art_exchanges = o.exch;
             const bool fin = oc.stage == BS_DONE && (o.status == GOMILP_OK || o.status == GOMILP_ERR_BLAND || o.status == GOMILP_ERR_UNSUPPORTED);
             on_done(id, oc, fin ? b.h_basic + (size_t)id * ld_max : nullptr, fin ? b.h_xb + (size_t)id * ld_max : nullptr);
         }

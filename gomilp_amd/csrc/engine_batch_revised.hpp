@@ -34,6 +34,12 @@ class RevBatchEngine {
     int run(const Engine::RootView &R, int64_t count, const int64_t *koff, const int32_t *var, const double *sign, const double *rhs,
             double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits, const WarmSpec *warm = nullptr);
 
+    // pool knob rev_exchange: a relaxation whose Phase I ends with the artificial basic at level zero exchanges it on the device (the
+    // candidate scan of batch_revised.hip: two launches in front of the set-up launches of the supersteps that have such a relaxation,
+    // none elsewhere; Outcome::art_exchanges) and goes on to Phase II; off: it is handed over as BS_HOST.  The |x_art| band
+    // (1e-13 < |x_art| < 1e-11) is BS_HOST either way: its verdict needs a fresh gonum-order solve.
+    void set_exchange(bool on) { exchange_ = on; }
+
     // gives the wave buffers back (they grow with the largest wave seen: 5 MB per 300 x 1500 relaxation); the pool calls it when the
     // root changes
     void release();
@@ -41,6 +47,7 @@ class RevBatchEngine {
    private:
     struct Buf;
     int device_;
+    bool exchange_ = true;
     hipStream_t stream_ = nullptr;
     Buf *b_;
 };

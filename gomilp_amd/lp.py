@@ -66,7 +66,8 @@ class FrontierStats(C.Structure):
                 ("seconds_busy_sum", C.c_double), ("batched_relaxations", C.c_int64), ("host_fallbacks", C.c_int64),
                 ("supersteps", C.c_int64), ("seconds_batch", C.c_double), ("blocks", C.c_int64), ("blocks_sampled", C.c_int64),
                 ("seconds_inner_kernels", C.c_double), ("seconds_update_kernels", C.c_double),
-                ("warm_started", C.c_int64), ("warm_fallbacks", C.c_int64), ("warm_kept", C.c_int64), ("pivots_dual", C.c_int64)]
+                ("warm_started", C.c_int64), ("warm_fallbacks", C.c_int64), ("warm_kept", C.c_int64), ("pivots_dual", C.c_int64),
+                ("art_exchanges", C.c_int64)]
 
 
 EXPORTS = [
@@ -350,7 +351,8 @@ class FrontierPool:
 
     def set(self, key: str, value: int) -> None:
         """"batched" (1: device-batched pivot loops, 0: one worker thread + stream per relaxation), "warm_revised" (1: solve_warm on wide
-        waves runs on the batched revised simplex with warm starts; default 0), the other pool knobs of include/gomilp_lp.h, or any
+        waves runs on the batched revised simplex with warm starts; default 0), "rev_exchange" (1: that schedule exchanges a zero-level
+        artificial on the device, stats art_exchanges; 0: the relaxation goes to a worker, host_fallbacks), the other pool knobs of include/gomilp_lp.h, or any
         Context knob."""
         rc = lib().gomilp_pool_set(self._h, key.encode(), int(value))
         if rc != OK:

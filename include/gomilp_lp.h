@@ -246,6 +246,8 @@ typedef struct gomilp_frontier_stats {
     int64_t warm_fallbacks;      /* of which handed back to the cold path (dual-pivot budget spent) */
     int64_t warm_kept;           /* final states kept for children */
     int64_t pivots_dual;         /* dual-simplex pivots of the warm starts (not counted in pivots_phase1 / 2) */
+    int64_t art_exchanges;       /* zero-level artificial exchanges (simplex.go:581-606) done inside the batched revised schedule (pool knob
+                                    "rev_exchange"); those of relaxations solved on a worker are not counted */
 } gomilp_frontier_stats;
 
 gomilp_pool *gomilp_pool_create(int device, int workers, int *status);
@@ -261,7 +263,11 @@ void gomilp_pool_destroy(gomilp_pool *pool);
  * relaxations a worker would run on the unguarded revised-simplex pipelines — slack starts of more than 256 rows at exact_degenerate = 1,
  * any size above 64 rows at = 0 — runs on the device-batched revised simplex: the three-kernel pipeline with the relaxation as a grid
  * dimension, Phase I and the Bland rule on the device, bit-identical to the worker path; 0: such waves on the workers, one relaxation per
- * stream.  DESIGN.md section 2.5e), "warm_revised" (default 0, opt-in: a gomilp_frontier_solve_warm call whose wave passes the routing
+ * stream.  DESIGN.md section 2.5e), "rev_exchange" (default 1: on that schedule a relaxation whose Phase I ends with the artificial basic at level
+ * zero exchanges it on the device — every nonbasic column tried at once by the worker's acceptance rule, the smallest passing id taken, one
+ * forced pivot, then Phase II: the column the worker takes, bit-identical results, counted in art_exchanges; 0: such a relaxation is handed
+ * to a worker's whole solve and counted in host_fallbacks.  Either way the schedule hands over a relaxation whose artificial ends Phase I
+ * with 1e-13 < |x_art| < 1e-11: that verdict needs a fresh gonum-order solve), "warm_revised" (default 0, opt-in: a gomilp_frontier_solve_warm call whose wave passes the routing
  * test of "batch_revised" runs on that schedule too — relaxations whose parent was kept by it start from the parent's B^-1 with a batched
  * dual simplex, the others cold in the same run, final states are kept as B^-1 + basis list; 0: such a call runs on the workers, cold, and
  * keeps nothing.  Cold calls never look at it.  DESIGN.md section 2.6b); any gomilp_ctx_set key is forwarded to the worker contexts. */
@@ -323,7 +329,8 @@ int gomilp_pool_solve_root(gomilp_pool *pool, double tol, double *opt_f, double 
  * B^-1 = [[B_p^-1, 0], [R, I_J]], a dual simplex on the batched revised-simplex kernels, then Phase II.  Everything else in the wave (no
  * parent, an unknown tag, a state kept by the tableau schedule, not a prefix) starts cold in the same run, and so does a narrow relaxation
  * whose parent was kept here: neither is an error.  A warm start that spends dual_budget is re-initialised in place and solved cold by
- * the same call, bit for bit what the cold call returns (warm_fallbacks).  Relaxations handed to a worker keep nothing; waves with more
+ * the same call, bit for bit what the cold call returns (warm_fallbacks).  Relaxations handed to a worker (host_fallbacks: the |x_art| band; with "rev_exchange" = 0 the zero-level artificial
+ * exchange too) keep nothing, one that exchanged its artificial on the device is kept like any other; waves with more
  * than 4096 rows run on this schedule cold, with keeping.  With the knob at 0 (default) a wide warm call runs on the workers, cold,
  * warm_started = 0.  Same parity contract. */
 int gomilp_frontier_solve_warm(gomilp_pool *pool, int64_t count, const int64_t *koff, const int32_t *var, const double *sign,

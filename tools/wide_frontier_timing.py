@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Seconds per wide frontier wave with the pool knob batch_revised at 0 (every relaxation on a worker's single-relaxation engine) and at 1
-(the device-batched revised simplex), same process, same pool: median of five pool calls after one warm-up.
+(the device-batched revised simplex), there with the pool knob rev_exchange at 0 (a zero-level artificial exchange goes
+to a worker's whole solve) and at 1 (it is done on the device), same process, same pool: median of five pool calls after one warm-up.
 
     python tools/wide_frontier_timing.py [m nv seed]        (default 300 1200 2)
     python tools/wide_frontier_timing.py --checkout DIR     wave P only, on the built package of another checkout (the parent commit,
                                                             which has no such knob): the yardstick that batch_revised = 0 must reproduce
 
 Waves on the root optimum the pool computes: P (64 children, 6 branch rows), D (one down branch per fractional integer variable),
-P8 (256 children, 8 branch rows).  One line per (wave, knob): seconds, relaxations / s, supersteps, launches, host_fallbacks, pivots."""
+P8 (256 children, 8 branch rows).  One line per (wave, knobs): seconds, the spread of the five calls (max - min), relaxations / s,
+supersteps, launches, host_fallbacks, art_exchanges, pivots."""
 import math
 import os
 import statistics
@@ -38,12 +40,13 @@ def main(argv):
     if OTHER:
         waves = {"P": waves["P"]}
     print("root %d x %d seed %d, %s" % (m, nv + m, seed, "the package of another checkout (--checkout)" if OTHER else "this checkout's package"))
-    print("| wave | children | batch_revised | s / wave | relaxations / s | supersteps | launches | host_fallbacks | pivots | bland |")
-    print("|---|---|---|---|---|---|---|---|---|---|")
+    print("| wave | children | batch_revised | rev_exchange | s / wave | spread | relaxations / s | supersteps | launches | host_fallbacks | art_exchanges | pivots | bland |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
     for name, wave in waves.items():
-        for knob in ((-1,) if OTHER else (0, 1)):
+        for knob, exch in (((-1, -1),) if OTHER else ((0, 0), (1, 0), (1, 1))):
             if knob >= 0:
                 pool.set("batch_revised", knob)
+                pool.set("rev_exchange", exch)
             pool.solve(wave)   # warm-up
             ts = []
             for _ in range(5):
@@ -51,8 +54,9 @@ def main(argv):
                 q = pool.solve(wave)
                 ts.append(time.perf_counter() - t0)
             s, t = q.stats, statistics.median(ts)
-            print("| %s | %d | %s | %.4f | %.0f | %d | %d | %d | %d | %d |" % (name, len(wave), knob if knob >= 0 else "other checkout", t, len(wave) / t, s["supersteps"],
-                                                                       s["kernel_launches"], s["host_fallbacks"], s["pivots_phase1"] + s["pivots_phase2"], s["bland_steps"]),
+            print("| %s | %d | %s | %s | %.4f | %.4f | %.0f | %d | %d | %d | %d | %d | %d |" % (
+                name, len(wave), knob if knob >= 0 else "other checkout", exch if knob > 0 else "-", t, max(ts) - min(ts), len(wave) / t, s["supersteps"],
+                s["kernel_launches"], s["host_fallbacks"], s.get("art_exchanges", 0), s["pivots_phase1"] + s["pivots_phase2"], s["bland_steps"]),
                   "  # calls: " + " ".join("%.4f" % v for v in ts), flush=True)
     pool.close()
     return 0
