@@ -20,6 +20,7 @@
 #include "engine.hpp"
 #include "engine_batch.hpp"
 #include "engine_batch_revised.hpp"
+#include "lu_host.h"
 
 using gomilp::BatchEngine;
 using gomilp::Engine;
@@ -775,6 +776,19 @@ int gomilp_debug_gonum_lu_cond(const double *M, int64_t n, int transposed, doubl
     bool dz = false;
     if (!gomilp::gonum_lu_cond(M, (int)n, (int)n, transposed != 0, cond, &dz)) return -1;
     return dz ? 1 : 0;
+}
+
+int gomilp_debug_lu_host_solve(int64_t m, int64_t nd, const int32_t *dl, const int32_t *phys, const double *diag, const double *W, int coupled,
+                               const double *rhs, double *x) {
+    if (m < 1 || m > 16384 || nd < 0 || nd > m || !phys || !diag || !rhs || !x || (nd > 0 && (!dl || !W))) return -1;
+    const int64_t nx = coupled ? nd : m;
+    for (int64_t i = 0; i < nx; i++) x[i] = 0.0;
+    if (gomilp::lu_det_is_zero(diag, phys, (int)m)) return 1;   // (Engine::lu_solve gives zeros as well)
+    if (coupled) {
+        std::vector<double> xdl((size_t)nd);
+        gomilp::lu_host_solve_coupled((int)nd, dl, phys, diag, W, rhs, xdl.data(), x);
+    } else gomilp::lu_host_solve((int)m, (int)nd, dl, phys, diag, W, rhs, x);
+    return 0;
 }
 
 int64_t gomilp_debug_find_independent_device(gomilp_ctx *ctx, int64_t problem, int64_t *idx_out, int64_t cap) {

@@ -852,439 +852,6 @@ int Engine::run_loop_fused(const Problem &P, int phase, double tol, int nn, cons
 }
 
 // ------------------------------------------------------------------------------------------------
-// Final solve x_B = ab^-1 b in gonum's order: LU on the device (k_lu_*), the two triangular solves
-// of Dgetrs (lapack/gonum/dgetrs.go:37-45 -> blas/gonum/level3double.go:75-118) on the host, because
-// the upper solve is one sequential dependency chain of m^2/2 rounded operations.
-// ------------------------------------------------------------------------------------------------
-// transpose: the system is ab^T y = rhs (the reference's BTRAN, simplex.go:236: LU of a materialised copy of ab.T()).  The
-// column-major image of ab^T is the row-major image of ab, so the two gathers just change places; no column of ab^T is known
-// to be a unit vector.  rhs_host (m entries, by basis position; default b): the right-hand side.
-int Engine::final_solve(const Problem &P, int, std::vector<double> &x, bool *singular, const int32_t *basic_host, bool transpose,
-                        const double *rhs_host) {
-    int rc = lu_factor(P, singular, basic_host, transpose);
-    if (rc != GOMILP_OK) return rc;
-    return lu_solve(P, x, rhs_host);
-}
-
-// The factorization half of the final solve: gather, gonum-order LU on the device, the packed factors on the host (and, for the large
-// bases, what the row kernel needs on the device).  Everything lu_solve needs stays in lu_cache_ / the work buffers until the next
-// factorization: an exact step solves for x_B, for the entering column and for every Bland candidate from ONE factorization of ab
-// (the reference factors again each time, simplex.go:289,315,356 — same matrix, same bits).
-int Engine::lu_factor(const Problem &P, bool *singular, const int32_t *basic_host, bool transpose) {
-    Work &w = *w_;
-    const double tf0 = now_s();
-    const int m = P.m, ldw = P.ld;
-    int nonunit = 0;
-    bool compressed = lu_blocked_ >= 2 && lu_compressed_supported(m, lu_large_ != 0);
-    const bool large = compressed && luc_large_rpt(m) > 0;   // knob lu_large: the compressed rounds beyond 4096 rows
-    lu_cache_.valid = false;
-    // the compressed schedule keeps L/U column-major (lu_compressed.hip), the other two row-major
-    if (compressed != transpose) launch_luc_gather(P.dAt, P.ld, m, w.basic, w.W, ldw, stream_);
-    else {
-        if (transpose) HIP_TRY(hipMemsetAsync(w.W, 0, (size_t)m * ldw * sizeof(double), stream_));   // (k_gather_w leaves the padding of a line alone)
-        launch_gather_w(P.dAt, P.ld, m, w.basic, w.W, ldw, stream_);
-    }
-    // unit columns of ab (from the column statistics of the upload): the blocked LU skips their elimination steps
-    if (!basic_host) {   // the caller has no host copy of the basis positions yet
-        HIP_TRY(hipMemcpyAsync(w.h_idx, w.basic, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(sync_stream());
-        basic_host = w.h_idx;
-    }
-    {
-        std::vector<int32_t> ur(m);
-        for (int pos = 0; pos < m; pos++) {
-            const int j = basic_host[pos];
-            ur[pos] = (!transpose && j < P.n && P.nnz[j] == 1 && P.allone[j]) ? P.lastrow[j] : -1;
-            if (ur[pos] < 0) nonunit++;
-        }
-        int rcu = stage_upload(w.unitrow, ur.data(), (size_t)m * sizeof(int32_t));
-        if (rcu != GOMILP_OK) return rcu;
-    }
-    LUArgs a;
-    a.W = w.W; a.ldw = ldw; a.m = m; a.lpos = w.lpos; a.rowstep = w.rowstep;
-    for (int t = 0; t < 2; t++) { a.pk[t] = w.lpk[t]; a.pl[t] = w.lpl[t]; a.pr[t] = w.lpr[t]; }
-    a.st = w.st;
-    a.unit_row = w.unitrow;
-    bool blocked = compressed || (lu_blocked_ && lu_blocked_supported(m));
-    a.dense_flag = blocked ? w.denseflag : nullptr;
-    a.ctl = w.luctl; a.Lp = w.luLp; a.Up = w.luUp;
-    // look-ahead schedule: where a factorization takes many rounds (measured: 2048 rows 23 rounds 2.20 -> 2.05 ms, 1000 rows 12 rounds
-    // 1.10 -> 1.03 ms on the device; 520-row children, 4 rounds: 0.63 -> 0.65 ms, and a wave runs dozens of them side by side)
-    // Its launches wait for their own workgroups (bounded), like the loop kernels: two such launches side by side, or one beside a loop
-    // kernel, can hold each other's workgroups off the CUs until a wait gives up (measured: four metric LPs finishing together, two of
-    // four factorizations fell back after ~50 ms).  So it runs only while this engine holds the device's loop slots, all of them, and
-    // only if they are free right now; a pool's workers never ask (knob lu_look).
-    a.slots = 1; a.look = (lu_blocked_ >= 3 && lu_look_ && m > 768 && compressed && !large) ? 1 : 0;   // (beyond 4096 rows: the plain schedule, no loop slots taken)
-    struct LookSlot {
-        int dev; bool held;
-        LookSlot(int d, bool want) : dev(d), held(want && Engine::loop_try_acquire_all(d)) {}
-        ~LookSlot() { drop(); }
-        void drop() { if (held) Engine::loop_release(dev, 4, 0); held = false; }
-    } look_slot(device_, a.look != 0);
-    if (!look_slot.held) a.look = 0;
-    // the rows of a panel on the workgroups of one XCD (lu_cross.hip).  1: sixteen slots, the plain schedule.  2: thirty-two slots (half the
-    // rounds where a round ends because its slots are used up) in the schedule chosen above — the default where the look-ahead runs (a pool's
-    // workers factor side by side and every such panel asks for workgroups of the same XCD: they keep the one-workgroup panel), from
-    // the size at which it measures ahead (final solve, 32 slots against the one-workgroup panel: 1100 rows 1.28 / 1.24 ms, 1280 rows
-    // 1.40 / 1.41, 1536 rows 1.40 / 1.45, 1792 rows 1.74 / 1.81, 2048 rows 2.13 / 2.19; up to 1024 rows a step of 512 threads is cheaper
-    // than the exchange: 1.17 / 1.10 ms)
-    const int cross_mode = lu_cross_ >= 0 ? (int)lu_cross_ : ((m > 1280 && m <= 2048 && lu_look_) ? 2 : 0);
-    // beyond 4096 rows (knob lu_large) that panel, several rows per lane on 8 workgroups, is the only one; lu_cross = 1 / 2 there name 16 / 32
-    // slots for the four-row instance (default 16 — measured at 4097 rows, 137 dense steps, 5 rounds either way: 1.4 ms against 2.1 ms with
-    // 32)
-    int cross_G = large ? 8 : ((cross_mode && compressed) ? luc_cross_groups(m, 1) : 0);
-    const int cross_slots = large ? (lu_cross_ == 2 ? 32 : 16) : (cross_mode == 2 ? 32 : 16);
-    if (cross_G) {
-        if (!w.luxrec) {
-            HIP_TRY(dmalloc(&w.luxrec, luc_cross_doubles()));
-            HIP_TRY(hipMemsetAsync(w.luxrec, 0, luc_cross_doubles() * sizeof(double), stream_));
-        }
-        if (cross_mode != 2 || large) { a.look = 0; look_slot.drop(); }
-    }
-    a.ctl_prev = a.ctl; a.Lp_prev = a.Lp; a.Up_prev = a.Up;
-    a.rowsnap = w.rowstep + w.cap_m; a.rowsnap_prev = a.rowsnap;   // (launch_luc_rounds sets the round's parity)
-    a.ctl_base = a.ctl; a.round = 0; a.pad3 = bt_fault_ == 2 ? 1 : 0;
-    w.st_host->lu_singular = 0;
-    if (!(compressed && m <= 128)) sync_state_to_device();   // (small bases: k_luc_init clears the flag on the device, the packed block brings it back)
-    lu_rounds_ = 0;
-    int32_t *h_dense = w.h_idx + w.cap_m;   // landing place of the dense-step flags (h_idx holds nm + nc entries; lpos lands in front)
-    // Small bases: the packed factors are asked for together with the control block, in ONE host round trip and ONE copy — all m
-    // columns (the compact list of dense columns would need the flags first; a unit-column step has zero multipliers and zero
-    // off-diagonal U entries, which the solves skip like gonum's do: same bits, m*m instead of m*nd doubles over PCIe), with the
-    // diagonal, the row positions, the flags and both control blocks behind them (k_luc_pack_small).  An exact step factors twice and
-    // small trees are made of round trips and 3 us copies (60 per relaxation before this).  Should the batch of rounds turn out too
-    // short, the general path takes over from where the rounds stand.
-    bool oneshot = compressed && !cross_G && m <= 128 && luc_pack_small_bytes(m) <= ((size_t)w.cap_m * w.cap_ld + 512) * sizeof(double);   // (the block fits Wd / h_W: ensure_work)
-    std::vector<int32_t> dl;
-    auto enqueue_pack = [&](int nd2) -> int {
-        int rcd = stage_upload(w.dlist, dl.data(), (size_t)nd2 * sizeof(int32_t));
-        if (rcd != GOMILP_OK) return rcd;
-        const bool split2 = compressed && m >= 1024 && nd2 > 0;
-        if (split2) launch_luc_pack_dense(a, w.dlist, nd2, w.rho, w.Wd, w.ludiag, stream_);
-        else if (compressed) launch_luc_pack(a, w.dlist, nd2, w.Wd, w.ludiag, stream_);
-        else launch_lu_pack(a, w.dlist, nd2, w.Wd, w.ludiag, stream_);
-        launches_++;
-        if (nd2) HIP_TRY(hipMemcpyAsync(w.h_W, w.Wd, (size_t)(split2 ? nd2 : m) * nd2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipMemcpyAsync(w.h_vec, w.ludiag, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipMemcpyAsync(w.h_idx, w.lpos, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-        if (compressed && m <= 128)   // (the state block was not uploaded in front of this factorization: only the flag comes back)
-            HIP_TRY(hipMemcpyAsync(&w.st_host->lu_singular, &w.st->lu_singular, sizeof(w.st_host->lu_singular), hipMemcpyDeviceToHost, stream_));
-        else
-            HIP_TRY(hipMemcpyAsync(w.st_host, w.st, sizeof(DevState), hipMemcpyDeviceToHost, stream_));
-        return GOMILP_OK;
-    };
-    if (compressed) {
-        // rounds are data dependent (lu_compressed.hip): enqueue a batch, read the control block, repeat.  The first
-        // batch is sized from the number of columns that are dense for sure.
-        const int nb = lu_compressed_nb(m, a.slots != 0);
-        for (int attempt = 0;; attempt++) {
-            launch_luc_init(a, stream_);
-            launches_++;
-            // measured: steps that do arithmetic ~ 3 x the non-unit columns (each of them usually turns a unit column dense)
-            // (the slot panel takes up to nb steps per round whatever the order of the columns; a wrong guess costs one more look at the
-            // control block, a generous one a run of empty rounds)
-            int batch = a.slots ? std::max(1, (std::min(m, (5 * nonunit) / 2) + nb - 1) / nb) : std::max(1, (3 * nonunit + nb - 1) / nb + 1);
-            if (oneshot && GOMILP_DBG_ENV("GOMILP_DEBUG_LU_SHORT")) batch = 1;   // (diagnostic flavour: a first batch that is too short — the small-basis block comes too early and the general path takes over)
-            int enq = 0;   // rounds enqueued so far: the look-ahead schedule keeps two control blocks, by round parity
-            int k_seen = -1;   // steps done when the control block was last read
-            const LUCtl *last = w.luctl_host;
-            for (;;) {
-                launches_ += cross_G ? launch_luc_rounds_cross(a, w.rho, batch, enq, w.luxrec, cross_G, cross_slots, stream_) : launch_luc_rounds(a, w.rho, batch, enq, stream_);
-                enq += batch;
-                if (oneshot) {
-                    launch_luc_pack_small(a, w.Wd, stream_);
-                    launches_++;
-                    HIP_TRY(hipMemcpyAsync(w.h_W, w.Wd, luc_pack_small_bytes(m), hipMemcpyDeviceToHost, stream_));
-                    HIP_TRY(sync_stream());
-                    const double *blk = w.h_W;
-                    const int32_t *io = reinterpret_cast<const int32_t *>(blk + (size_t)m * m + m);
-                    memcpy(w.h_vec, blk + (size_t)m * m, (size_t)m * sizeof(double));   // diag
-                    memcpy(w.h_idx, io, (size_t)m * sizeof(int32_t));                   // lpos
-                    memcpy(h_dense, io + m, (size_t)m * sizeof(int32_t));
-                    memcpy(w.luctl_host, io + 2 * m, 2 * sizeof(LUCtl));
-                    w.st_host->lu_singular = io[2 * m + (int)(2 * sizeof(LUCtl) / sizeof(int32_t))];
-                    dl.resize(m);
-                    for (int k = 0; k < m; k++) dl[k] = k;
-                } else {
-                    HIP_TRY(hipMemcpyAsync(w.luctl_host, w.luctl, 2 * sizeof(LUCtl), hipMemcpyDeviceToHost, stream_));
-                    // the dense-step flags ride along (final once k_next == m): no separate round trip for them
-                    HIP_TRY(hipMemcpyAsync(h_dense, w.denseflag, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-                    HIP_TRY(sync_stream());
-                }
-                last = w.luctl_host + (a.look ? ((enq - 1) & 1) : 0);
-                if (w.luctl_host[0].fault || last->k_next >= m) break;
-                // (every round performs at least the step it starts at — a listed column or a bookkeeping step; a batch that moved nothing
-                // would repeat for ever: report it instead)
-                if (last->k_next <= k_seen) return GOMILP_ERR_DEVICE;
-                k_seen = last->k_next;
-                oneshot = false;   // (the batch was too short: that pack came too early)
-                batch = std::max(4, (int)(((int64_t)(m - last->k_next) * last->rounds) / std::max(1, last->k_next)) + 2);
-                if (batch > 64) batch = 64;
-            }
-            lu_rounds_ = last->rounds;
-            if (cross_G && !w.luctl_host[0].fault) { launch_luc_lpos_final(a, stream_); launches_++; }   // (that panel keeps its maps up to the last tied search only)
-            look_slot.drop();   // (the rounds are behind the last sync)
-            if (!w.luctl_host[0].fault) break;
-            // a wait inside a look-ahead launch ran out of patience (its workgroups never became resident together): once more, from the
-            // basis, with the whole update behind each panel
-            // (the cross-workgroup panel under the look-ahead: first the same panel in the plain schedule — the rounds stay what they were —,
-            // then, should its own exchange give up as well, the one-workgroup panel)
-            // (beyond 4096 rows there is no one-workgroup panel: one launch per column from the basis, in this call)
-            if (attempt > 1 || !(a.look || cross_G)) return GOMILP_ERR_DEVICE;
-            if (a.look) a.look = 0; else cross_G = 0;
-            if (large) { compressed = blocked = false; a.dense_flag = nullptr; }
-            oneshot = false;
-            lu_look_faults_++; lu_look_fault_++;
-            if (w.luxrec) HIP_TRY(hipMemsetAsync(w.luxrec, 0, luc_cross_doubles() * sizeof(double), stream_));   // (a launch that gave up has not recorded how far its sequence numbers went)
-            if (GOMILP_DBG_ENV("GOMILP_DEBUG_LOOP")) fprintf(stderr, "final_solve: a look-ahead launch gave up a wait (m %d, rounds enqueued %d, cnt_x %u cnt_u %u cnt_s %u): plain schedule\n", m, enq, w.luctl_host[0].cnt_x, w.luctl_host[0].cnt_u, w.luctl_host[0].cnt_s);
-            if (compressed != transpose) launch_luc_gather(P.dAt, P.ld, m, w.basic, w.W, ldw, stream_);
-            else {
-                if (transpose) HIP_TRY(hipMemsetAsync(w.W, 0, (size_t)m * ldw * sizeof(double), stream_));
-                launch_gather_w(P.dAt, P.ld, m, w.basic, w.W, ldw, stream_);
-            }
-            if (!compressed) { lu_rounds_ = 0; sync_state_to_device(); launch_lu(a, stream_); launches_ += m + 2; break; }
-        }
-    } else if (blocked) launches_ += launch_lu_blocked(a, w.rho, stream_) + 1;
-    else { launch_lu(a, stream_); launches_ += m + 2; }
-    // Only the columns whose elimination step did arithmetic carry non-zero L / off-diagonal U entries (a unit-column
-    // step has zero multipliers and its column is zero in every earlier pivot row), so the host solves need those
-    // columns and the diagonal only: m*(nd+1) doubles cross PCIe instead of m*m.
-    int nd;
-    bool split;
-    int ndense = 0;   // steps that did arithmetic (stats)
-    if (oneshot) {    // everything is on the host already
-        nd = m; split = false;
-        for (int k = 0; k < m; k++) ndense += h_dense[k] != 0;
-    } else {
-        dl.clear();
-        if (blocked) {
-            if (!compressed) {
-                HIP_TRY(hipMemcpyAsync(h_dense, w.denseflag, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-                HIP_TRY(sync_stream());
-            }
-            for (int k = 0; k < m; k++) if (h_dense[k]) dl.push_back(k);
-        } else {
-            for (int k = 0; k < m; k++) dl.push_back(k);
-        }
-        nd = (int)dl.size();
-        ndense = nd;
-        // large bases: only the nd x nd part that couples the dense positions goes to the host (lu_compressed.hip,
-        // k_luc_pack_dense / k_luc_solve_rows); small ones take one host pass over all rows (one round trip fewer)
-        split = compressed && m >= 1024 && nd > 0;
-        int rcp = enqueue_pack(nd);
-        if (rcp != GOMILP_OK) return rcp;
-        HIP_TRY(sync_stream());
-    }
-    lu_dense_ = ndense;
-    HIP_TRY(hipGetLastError());
-    const double tf1 = now_s();
-    fs_device_ += tf1 - tf0;
-    std::vector<int32_t> phys(m);
-    for (int R = 0; R < m; R++) phys[w.h_idx[R]] = R;
-    const double *diag = w.h_vec;
-    // LU.Det() == 0 (mat/lu.go:301, :118-135): exp(sum log|u_ii|) == 0.  The sum of the binary exponents brackets it ( |u| in
-    // [2^(e-1), 2^e) ): only a product that could underflow (or a zero / NaN on the diagonal) pays for the m logarithms in gonum's order.
-    double logdet = 0;
-    {
-        long long esum = 0;
-        bool plain = true;
-        for (int i = 0; i < m; i++) {
-            int e = 0;
-            const double d = diag[i];
-            if (!(fabs(d) > 0) || !std::isfinite(d)) { plain = false; break; }
-            (void)frexp(d, &e);
-            esum += e;
-        }
-        // sum log|u_ii| >= (esum - m) ln 2, minus rounding of m additions; exp() is zero below -745.14
-        if (plain && (double)(esum - m) * 0.6931471805599453 > -700.0) logdet = 0;   // (exp(logdet) != 0 for sure; the value itself is not used)
-        else for (int i = 0; i < m; i++) logdet += log(fabs(diag[phys[i]]));
-    }
-    *singular = w.st_host->lu_singular != 0 || exp(logdet) == 0;
-    if (*singular && GOMILP_DBG_ENV("GOMILP_DEBUG_LOOP")) {
-        int nz = 0; double dmin = 1e300;
-        for (int i = 0; i < m; i++) { if (diag[phys[i]] == 0) nz++; dmin = std::min(dmin, fabs(diag[phys[i]])); }
-        fprintf(stderr, "final_solve: singular (transpose %d, m %d, nd %d, rounds %lld, lu_singular flag %d, logdet %g, zero diagonals %d, min |u_ii| %g, compressed %d)\n",
-                (int)transpose, m, nd, (long long)lu_rounds_, (int)w.st_host->lu_singular, logdet, nz, dmin, (int)compressed);
-    }
-    lu_cache_.m = m; lu_cache_.nd = nd; lu_cache_.split = split; lu_cache_.singular = *singular;
-    lu_cache_.phys = phys; lu_cache_.dl = dl;
-    lu_cache_.diag.assign(diag, diag + m);   // (h_vec is everybody's landing buffer)
-    lu_cache_.args = a;
-    lu_cache_.valid = true;
-    fs_host_ += now_s() - tf1;
-    return GOMILP_OK;
-}
-
-// The solve half (Dgetrs, lapack/gonum/dgetrs.go:37-45) from the factors lu_factor left: rhs_host (m entries, by basis position;
-// default b).  A singular factorization gives zeros (the caller has the flag).
-int Engine::lu_solve(const Problem &P, std::vector<double> &x, const double *rhs_host) {
-    Work &w = *w_;
-    if (!lu_cache_.valid || lu_cache_.m != P.m) return GOMILP_ERR_DEVICE;
-    const double tf1 = now_s();
-    const int m = P.m, nd = lu_cache_.nd;
-    const bool split = lu_cache_.split;
-    const std::vector<int32_t> &phys = lu_cache_.phys, &dl = lu_cache_.dl;
-    const double *diag = lu_cache_.diag.data();
-    const LUArgs &a = lu_cache_.args;
-    const double *rhs = rhs_host ? rhs_host : P.hb.data();
-    x.assign(m, 0.0);
-    if (lu_cache_.singular) return GOMILP_OK;
-    auto term = [](double bi, double va, double xk) { return va != 0 ? (-va) * xk + bi : bi; };
-    if (split) {
-        const double *rhs_dev = P.db;
-        if (rhs_host) {   // the row kernel reads the right-hand side on the device
-            int rcr = stage_upload(w.move, rhs_host, (size_t)m * sizeof(double));
-            if (rcr != GOMILP_OK) return rcr;
-            rhs_dev = w.move;
-        }
-        // coupled part on the host: row s of h_W is dense position dl[s] restricted to the dense columns
-        std::vector<double> xdl(nd), xdu(nd);
-        // Dtrsm(Left, Lower, NoTrans, Unit): a row is one chain of dependent rounded additions in ascending t; four rows run side by
-        // side over the part of the solution that is known before the first of them, then finish one after the other
-        int s2 = 0;
-        for (; s2 + 4 <= nd; s2 += 4) {
-            const double *r0 = w.h_W + (size_t)s2 * nd, *r1 = r0 + nd, *r2 = r1 + nd, *r3 = r2 + nd;
-            double b0 = rhs[phys[dl[s2]]], b1 = rhs[phys[dl[s2 + 1]]], b2 = rhs[phys[dl[s2 + 2]]], b3 = rhs[phys[dl[s2 + 3]]];
-            for (int t = 0; t < s2; t++) {
-                const double xk = xdl[t];
-                b0 = term(b0, r0[t], xk); b1 = term(b1, r1[t], xk); b2 = term(b2, r2[t], xk); b3 = term(b3, r3[t], xk);
-            }
-            xdl[s2] = b0;
-            b1 = term(b1, r1[s2], b0); xdl[s2 + 1] = b1;
-            b2 = term(b2, r2[s2], b0); b2 = term(b2, r2[s2 + 1], b1); xdl[s2 + 2] = b2;
-            b3 = term(b3, r3[s2], b0); b3 = term(b3, r3[s2 + 1], b1); b3 = term(b3, r3[s2 + 2], b2); xdl[s2 + 3] = b3;
-        }
-        for (; s2 < nd; s2++) {
-            const double *row = w.h_W + (size_t)s2 * nd;
-            double bi = rhs[phys[dl[s2]]];
-            for (int t = 0; t < s2; t++) bi = term(bi, row[t], xdl[t]);
-            xdl[s2] = bi;
-        }
-        for (int s2 = nd - 1; s2 >= 0; s2--) {   // Dtrsm(Left, Upper, NoTrans, NonUnit)
-            const double *row = w.h_W + (size_t)s2 * nd;
-            double bi = xdl[s2];
-            for (int t = s2 + 1; t < nd; t++) bi = term(bi, row[t], xdu[t]);
-            const double tinv = 1 / diag[phys[dl[s2]]];
-            xdu[s2] = bi * tinv;
-        }
-        fs_host_ += now_s() - tf1;
-        const double tf2 = now_s();
-        double *dxl = w.yscratch, *dxu = w.yscratch + P.ld, *dx = w.yscratch + 2 * (size_t)P.ld;   // 64 * ld doubles
-        int rcs = stage_upload(dxl, xdl.data(), (size_t)nd * sizeof(double));
-        if (rcs == GOMILP_OK) rcs = stage_upload(dxu, xdu.data(), (size_t)nd * sizeof(double));
-        if (rcs != GOMILP_OK) return rcs;
-        launch_luc_solve_rows(a, w.dlist, nd, rhs_dev, dxl, dxu, dx, stream_);
-        launches_++;
-        HIP_TRY(hipMemcpyAsync(w.h_vec, dx, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(sync_stream());
-        HIP_TRY(hipGetLastError());
-        for (int i = 0; i < m; i++) x[i] = w.h_vec[i];
-        for (int s2 = 0; s2 < nd; s2++) x[dl[s2]] = xdu[s2];
-        fs_device_ += now_s() - tf2;
-        return GOMILP_OK;
-    }
-    // Dlaswp: b in logical row order
-    for (int i = 0; i < m; i++) x[i] = rhs[phys[i]];
-    // The two Dtrsm of Dgetrs, per row in gonum's order: ascending k, zero multipliers skipped, b_i = (-a_ik)*b_k + b_i
-    // as a rounded multiply and a rounded add (level3double.go:75-118).  Only the nd columns whose elimination step did
-    // arithmetic carry off-diagonal entries, so a row depends on the solution at those "dense" positions only: they are
-    // solved first, one after the other; every other row is then independent of the rest and four of them run
-    // interleaved (each row is one chain of dependent rounded additions: a single chain leaves the FPU idle).
-    std::vector<double> xd(nd);
-    std::vector<char> isd(m, 0);
-    for (int t = 0; t < nd; t++) isd[dl[t]] = 1;
-    std::vector<int> nl;   // logical positions that are not dense, ascending
-    nl.reserve(m - nd);
-    for (int i = 0; i < m; i++) if (!isd[i]) nl.push_back(i);
-    // ---- Dtrsm(Left, Lower, NoTrans, Unit)
-    for (int s2 = 0; s2 < nd; s2++) {
-        const int i = dl[s2];
-        const double *row = w.h_W + (size_t)phys[i] * nd;
-        double bi = x[i];
-        for (int t = 0; t < s2; t++) bi = term(bi, row[t], xd[t]);
-        x[i] = bi; xd[s2] = bi;
-    }
-    {
-        size_t g = 0;
-        int cnt = 0;   // dense positions below the current row
-        for (; g + 4 <= nl.size(); g += 4) {
-            int c[4];
-            const double *row[4];
-            double acc[4];
-            for (int r = 0; r < 4; r++) {
-                const int i = nl[g + r];
-                while (cnt < nd && dl[cnt] < i) cnt++;
-                c[r] = cnt; row[r] = w.h_W + (size_t)phys[i] * nd; acc[r] = x[i];
-            }
-            const int c0 = c[0];   // c[0] <= c[1] <= c[2] <= c[3]
-            for (int t = 0; t < c0; t++) {
-                const double xk = xd[t];
-                acc[0] = term(acc[0], row[0][t], xk); acc[1] = term(acc[1], row[1][t], xk);
-                acc[2] = term(acc[2], row[2][t], xk); acc[3] = term(acc[3], row[3][t], xk);
-            }
-            for (int r = 1; r < 4; r++)
-                for (int t = c0; t < c[r]; t++) acc[r] = term(acc[r], row[r][t], xd[t]);
-            for (int r = 0; r < 4; r++) x[nl[g + r]] = acc[r];
-        }
-        for (; g < nl.size(); g++) {
-            const int i = nl[g];
-            while (cnt < nd && dl[cnt] < i) cnt++;
-            const double *row = w.h_W + (size_t)phys[i] * nd;
-            double bi = x[i];
-            for (int t = 0; t < cnt; t++) bi = term(bi, row[t], xd[t]);
-            x[i] = bi;
-        }
-    }
-    // ---- Dtrsm(Left, Upper, NoTrans, NonUnit): rows from the bottom, ascending k within a row, then * (1/u_ii)
-    for (int s2 = nd - 1; s2 >= 0; s2--) {
-        const int i = dl[s2];
-        const double *row = w.h_W + (size_t)phys[i] * nd;
-        double bi = x[i];
-        for (int t = s2 + 1; t < nd; t++) bi = term(bi, row[t], xd[t]);
-        const double tinv = 1 / diag[phys[i]];
-        x[i] = bi * tinv; xd[s2] = x[i];
-    }
-    {
-        size_t g = 0;
-        int first = 0;   // first dense position above the current row
-        for (; g + 4 <= nl.size(); g += 4) {
-            int f[4];
-            const double *row[4];
-            double acc[4];
-            for (int r = 0; r < 4; r++) {
-                const int i = nl[g + r];
-                while (first < nd && dl[first] < i) first++;
-                f[r] = first; row[r] = w.h_W + (size_t)phys[i] * nd; acc[r] = x[i];
-            }
-            const int f3 = f[3];   // f[0] <= f[1] <= f[2] <= f[3]: the leading terms of rows 0..2 come first, in order
-            for (int r = 0; r < 3; r++)
-                for (int t = f[r]; t < f3; t++) acc[r] = term(acc[r], row[r][t], xd[t]);
-            for (int t = f3; t < nd; t++) {
-                const double xk = xd[t];
-                acc[0] = term(acc[0], row[0][t], xk); acc[1] = term(acc[1], row[1][t], xk);
-                acc[2] = term(acc[2], row[2][t], xk); acc[3] = term(acc[3], row[3][t], xk);
-            }
-            for (int r = 0; r < 4; r++) {
-                const int i = nl[g + r];
-                const double tinv = 1 / diag[phys[i]];
-                x[i] = acc[r] * tinv;
-            }
-        }
-        for (; g < nl.size(); g++) {
-            const int i = nl[g];
-            while (first < nd && dl[first] < i) first++;
-            const double *row = w.h_W + (size_t)phys[i] * nd;
-            double bi = x[i];
-            for (int t = first; t < nd; t++) bi = term(bi, row[t], xd[t]);
-            const double tinv = 1 / diag[phys[i]];
-            x[i] = bi * tinv;
-        }
-    }
-    fs_host_ += now_s() - tf1;
-    return GOMILP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
 // simplex() — simplex.go:93-302
 // ------------------------------------------------------------------------------------------------
 int Engine::solve(int64_t id, double tol, const int64_t *initial_basic, double *opt_f, double *opt_x, int32_t *has_x,
@@ -1355,7 +922,7 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
         for (int j = 0; j < n; j++) ident[j] = j;
         if ((rc = upload_index_lists(ident, {})) != GOMILP_OK) return finish(rc);
         const double t1 = now_s();
-        if ((rc = final_solve(P, n, xb_exact, &singular)) != GOMILP_OK) return finish(rc);
+        if ((rc = final_solve(P, xb_exact, &singular)) != GOMILP_OK) return finish(rc);
         st->seconds_final_solve = now_s() - t1;
         if (singular) return finish(GOMILP_ERR_SINGULAR);
         if (cond_guard_ && !P.hA.empty() && n <= 1024) {   // cond > 1e16 is a Condition too: lp.ErrSingular (simplex.go:109-112)
@@ -1447,7 +1014,7 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
         // simplex.go:459-469 then sees the same bits
         if ((rc = upload_index_lists(basic, {})) != GOMILP_OK) return finish(rc);
         bool sing = false;
-        if ((rc = final_solve(P, n, xb_exact, &sing)) != GOMILP_OK) return finish(rc);
+        if ((rc = final_solve(P, xb_exact, &sing)) != GOMILP_OK) return finish(rc);
         if (sing) { feasible = false; }  // "singular" also sends the reference to Phase I (simplex.go:504-507), xb stays zero
         else { xb = xb_exact; for (int pos = 0; pos < m; pos++) if (xb[pos] < -1e-13) feasible = false; }
         if (initial_basic && !feasible) return finish(GOMILP_ERR_PANIC);  // initializeFromBasic errors panic (:156-158)
@@ -1587,7 +1154,7 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
         double xart = added >= 0 ? xb[added] : 0.0;
         if (added >= 0 && fabs(xart) > 1e-13 && fabs(xart) < 1e-11) {
             // too close to phaseIZeroTol to trust the updated x_B: take the reference's own value (fresh gonum-order solve)
-            if ((rc = final_solve(P, n + 1, xb_exact, &singular)) != GOMILP_OK) return finish(rc);
+            if ((rc = final_solve(P, xb_exact, &singular)) != GOMILP_OK) return finish(rc);
             if (!singular) xart = xb_exact[added];
         }
         if (fabs(xart) > 1e-12) return finish(GOMILP_ERR_INFEASIBLE);  // phaseIZeroTol, :563-565
@@ -1719,7 +1286,7 @@ int Engine::epilogue(const Problem &P, std::vector<int32_t> &basic, std::vector<
     std::vector<double> xb_exact;
     bool singular = false;
     const double t1 = now_s();
-    int rc = final_solve(P, n, xb_exact, &singular, basic.data());
+    int rc = final_solve(P, xb_exact, &singular, basic.data());
     if (rc != GOMILP_OK) return rc;
     st->seconds_final_solve = now_s() - t1;
     if (singular) {
@@ -1799,7 +1366,7 @@ bool Engine::root_general(int64_t id, RootView *out) {
     // x_B of the basis with the reference's own arithmetic (as Engine::solve does for the feasibility test)
     std::vector<double> xb;
     bool sing = false;
-    if (final_solve(P, n, xb, &sing, basic.data()) != GOMILP_OK || sing) return false;
+    if (final_solve(P, xb, &sing, basic.data()) != GOMILP_OK || sing) return false;
     std::shared_ptr<RootView::General> G(new RootView::General);
     G->m = m; G->nn = nn; G->ldt = tab_ld(nn);
     auto ok = [](hipError_t e) { return e == hipSuccess; };

@@ -51,6 +51,30 @@ struct Problem {
     std::vector<double> ksign;
 };
 
+// Which kernels one factorization of the final solve runs (engine_final.cpp): decided once, at the top of Engine::lu_factor, from the row
+// count, the knobs lu_blocked / lu_look / lu_cross / lu_large / bt_fault and the capacity of the buffer the small pack lands in —
+// before anything is launched or acquired.  Afterwards only two things change it: the loop slots that could not be had
+// (look_wanted) and step_down().
+struct LuPlan {
+    int m = 0;
+    bool compressed = false;    // the compressed rounds (lu_compressed.hip, L/U column-major); else L/U row-major:
+    bool blocked = false;       //   the blocked panels (lu_kernels.hip), or — neither — one launch per column.  Both skip unit-column steps
+    bool large = false;         // knob lu_large: the compressed rounds on the eight-workgroup panel with several rows per lane
+    bool small = false;         // compressed, few rows: k_luc_init clears the singular flag on the device and only the flag comes back
+    bool look_wanted = false;   // the look-ahead schedule (LUArgs::look), while the engine holds the device's loop slots
+    int cross_G = 0;            // workgroups of the cross-workgroup panel (lu_cross.hip); 0: the one-workgroup panel
+    int cross_slots = 16;       // its register slots, 16 or 32
+    bool oneshot = false;       // one batch of rounds and the small pack (k_luc_pack_small) in one host round trip
+    bool inject_fault = false;  // diagnostic flavour, knob bt_fault = 2 (LUArgs::pad3)
+    int steps_down = 0;
+    // large bases: only the nd x nd part that couples the dense positions goes to the host (lu_compressed.hip,
+    // k_luc_pack_dense / k_luc_solve_rows); small ones take one host pass over all rows (one round trip fewer)
+    bool split(int nd) const { return compressed && m >= 1024 && nd > 0; }
+    static LuPlan make(int m, int64_t lu_blocked, int64_t lu_look, int64_t lu_cross, int64_t lu_large, int64_t bt_fault, size_t small_pack_cap_bytes);
+    bool step_down();   // after a launch gave up a wait: the next plainer schedule (false: there is none)
+};
+struct LuRoundsEnd { bool gave_up = false, landed = false; int enq = 0; };   // Engine::run_compressed_rounds
+
 class Engine {
    public:
     explicit Engine(int device);
@@ -176,11 +200,19 @@ class Engine {
     int refresh_xb_y(const Problem &P, const double *cost);
     int epilogue(const Problem &P, std::vector<int32_t> &basic, std::vector<double> &xb, int loop_rc, double *opt_f, double *opt_x,
                  int32_t *has_x, int64_t *basis_out, gomilp_lp_stats *st);
-    int final_solve(const Problem &P, int ncols_rows, std::vector<double> &xb_exact, bool *singular, const int32_t *basic_host = nullptr,
+    // the bit-exact final solve (engine_final.cpp)
+    int final_solve(const Problem &P, std::vector<double> &xb_exact, bool *singular, const int32_t *basic_host = nullptr,
                     bool transpose = false, const double *rhs_host = nullptr);
-    // its two halves (engine.cpp): one factorization, any number of right-hand sides
+    // its two halves: one factorization, any number of right-hand sides
     int lu_factor(const Problem &P, bool *singular, const int32_t *basic_host = nullptr, bool transpose = false);
     int lu_solve(const Problem &P, std::vector<double> &x, const double *rhs_host = nullptr);
+    // the steps of lu_factor
+    int gather_basis(const Problem &P, const LuPlan &plan, bool transpose);
+    int upload_unit_rows(const Problem &P, const int32_t *basic_host, bool transpose, int *nonunit);
+    int run_compressed_rounds(const LUArgs &a, const LuPlan &plan, int nonunit, LuRoundsEnd *end);
+    int pack_and_fetch(const LUArgs &a, const LuPlan &plan, std::vector<int32_t> &dl);
+    // What lu_solve needs of the last factorization, besides the packed factors themselves: those stay where lu_factor landed them, in
+    // Work::h_W (m x nd by physical row; split: nd x nd by dense position), between lu_factor and any number of lu_solve calls.
     struct LuCache {
         bool valid = false, split = false, singular = false;
         int m = 0, nd = 0;
@@ -402,7 +434,7 @@ bool lu_blocked_supported(int m);
 int launch_lu_blocked(const LUArgs &a, int32_t *pivrow, hipStream_t s);
 // lu_compressed.hip
 bool lu_compressed_supported(int m, bool large);   // large: knob lu_large (4097 .. 16384 rows: lu_cross.hip luc_large_rpt)
-int lu_compressed_nb(int m, bool slots);
+int lu_compressed_nb();   // dense steps a round can take
 void launch_luc_init(const LUArgs &a, hipStream_t s);
 int launch_luc_rounds(const LUArgs &a, int32_t *pivrow, int nrounds, int round_base, hipStream_t s);
 void launch_luc_gather(const double *At, int ld, int m, const int32_t *basic, double *W, int ldw, hipStream_t s);

@@ -372,7 +372,7 @@ int Engine::exact_iter(const Problem &P, int phase, double tol, int nn, double *
     for (int i = 0; i < m; i++) cb[i] = cost(basic[i]);
     bool sing = false;
     int rc;
-    if ((rc = final_solve(P, n, y, &sing, basic.data(), true, cb.data())) != GOMILP_OK) return -rc;
+    if ((rc = final_solve(P, y, &sing, basic.data(), true, cb.data())) != GOMILP_OK) return -rc;
     if (sing) { if (GOMILP_DBG_ENV("GOMILP_DEBUG_LOOP")) fprintf(stderr, "exact_step: ab^T singular (phase %d, m %d)\n", phase, m); return -GOMILP_ERR_LINSOLVE; }
     {
         std::vector<double> ypad(P.ld, 0.0);
@@ -387,7 +387,7 @@ int Engine::exact_iter(const Problem &P, int phase, double tol, int nn, double *
     for (int j = 0; j < nn; j++) r[j] = w.h_vec[j];
     // x_B of this iteration (simplex.go:289 of the previous one): resident from here on
     // (ONE factorization of ab serves x_B, the entering column and every Bland candidate below: the reference factors the same matrix
-    // again each time, simplex.go:289 / :315 / :356 — same bits; Engine::lu_factor / lu_solve)
+    // again each time, simplex.go:289 / :315 / :356 — same bits; Engine::lu_factor / lu_solve, engine_final.cpp)
     if ((rc = lu_factor(P, &sing, basic.data())) != GOMILP_OK) return -rc;
     if (sing) { if (GOMILP_DBG_ENV("GOMILP_DEBUG_LOOP")) fprintf(stderr, "exact_step: ab singular for x_B (phase %d, m %d)\n", phase, m); return -GOMILP_ERR_LINSOLVE; }
     if ((rc = lu_solve(P, xb)) != GOMILP_OK) return -rc;
@@ -853,7 +853,7 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
         if (added >= 0 && fabs(xart) > 1e-13 && fabs(xart) < 1e-11) {
             std::vector<double> xe;
             bool sing = false;
-            if ((rc = final_solve(P, n + 1, xe, &sing)) != GOMILP_OK) return rc;
+            if ((rc = final_solve(P, xe, &sing)) != GOMILP_OK) return rc;
             if (!sing) xart = xe[added];
         }
         if (fabs(xart) > 1e-12) return GOMILP_ERR_INFEASIBLE;  // phaseIZeroTol, :563-565

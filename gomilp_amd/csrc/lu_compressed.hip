@@ -742,7 +742,7 @@ int launch_luc_rounds_cross(const LUArgs &base, int32_t *pivrow, int nrounds, in
 
 bool lu_compressed_supported(int m, bool large) { return m <= 4096 || (large && luc_large_rpt(m) > 0); }   // (large: knob lu_large)
 // dense steps a round can take (the host sizes its batches of rounds with it)
-int lu_compressed_nb(int, bool) { return kLucSlotSteps; }
+int lu_compressed_nb() { return kLucSlotSteps; }
 
 void launch_luc_init(const LUArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_luc_init, dim3((a.m + 255) / 256), dim3(256), 0, s, a);

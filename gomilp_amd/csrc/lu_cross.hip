@@ -29,7 +29,7 @@
 //      loads and the unit columns of rows still active when the round before ended (the only columns this panel writes: a listed column,
 //      or the unit column of the row a dense step takes), and every read of the round's pivot rows in phase U's columns is behind cnt_s
 //      before workgroup 0 writes their U entries.
-// Fall-backs (engine.cpp lu_factor, one stats.device_retries each): a look-ahead launch that gave up a wait -> the SAME panel in the plain
+// Fall-backs (engine_final.cpp LuPlan::step_down, one stats.device_retries each): a look-ahead launch that gave up a wait -> the SAME panel in the plain
 // schedule (the rounds stay what they were); an exchange of the panel that gave up -> the one-workgroup panel.
 // Bases of 4097 .. 16384 rows (knob lu_large, off by default): k_luc_panel_xl below, the same panel with four or eight rows per lane; an
 // exchange that gave up there -> one launch per column (there is no one-workgroup panel at these sizes).

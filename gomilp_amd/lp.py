@@ -72,7 +72,7 @@ class FrontierStats(C.Structure):
 
 EXPORTS = [
     "gomilp_lp_solve_warm", "gomilp_frontier_solve_warm", "gomilp_pool_release_warm",
-    "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond",
+    "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond", "gomilp_debug_lu_host_solve",
     "gomilp_lp_simplex", "gomilp_ctx_create", "gomilp_ctx_destroy", "gomilp_ctx_device", "gomilp_ctx_set",
     "gomilp_lp_upload", "gomilp_lp_free", "gomilp_lp_solve_resident", "gomilp_lp_last_trace", "gomilp_version",
     "gomilp_device_count", "gomilp_compiled_arch", "gomilp_comm_unique_id", "gomilp_comm_create", "gomilp_comm_destroy",
@@ -130,6 +130,8 @@ def lib():
     L.gomilp_debug_cond_estimate.argtypes = [dp, C.c_int64, C.c_int]
     L.gomilp_debug_gonum_lu_cond.restype = C.c_int
     L.gomilp_debug_gonum_lu_cond.argtypes = [dp, C.c_int64, C.c_int, C.POINTER(C.c_double)]
+    L.gomilp_debug_lu_host_solve.restype = C.c_int
+    L.gomilp_debug_lu_host_solve.argtypes = [C.c_int64, C.c_int64, i32p, i32p, dp, dp, C.c_int, dp, dp]
     L.gomilp_debug_find_independent.restype = C.c_int64
     L.gomilp_debug_find_independent_device.restype = C.c_int64
     L.gomilp_debug_find_independent_device.argtypes = [C.c_void_p, C.c_int64, ip, C.c_int64]
@@ -549,6 +551,24 @@ def debug_gonum_lu_cond(M, transposed: bool = False):
     if rc < 0:
         raise ValueError("n out of range")
     return float(c.value), bool(rc)
+
+
+def debug_lu_host_solve(dl, phys, diag, W, rhs, coupled: bool = False):
+    """(x, det_is_zero): the host half of the final solve (gomilp_amd/csrc/lu_host.cpp) on packed LU factors — m entries by basis
+    position, or the nd entries at the positions dl when `coupled` (W then nd x nd) — host only (no device)."""
+    dl = np.ascontiguousarray(dl, dtype=np.int32)
+    phys = np.ascontiguousarray(phys, dtype=np.int32)
+    diag = np.ascontiguousarray(diag, dtype=np.float64)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+    m, nd = phys.size, dl.size
+    assert diag.shape == (m,) and rhs.shape == (m,) and W.shape == ((nd if coupled else m), nd)
+    x = np.zeros(nd if coupled else m)
+    i32p = C.POINTER(C.c_int32)
+    rc = lib().gomilp_debug_lu_host_solve(m, nd, dl.ctypes.data_as(i32p), phys.ctypes.data_as(i32p), _dp(diag), _dp(W), 1 if coupled else 0, _dp(rhs), _dp(x))
+    if rc < 0:
+        raise ValueError("bad shape")
+    return x, bool(rc)
 
 
 def debug_cond_estimate(B, inf: bool = False) -> float:

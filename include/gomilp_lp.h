@@ -363,6 +363,14 @@ double gomilp_debug_cond_estimate(const double *B, int64_t n, int inf);
  * Det() == 0 test fires (mat/lu.go:301), 0 when not, -1 for n out of range.  The host replay of the reference's guards for bases of up
  * to 64 rows uses exactly this (engine_general.cpp general_condition_replay); tests compare it with the checker's restatement. */
 int gomilp_debug_gonum_lu_cond(const double *M, int64_t n, int transposed, double *cond);
+/* Diagnostic (host only): the host half of the bit-exact final solve on packed LU factors (gomilp_amd/csrc/lu_host.h) — Dlaswp and the two
+ * Dtrsm of Dgetrs (lapack/gonum/dgetrs.go:37-45) in gonum's rounding order.  dl: the nd logical positions (ascending) whose column of the
+ * in-place L\U has off-diagonal entries; phys[i]: the physical row at logical position i; diag[R]: u_ii of physical row R; rhs: m entries
+ * by physical row.  coupled = 0: W is m x nd (row R: those columns of physical row R), x gets m entries by logical position.  coupled = 1:
+ * W is nd x nd (row s: logical position dl[s] restricted to those columns), x gets the nd entries of the solution at dl.  Returns 1 when
+ * LU.Solve's Det() == 0 test fires (mat/lu.go:301; x is zeroed), 0 when not, -1 for bad arguments.  Tests compare it with the checker's SolveVec. */
+int gomilp_debug_lu_host_solve(int64_t m, int64_t nd, const int32_t *dl, const int32_t *phys, const double *diag, const double *W, int coupled,
+                               const double *rhs, double *x);
 
 /* Library / device probes (no compute): used by the loader checks and by __graft_entry__. */
 const char *gomilp_version(void);
