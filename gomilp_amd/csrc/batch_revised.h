@@ -1,7 +1,8 @@
 // Device-batched revised simplex (batch_revised.hip, engine_batch_revised.cpp): the three-kernel revised simplex of
 // simplex_kernels.hip with the relaxation as blockIdx.y.  One RevLP per relaxation of a wave, resident in HBM: it plays the role
 // of LPArgs (the pointers), carries the relaxation's stage and its ping-pong parity, and takes the work orders that the control
-// kernels write for the set-up launches of the next superstep.  The host enqueues a fixed list of launches per superstep and looks
+// kernels write for the set-up launches of the next superstep.  The relaxations of a wave may be children of several roots: every
+// kernel reads its relaxation's shape and pointers from its RevLP, the grids are sized for the wave's largest shape.  The host enqueues a fixed list of launches per superstep and looks
 // at one small record per relaxation afterwards.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,7 +33,7 @@ enum : int32_t { RR_NONE = 0, RR_LOOP = 1, RR_FORCED = 2, RR_DUAL = 3, RR_EXCH =
 
 struct RevLP {
     // ---- fixed for the wave (written by the host) ----
-    double *At;              // (n + 1) x ld: row j = column j of the child's A (k_child_assemble), row n = the Phase-I artificial
+    double *At;              // (n + 1) x ld: row j = column j of the child's A (k_rv_assemble), row n = the Phase-I artificial
     const double *c2;        // Phase-II cost [c0, 0, ...] (at least n + 1 entries)
     double *c1;              // Phase-I cost: e_n (n + 1 entries, written by k_rv_init)
     double *b;               // ld, zero padded
@@ -44,7 +45,7 @@ struct RevLP {
     DevState *st;
     const double *b0, *rhs;  // root right-hand side (m0), the child's branch right-hand sides (K)
     const int32_t *rho0;     // m0: row of the 1 in root column n0 - 1 - pos
-    int32_t m0, n0, K, m, n, ld;
+    int32_t m0, n0, K, m, n, ld;   // (m0 / n0, b0 / c2 / rho0: of the relaxation's OWN root — a wave may hold children of several roots)
     int64_t max_pivots;      // pool knob max_pivots (0: none)
     double tol_user;         // Phase-II tolerance of the call
     // ---- state (device) ----
@@ -80,6 +81,12 @@ struct RevLP {
     int32_t exch_on, x_added;
     unsigned int x_best;
     int32_t exch;
+    // ---- what k_rv_assemble builds At from (written by the host; at the tail, for the same reason): the relaxation's own root — its
+    // resident At0 with row stride ld0 (m0 / n0 above) — and its K branch rows' variables and signs
+    const double *At0;
+    const double *asign;
+    const int32_t *avar;
+    int32_t ld0, pad3;
 };
 
 // what the host reads of every active relaxation after a superstep
@@ -92,6 +99,9 @@ struct RevOut {
 
 // launches (batch_revised.hip).  act: list positions -> relaxation; nact entries.  gp / gr: workgroups per relaxation of the pricing
 // kernel and of the row kernels (grid_for_rows of the wave's largest nn / m); lds: bytes of the largest staged vector.
+// the whole wave's At in one launch, in front of launch_rv_init: grid (n_max + 1 child columns, count relaxations); writes what
+// k_child_assemble (simplex_kernels.hip) writes per child
+void launch_rv_assemble(const RevLP *lps, int count, int n_max, hipStream_t s);
 void launch_rv_init(RevLP *lps, int count, hipStream_t s);
 void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, hipStream_t s);   // forced pivot, lists, refresh, check: 7 launches
 void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, hipStream_t s);               // Bland step?, K1, K2, K3: 4 launches

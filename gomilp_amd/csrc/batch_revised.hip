@@ -1,5 +1,5 @@
 // gfx950 (CDNA4, wave64) kernels of the device-batched revised simplex: K1-K3 of simplex_kernels.hip with the relaxation as
-// blockIdx.y, and the small kernels that run a relaxation's stages on the device (slack start, Phase-I set-up, list rebuilds,
+// blockIdx.y, and the small kernels that run a relaxation's stages on the device (assembly of the children, slack start, Phase-I set-up, list rebuilds,
 // refreshes, the Bland rule, the zero-level artificial exchange, the verdicts) so that a wave costs a constant number of host round trips per superstep.
 //
 // The pivot rules, the per-element work and the commit are the helpers of simplex_helpers.h, the code the single-relaxation
@@ -49,6 +49,35 @@ __device__ __forceinline__ void clear_orders(RevLP *d) {
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// At of every relaxation of the wave in one launch (k_child_assemble of simplex_kernels.hip with the relaxation as blockIdx.y;
+// subproblem.go:81-139, :245-255): child A = [[A0, 0], [G#, I_K]], G# row k = sign_k * e_{var_k}, of the relaxation's own root.  In
+// the transposed layout root column j keeps its m0 entries and gains sign_k at the branch rows on it; the K unit columns follow; row n
+// is the zeroed artificial slot.  blockIdx.x = child column, up to the widest relaxation's n: a workgroup past its relaxation's width
+// has nothing to write.  Plain loads and stores, no LDS, no workgroup depends on another.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_rv_assemble(const RevLP *__restrict__ lps) {
+    const RevLP *d = lps + blockIdx.y;
+    const int j = blockIdx.x, n = d->n;
+    if (j > n) return;
+    const int m0 = d->m0, n0 = d->n0, K = d->K, ld = d->ld;
+    double *dst = d->At + (size_t)j * ld;
+    if (j < n0) {
+        const double *src = d->At0 + (size_t)j * d->ld0;
+        const int32_t *var = d->avar;
+        const double *sign = d->asign;
+        for (int i = threadIdx.x; i < ld; i += kBlock) {
+            double v = 0.0;
+            if (i < m0) v = src[i];
+            else if (i < m0 + K && var[i - m0] == j) v = sign[i - m0];
+            dst[i] = v;
+        }
+    } else {
+        const int unit = (j < n0 + K) ? m0 + (j - n0) : -1;
+        for (int i = threadIdx.x; i < ld; i += kBlock) dst[i] = (i == unit) ? 1.0 : 0.0;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // start of a relaxation from its slack basis (Engine::solve_locked, unit-basis branch): b' = [b0; h], x_B = b'[rho], B^-1 = the
@@ -653,6 +682,9 @@ __global__ void k_rv_exch_pick(RevLP *__restrict__ lps, const int *__restrict__ 
 // ------------------------------------------------------------------------------------------------
 // host-callable launch wrappers
 // ------------------------------------------------------------------------------------------------
+void launch_rv_assemble(const RevLP *lps, int count, int n_max, hipStream_t s) {
+    hipLaunchKernelGGL(k_rv_assemble, dim3(n_max + 1, count), dim3(kBlock), 0, s, lps);
+}
 void launch_rv_init(RevLP *lps, int count, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_init, dim3(count), dim3(kBlock), 0, s, lps);
 }

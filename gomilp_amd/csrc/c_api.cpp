@@ -1,6 +1,7 @@
 // extern "C" surface declared in include/gomilp_lp.h.  Each entry point names the reference
 // interface it replaces; see INTEGRATION.md for the cgo binding.
 #include <math.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -60,6 +61,9 @@ struct gomilp_pool {
     int rev_exchange = 1;       // knob: on the batched revised simplex a relaxation whose Phase I ends with the artificial basic at level zero
                                 // exchanges it on the device (batch_revised.hip: k_rv_exch) instead of going to a worker's whole solve — the same
                                 // column, bit-identical results; 0: the hand-over (host_fallbacks)
+    int rev_roots = 1;          // knob: a wide wave that uses several roots, or a root other than the set_root problem (gomilp_frontier_solve_roots),
+                                // runs on the batched revised simplex when every root it uses passes that schedule's test — one schedule for the
+                                // wave, bit-identical results; 0: such a wave on the workers, whole
     int64_t refresh = 0, max_pivots = 0;   // the workers' knobs of these names, as the batched revised simplex needs them
     std::unique_ptr<RevBatchEngine> rev;   // created on first use
     gomilp::WarmStore warm;     // final states kept for warm starts (gomilp_frontier_solve_warm), shared by both schedules
@@ -232,6 +236,7 @@ int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value) {
     if (std::string(key) == "batch_revised") { pool->batch_revised = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "warm_revised") { pool->warm_revised = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "rev_exchange") { pool->rev_exchange = value ? 1 : 0; return GOMILP_OK; }
+    if (std::string(key) == "rev_roots") { pool->rev_roots = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "split_large") { pool->split_large = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "split_phase") { pool->split_phase = value ? 1 : 0; return GOMILP_OK; }
     if (std::string(key) == "batch_virt") {   // wide waves on virtual tableaus for their first block (default 1)
@@ -427,16 +432,28 @@ static int frontier_solve_impl(gomilp_pool *pool, int64_t count, const int32_t *
         if (use_batch && pool->large_loop && need > 1024 && need <= 2048) use_batch = false;
     }
     // Wide waves: the device-batched revised simplex, where every relaxation of the wave is one that a worker's Engine::solve runs on the
-    // revised pipelines without the exact-step guard (one root, slack starts; a periodic refresh stays on the workers).  Cold calls, and
-    // with the knob warm_revised the warm call: relaxations whose parent's kept state is of this schedule start from it (section 2.6b)
+    // revised pipelines without the exact-step guard (slack starts; a periodic refresh stays on the workers).  Cold calls, and with the
+    // knob warm_revised the warm call: relaxations whose parent's kept state is of this schedule start from it (section 2.6b).
+    // The test runs over the roots the WAVE uses, each with the K range of its own children; roots the pool merely holds do not count.
+    // One used root that fails (narrow, no slack basis, a guarded size, a verify verdict) sends the wave where it went before, whole.
     bool use_rev = false;
-    if (!use_batch && pool->batched && pool->batch_revised && count > 0 && (!wa || pool->warm_revised) && nroots == 1 && pool->refresh == 0) {
-        int K_min = K_max;
-        for (int64_t i = 0; i < count; i++) K_min = std::min<int>(K_min, (int)(koff[i + 1] - koff[i]));
-        use_rev = RevBatchEngine::eligible(pool->view, K_min, K_max, pool->exact_degenerate, pool->cond_guard);
-        // (a branch row on one of the root's slack columns: the child has no slack basis)
-        const int64_t first_slack = (int64_t)pool->view.n - pool->view.m;
-        for (int64_t k = koff[0]; k < koff[count] && use_rev; k++) if (var[k] < 0 || var[k] >= first_slack) use_rev = false;
+    if (!use_batch && pool->batched && pool->batch_revised && count > 0 && (!wa || pool->warm_revised) && pool->refresh == 0) {
+        std::vector<int> k_lo((size_t)nroots, INT32_MAX), k_hi((size_t)nroots, -1);
+        bool other_root = false;   // the wave uses more than one root, or a root other than the set_root problem
+        for (int64_t i = 0; i < count; i++) {
+            const int ri = root_of ? root_of[i] : 0, K = (int)(koff[i + 1] - koff[i]);
+            k_lo[(size_t)ri] = std::min(k_lo[(size_t)ri], K); k_hi[(size_t)ri] = std::max(k_hi[(size_t)ri], K);
+            if (ri != 0) other_root = true;
+        }
+        use_rev = pool->rev_roots || !other_root;
+        for (int r = 0; r < nroots && use_rev; r++)
+            if (k_hi[(size_t)r] >= 0) use_rev = RevBatchEngine::eligible(*views[r], k_lo[(size_t)r], k_hi[(size_t)r], pool->exact_degenerate, pool->cond_guard);
+        // (a branch row on one of its root's slack columns: the child has no slack basis)
+        for (int64_t i = 0; i < count && use_rev; i++) {
+            const Engine::RootView &V = *views[root_of ? root_of[i] : 0];
+            const int64_t first_slack = (int64_t)V.n - V.m;
+            for (int64_t k = koff[i]; k < koff[i + 1] && use_rev; k++) if (var[k] < 0 || var[k] >= first_slack) use_rev = false;
+        }
     }
     if (use_rev) {
         if (!pool->rev) pool->rev.reset(new RevBatchEngine(pool->device));
@@ -466,7 +483,7 @@ static int frontier_solve_impl(gomilp_pool *pool, int64_t count, const int32_t *
         if (wa) {
             wspec.store = &pool->warm; wspec.parent = wa->parent; wspec.tag = wa->tag; wspec.keep = wa->keep; wspec.dual_budget = wa->budget;
         }
-        const int rc = pool->rev->run(pool->view, count, koff, var, sign, rhs, tol, pool->max_pivots, on_done, &rs, &fits, wa ? &wspec : nullptr);
+        const int rc = pool->rev->run(views.data(), nroots, root_of, count, koff, var, sign, rhs, tol, pool->max_pivots, on_done, &rs, &fits, wa ? &wspec : nullptr);
         pool->drain();
         if (rc != GOMILP_OK) return rc;
         if (fits) { bs.launches = rs.launches; bs.supersteps = rs.supersteps; bs.seconds_total = rs.seconds_total; bs.warm_kept = rs.warm_kept; }

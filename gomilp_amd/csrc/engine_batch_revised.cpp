@@ -71,20 +71,31 @@ bool RevBatchEngine::eligible(const Engine::RootView &R, int K_min, int K_max, i
     return true;
 }
 
-int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t *koff, const int32_t *var, const double *sign,
-                        const double *rhs, double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits,
-                        const WarmSpec *warm) {
+int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const int32_t *root_of, int64_t count, const int64_t *koff,
+                        const int32_t *var, const double *sign, const double *rhs, double tol, int64_t max_pivots,
+                        const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits, const WarmSpec *warm) {
     const auto t0 = std::chrono::steady_clock::now();
     *fits = true;
     if (count <= 0) return GOMILP_OK;
+    if (!roots || nroots < 1) return GOMILP_ERR_BAD_SHAPE;
+    for (int64_t i = 0; i < count && root_of; i++) if (root_of[i] < 0 || root_of[i] >= nroots) return GOMILP_ERR_BAD_SHAPE;
     RV_TRY(hipSetDevice(device_));
     if (!stream_) RV_TRY(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     Buf &b = *b_;
-    const int m0 = R.m, n0 = R.n, ld0 = R.ld;
+    auto root_at = [&](int64_t i) -> const Engine::RootView & { return *roots[root_of ? root_of[i] : 0]; };
     const int64_t k_base = koff[0], ktot = koff[count] - koff[0];
-    int K_max = 0;
-    for (int64_t i = 0; i < count; i++) K_max = std::max<int>(K_max, (int)(koff[i + 1] - koff[i]));
-    const int m_max = m0 + K_max, n_max = n0 + K_max, ld_max = (m_max + 1) & ~1;
+    // the wave's largest shapes, over its relaxations (each has its own root's m0 / n0): they size the grids, the staged vectors and the
+    // host buffers; nn1_max: nonbasic positions of a Phase-I loop (n + 1 - m, the same for every K of a root)
+    int K_max = 0, m_max = 0, n_max = 0, nn1_max = 0;
+    std::vector<char> root_used((size_t)nroots, 0);
+    for (int64_t i = 0; i < count; i++) {
+        const Engine::RootView &R = root_at(i);
+        const int K = (int)(koff[i + 1] - koff[i]);
+        K_max = std::max(K_max, K);
+        m_max = std::max(m_max, R.m + K); n_max = std::max(n_max, R.n + K); nn1_max = std::max(nn1_max, R.n + 1 - R.m);
+        root_used[(size_t)(root_of ? root_of[i] : 0)] = 1;
+    }
+    const int ld_max = (m_max + 1) & ~1;
 
     // ---- warm starts: the kept WK_REVISED state that parent[i] names, where this relaxation's rows extend its rows (bitwise prefix) by J >= 1
     struct Plan { std::shared_ptr<WarmEntry> e; int J = 0; size_t kp = 0; };
@@ -96,7 +107,8 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
             const int K = (int)(koff[i + 1] - koff[i]);
             if (warm->parent[i] < 0 || K < 1) continue;
             std::shared_ptr<WarmEntry> e = warm->store->find(warm->parent[i]);
-            if (!e || e->kind != WK_REVISED || e->root_serial != R.serial || e->K >= K || e->m != m0 + e->K || e->n != n0 + e->K ||
+            const Engine::RootView &R = root_at(i);
+            if (!e || e->kind != WK_REVISED || e->root_serial != R.serial || e->K >= K || e->m != R.m + e->K || e->n != R.n + e->K ||
                 (int)e->hbasic.size() != e->m || (int)e->kvar.size() != e->K) continue;
             const int64_t k0 = koff[i];
             bool prefix = true;
@@ -116,7 +128,7 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
     std::vector<Lay> lay((size_t)count);
     size_t at_tot = 0, wk_tot = 0;
     for (int64_t i = 0; i < count; i++) {
-        const int K = (int)(koff[i + 1] - koff[i]), m = m0 + K, n = n0 + K, ld = (m + 1) & ~1;
+        const int K = (int)(koff[i + 1] - koff[i]), m = root_at(i).m + K, n = root_at(i).n + K, ld = (m + 1) & ~1;
         Lay &L = lay[(size_t)i];
         L.at = at_tot; at_tot += (size_t)(n + 1) * ld;
         auto take = [&](size_t doubles) { const size_t o = wk_tot; wk_tot += even(doubles); return o; };
@@ -129,8 +141,18 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
         L.st = take((sizeof(DevState) + 7) / 8);
         L.wk1 = wk_tot;
     }
-    const size_t k_doubles = even((size_t)2 * ktot + 2) + even((size_t)m0) + even((size_t)n_max + 2);
-    const size_t k_tot = k_doubles + ((size_t)ktot + 1 + (size_t)m0 + 1 + wj_tot + 1) / 2 + 2;
+    // one block per used root in the shared arena: b0 (m_r) | c2 = [c, 0...] (n_r + K_max + 2) among the doubles, rho0 (m_r + 1) among the ints
+    struct RootBlk { size_t b0 = 0, c2 = 0, rho = 0; };
+    std::vector<RootBlk> blk((size_t)nroots);
+    size_t k_doubles = even((size_t)2 * ktot + 2), k_ints = (size_t)ktot + 1;
+    for (int r = 0; r < nroots; r++) {
+        if (!root_used[(size_t)r]) continue;
+        RootBlk &B = blk[(size_t)r];
+        B.b0 = k_doubles; k_doubles += even((size_t)roots[r]->m);
+        B.c2 = k_doubles; k_doubles += even((size_t)roots[r]->n + K_max + 2);
+        B.rho = k_ints; k_ints += (size_t)roots[r]->m + 1;
+    }
+    const size_t k_tot = k_doubles + (k_ints + wj_tot + 1) / 2 + 2;
     // ---- what has to grow must fit the free device memory (with the head-room of Engine::device_fits): else the wave goes to the workers
     {
         size_t grow = 0;
@@ -177,13 +199,20 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
         b.cap_h = (size_t)count * ld_max;
     }
 
-    // ---- the wave's shared data: sign | rhs | b0 | c2, var | rho0 | kpos (parent position of each new row's variable, warm starts) ----
+    // ---- the wave's shared data: sign | rhs | per used root b0 | c2, var | per used root rho0 | kpos (parent position of each new row's
+    // variable, warm starts) ----
     std::vector<double> hk(k_tot, 0.0);
-    double *h_sign = hk.data(), *h_rhs = h_sign + ktot, *h_b0 = hk.data() + even((size_t)2 * ktot + 2), *h_c2 = h_b0 + even((size_t)m0);
-    int32_t *h_var = reinterpret_cast<int32_t *>(hk.data() + k_doubles), *h_rho = h_var + ktot + 1, *h_kpos = h_rho + m0 + 1;
+    double *h_sign = hk.data(), *h_rhs = h_sign + ktot;
+    int32_t *h_var = reinterpret_cast<int32_t *>(hk.data() + k_doubles), *h_kpos = h_var + k_ints;
     for (int64_t k = 0; k < ktot; k++) { h_sign[k] = sign[k_base + k]; h_rhs[k] = rhs[k_base + k]; h_var[k] = var[k_base + k]; }
-    for (int i = 0; i < m0; i++) { h_b0[i] = R.hb[(size_t)i]; h_rho[i] = R.rho0[(size_t)i]; }
-    for (int j = 0; j < n0; j++) h_c2[j] = R.hc[(size_t)j];   // c' = [c, 0] (subproblem.go:110-114)
+    for (int r = 0; r < nroots; r++) {
+        if (!root_used[(size_t)r]) continue;
+        const Engine::RootView &R = *roots[r];
+        double *h_b0 = hk.data() + blk[(size_t)r].b0, *h_c2 = hk.data() + blk[(size_t)r].c2;
+        int32_t *h_rho = h_var + blk[(size_t)r].rho;
+        for (int i = 0; i < R.m; i++) { h_b0[i] = R.hb[(size_t)i]; h_rho[i] = R.rho0[(size_t)i]; }
+        for (int j = 0; j < R.n; j++) h_c2[j] = R.hc[(size_t)j];   // c' = [c, 0] (subproblem.go:110-114)
+    }
     for (int64_t i = 0; i < count && nwarm; i++) {
         const Plan &P = plan[(size_t)i];
         if (!P.e) continue;
@@ -195,13 +224,18 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
             h_kpos[P.kp + (size_t)k] = pos;
         }
     }
-    double *d_sign = b.d_k, *d_rhs = d_sign + ktot, *d_b0 = b.d_k + (h_b0 - hk.data()), *d_c2 = b.d_k + (h_c2 - hk.data());
-    int32_t *d_var = reinterpret_cast<int32_t *>(b.d_k + k_doubles), *d_rho = d_var + ktot + 1, *d_kpos = d_rho + m0 + 1;
+    double *d_sign = b.d_k, *d_rhs = d_sign + ktot;
+    int32_t *d_var = reinterpret_cast<int32_t *>(b.d_k + k_doubles), *d_kpos = d_var + k_ints;
     RV_TRY(hipMemcpyAsync(b.d_k, hk.data(), k_tot * sizeof(double), hipMemcpyHostToDevice, stream_));
 
     std::vector<RevLP> lps((size_t)count);
     for (int64_t i = 0; i < count; i++) {
+        const Engine::RootView &R = root_at(i);
+        const RootBlk &B = blk[(size_t)(root_of ? root_of[i] : 0)];
+        const int m0 = R.m, n0 = R.n;
         const int K = (int)(koff[i + 1] - koff[i]), m = m0 + K, n = n0 + K, ld = (m + 1) & ~1;
+        const double *d_b0 = b.d_k + B.b0, *d_c2 = b.d_k + B.c2;
+        const int32_t *d_rho = d_var + B.rho;
         const Lay &L = lay[(size_t)i];
         RevLP &d = lps[(size_t)i];
         memset(&d, 0, sizeof(d));
@@ -219,6 +253,7 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
         d.max_pivots = max_pivots; d.tol_user = tol;
         d.stage = RS_RUN; d.run = RR_NONE; d.cost = d_c2; d.f_var = d.f_pos = d.f_p = -1;
         d.exch_on = exchange_ ? 1 : 0; d.x_added = -1; d.x_best = 0xFFFFFFFFu;
+        d.At0 = R.dAt; d.ld0 = R.ld; d.avar = d_var + (koff[i] - k_base); d.asign = d_sign + (koff[i] - k_base);
         const Plan &P = plan[(size_t)i];
         if (P.e) {
             d.warm = 1; d.wJ = P.J; d.wmp = P.e->m; d.wldp = P.e->ld;
@@ -229,19 +264,20 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
     RV_TRY(hipMemcpyAsync(b.d_lps, lps.data(), (size_t)count * sizeof(RevLP), hipMemcpyHostToDevice, stream_));
     RV_TRY(hipMemsetAsync(b.d_work, 0, wk_tot * sizeof(double), stream_));
     int64_t launches = 0;
-    for (int64_t i = 0; i < count; i++) {
-        const RevLP &d = lps[(size_t)i];
-        launch_child_assemble(R.dAt, ld0, m0, n0, d.At, d.ld, d.K, d_var + (koff[i] - k_base), d_sign + (koff[i] - k_base), stream_);
-    }
+    // (the roots' At0 are read where they lie: a root's upload, Engine::upload on its owner's stream, ends with a synchronisation of that
+    // stream, so every root the pool holds is complete on the device before this stream reads it)
+    launch_rv_assemble(b.d_lps, (int)count, n_max, stream_);
     launch_rv_init(b.d_lps, (int)count, stream_);
-    launches += count + 1;
+    launches += 2;
     if (nwarm) { launch_rv_warm_binv(b.d_lps, (int)count, m_max, stream_); launches++; }
     RV_TRY(hipStreamSynchronize(stream_));   // (the pageable staging vectors go out of use here)
     RV_TRY(hipGetLastError());
 
     // ---- supersteps ----
-    const int gp = grid_for_rows(n_max + 1 - m0), gr = grid_for_rows(m_max);
-    const int nn_max = n0 + 1 - m0;   // nonbasic positions of a Phase-I loop (n + 1 - m, the same for every K)
+    // (the pricing grid: K_max positions more than the longest list, as the schedule has always sized it — a relaxation's values do not
+    // depend on the grid it gets)
+    const int gp = grid_for_rows(nn1_max + K_max), gr = grid_for_rows(m_max);
+    const int nn_max = nn1_max;
     const size_t lds = (size_t)ld_max * sizeof(double);
     std::vector<int> act((size_t)count), done_now;
     std::vector<char> is_warm((size_t)count, 0), in_dual((size_t)count, 0);   // started warm (and still is) / the dual loop runs or is ordered
@@ -323,7 +359,7 @@ int RevBatchEngine::run(const Engine::RootView &R, int64_t count, const int64_t 
             WarmEntry &e = *kp.e;
             const int64_t k0 = koff[kp.id];
             e.kind = WK_REVISED; e.m = d.m; e.n = d.n; e.ld = d.ld; e.K = d.K; e.nn = 0; e.ldt = 0;
-            e.root_serial = R.serial;
+            e.root_serial = root_at(kp.id).serial;
             e.hbasic.assign(b.h_basic + (size_t)kp.id * ld_max, b.h_basic + (size_t)kp.id * ld_max + d.m);
             e.kvar.assign(var + k0, var + k0 + d.K); e.ksign.assign(sign + k0, sign + k0 + d.K); e.krhs.assign(rhs + k0, rhs + k0 + d.K);
             warm->store->put(warm->tag[kp.id], kp.e);

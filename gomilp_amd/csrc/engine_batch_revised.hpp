@@ -22,7 +22,10 @@ class RevBatchEngine {
     // do children of this root with K_min..K_max branch rows run on the revised pipelines, unguarded, on a worker with these knobs?
     // (the predicate of Engine::solve_locked: use_tab / exact_wanted / shadow_trace_)
     static bool eligible(const Engine::RootView &R, int K_min, int K_max, int exact_degenerate, int cond_guard);
-    // The wave (children of R; relaxation i has rows koff[i]..koff[i+1] of var / sign / rhs).  on_done as BatchEngine::run_roots: stage
+    // The wave (relaxation i is a child of roots[root_of[i]] — root_of null: of roots[0] — with rows koff[i]..koff[i+1] of var / sign /
+    // rhs; every root the wave uses must pass `eligible` with its own children's K range).  One schedule for the whole wave: each
+    // relaxation carries its own root's shape and data, the grids and staged vectors are sized for the wave's largest relaxation, and a
+    // relaxation's values depend neither on them nor on its neighbours.  on_done as BatchEngine::run_roots: stage
     // BS_DONE with the final status (basic / xb non-null where the status wants the final solve) or BS_HOST.  *fits = false: the wave's
     // buffers do not fit the free device memory — nothing ran, the caller solves the wave on the workers.
     // warm (pool knob warm_revised; nullptr: a cold wave): relaxation i starts from the kept WK_REVISED state that
@@ -30,9 +33,10 @@ class RevBatchEngine {
     // dual loop, then Phase II — and cold otherwise, in the same run; a relaxation with keep[i] that ends BS_DONE with GOMILP_OK leaves
     // its B^-1 and basis list in the store under tag[i].  A warm start that spends its dual budget is reported once with stage BS_COLD
     // (warm = 1, pivd), re-initialised in place and solved cold by the same run: its second report has warm = 0.  Waves with
-    // ld_max > kRevDualLd run cold, with keeping.
-    int run(const Engine::RootView &R, int64_t count, const int64_t *koff, const int32_t *var, const double *sign, const double *rhs,
-            double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits, const WarmSpec *warm = nullptr);
+    // ld_max > kRevDualLd run cold, with keeping.  A kept state serves children of the root it was kept under only (root_serial).
+    int run(const Engine::RootView *const *roots, int nroots, const int32_t *root_of, int64_t count, const int64_t *koff, const int32_t *var,
+            const double *sign, const double *rhs, double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits,
+            const WarmSpec *warm = nullptr);
 
     // pool knob rev_exchange: a relaxation whose Phase I ends with the artificial basic at level zero exchanges it on the device (the
     // candidate scan of batch_revised.hip: two launches in front of the set-up launches of the supersteps that have such a relaxation,

@@ -354,8 +354,9 @@ class FrontierPool:
     def set(self, key: str, value: int) -> None:
         """"batched" (1: device-batched pivot loops, 0: one worker thread + stream per relaxation), "warm_revised" (1: solve_warm on wide
         waves runs on the batched revised simplex with warm starts; default 0), "rev_exchange" (1: that schedule exchanges a zero-level
-        artificial on the device, stats art_exchanges; 0: the relaxation goes to a worker, host_fallbacks), the other pool knobs of include/gomilp_lp.h, or any
-        Context knob."""
+        artificial on the device, stats art_exchanges; 0: the relaxation goes to a worker, host_fallbacks), "rev_roots" (1, default: a
+        wide wave of several roots — solve(children, roots=...) — runs on the batched revised simplex as one schedule; 0: on the workers),
+        the other pool knobs of include/gomilp_lp.h, or any Context knob."""
         rc = lib().gomilp_pool_set(self._h, key.encode(), int(value))
         if rc != OK:
             raise ValueError("bad knob %s=%s" % (key, value))
@@ -394,7 +395,10 @@ class FrontierPool:
 
     def solve(self, children, tol: float = 0.0, roots=None) -> FrontierResult:
         """children: list of constraint lists [(var, sign, rhs), ...]; roots: per child the index of its root
-        (default: all children of the set_root problem).  Independent LPs: children [] of different roots."""
+        (default: all children of the set_root problem).  Independent LPs: children [] of different roots.  The wave runs
+        device-batched when one schedule takes every root it uses: narrow roots (n - m < 2m) the tableau schedule, wide roots with a
+        slack basis the batched revised simplex (knobs batch_revised, rev_roots; the roots may differ in shape).  A wave that mixes the
+        two kinds runs on the workers, whole; roots the pool holds but the wave does not use play no part."""
         pk = pack_children(children)   # (a PackedChildren is taken as is)
         count, koff, var, sign, rhs = pk.count, pk.koff, pk.var, pk.sign, pk.rhs
         z = np.full(count, math.nan)

@@ -263,7 +263,11 @@ void gomilp_pool_destroy(gomilp_pool *pool);
  * relaxations a worker would run on the unguarded revised-simplex pipelines — slack starts of more than 256 rows at exact_degenerate = 1,
  * any size above 64 rows at = 0 — runs on the device-batched revised simplex: the three-kernel pipeline with the relaxation as a grid
  * dimension, Phase I and the Bland rule on the device, bit-identical to the worker path; 0: such waves on the workers, one relaxation per
- * stream.  DESIGN.md section 2.5e), "rev_exchange" (default 1: on that schedule a relaxation whose Phase I ends with the artificial basic at level
+ * stream.  Several roots: the test runs over the roots the wave USES, each with the row counts of its own children, and the wave runs as one
+ * schedule when all of them pass; roots the pool merely holds do not count.  DESIGN.md section 2.5e), "rev_roots" (default 1: a wide wave of
+ * gomilp_frontier_solve_roots that uses more than one root, or a root other than the gomilp_pool_set_root problem, takes that schedule when
+ * every root it uses passes its test — bit-identical results; 0: such a wave runs on the workers, whole, as it did before the knob
+ * existed.  Waves of root 0 alone never look at it), "rev_exchange" (default 1: on that schedule a relaxation whose Phase I ends with the artificial basic at level
  * zero exchanges it on the device — every nonbasic column tried at once by the worker's acceptance rule, the smallest passing id taken, one
  * forced pivot, then Phase II: the column the worker takes, bit-identical results, counted in art_exchanges; 0: such a relaxation is handed
  * to a worker's whole solve and counted in host_fallbacks.  Either way the schedule hands over a relaxation whose artificial ends Phase I
@@ -342,7 +346,12 @@ int gomilp_pool_release_warm(gomilp_pool *pool, int64_t tag);   /* tag < 0: all 
 /* Several roots in one pool: relaxation i of a wave is a child (K_i >= 0 rows) of root root_of[i]; index 0 is the root of
  * gomilp_pool_set_root, gomilp_pool_add_root returns 1, 2, ... (or -(gomilp_status)).  Independent LPs of similar shape
  * are children with K = 0 of different roots: they advance together through the device-batched schedule (one launch per
- * kernel type for all of them).  x_out has row stride ldx >= the widest root; gomilp_pool_set_root drops the added roots. */
+ * kernel type for all of them) — narrow relaxations (n - m < 2m) on the tableau schedule, WIDE ones (n - m >= 2m, slack
+ * starts) on the batched revised simplex of pool knob "batch_revised" (pool knob "rev_roots"), where the roots may differ in
+ * rows and columns.  Which schedule takes the wave is decided over the roots the wave uses; a wave that mixes roots of both
+ * kinds, or uses a root no schedule takes, runs on the workers, whole (one relaxation per stream): it is not split.
+ * gomilp_frontier_solve_warm names no roots: its wave is one of root 0, whatever else the pool holds.
+ * x_out has row stride ldx >= the widest root; gomilp_pool_set_root drops the added roots. */
 int gomilp_pool_add_root(gomilp_pool *pool, const double *c, const double *A, int64_t lda, const double *b, int64_t m, int64_t n);
 int gomilp_frontier_solve_roots(gomilp_pool *pool, int64_t count, const int32_t *root_of, const int64_t *koff, const int32_t *var,
                                 const double *sign, const double *rhs, double tol, double *z_out, double *x_out, int64_t ldx,
