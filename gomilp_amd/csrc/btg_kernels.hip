@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "device_types.h"
@@ -46,9 +47,11 @@ struct BtWinG { double m; unsigned int i; };                   // a wave's own w
 // G workgroups x NT threads, RI rows and RI columns per thread (m <= G*NT*RI, ldt <= G*NT*RI), KR block terms in registers
 // LOOP: the pivot role of the persistent loop kernel (k_bt_loop): up to a.nblocks blocks of 8 pivots in one launch, the terms
 // of the previous block carried along as lagging terms while the update workgroups of the same launch apply them
-template <int G, int NT, int RI, int KR, bool STAMP, bool LOOP = false>
+// WREC (loop mode, 16 x 128 threads): every WAVE posts a half-line record of its own — no workgroup stage in front of a post (xchg_wave)
+template <int G, int NT, int RI, int KR, bool STAMP, bool LOOP = false, bool WREC = false>
 __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, const int nupd = 0) {
     constexpr int NW = NT / 64;
+    static_assert(!WREC || (LOOP && G == 16 && NW == 2 && RI == 1), "wave records: two half-line records per workgroup, 32 in all");
     static_assert(!LOOP || KR == 16 || KR == 24 || KR == 32, "loop mode: KR / 2 lagging + KR / 2 current terms");
     constexpr int KB = LOOP ? KR / 2 : KR;   // pivots per block
     static_assert(G == 2 || G == 4 || G == 8 || G == 16, "G");
@@ -155,6 +158,7 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
     int kd = 0, status = ST_RUNNING, blands = 0;
     bool dead = false;
     long long trace_len = 0, npiv = 0;
+    unsigned long long spiv = 0;   // STAMP: pivots behind the cycle sums of this launch
     if (g == 0 && tid == 0) { trace_len = st->trace_len; npiv = st->pivots; }
 
     auto wave_first_min = [&](const double (&val)[RI]) -> BtWinG {
@@ -333,9 +337,91 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
         stamp(which * 5 + 4);
         return r;
     };
+    // The exchange with one record per WAVE (WREC).  A workgroup's 128-byte line holds two half-records, wave w owns slots 4 w .. 4 w + 3;
+    // a slot is {64-bit integer tag, double}: tag = low 32 bits of the sequence number << 32 | a 32-bit integer.  Slot 0: first index,
+    // minimum; slot 1: the winner's variable id, r_q resp. d_p; slot 2: the XCC id, x_B[p]; slot 3: -, the winner's newest block term.
+    // A wave posts right behind its own argmin: the winner lane's values reach lanes 0..3 by v_readlane, one 16-byte store per lane —
+    // no LDS, no barrier, no fold over the workgroup's waves.  The poll reads the same 16 lines with the same two loads per lane as the
+    // workgroup records: lane l takes half-record l & 31, slots 2 (l >> 5) and + 1.  Tags are compared as INTEGERS (a packed tag may be
+    // a NaN pattern).  The lexicographic minimum over the 32 wave candidates is the one over 16 workgroup winners of two waves each.
+    // Term stores: a wave's s_waitcnt vmcnt(0) in its row phase precedes its own next post, so whoever has seen a wave's post may read
+    // that wave's older terms from U / V.  (The buffer is shared with the workgroup-record kernels of the same context, whose slots
+    // hold {(double)sequence number, value}: a stale one of those reads as this exchange's tag only 2^30 exchanges later.)
+    auto xchg_wave = [&](int which, const BtWinG w, double v1, int id1, double v2, double v3) -> XWin {
+        typedef unsigned long long xtag2 __attribute__((ext_vector_type(2)));
+        stamp(which * 5 + 0);
+        stamp(which * 5 + 1);   // (no wait, no barrier: the segment stays for the comparison with the workgroup form)
+        xs += 1;
+        const unsigned int seq32 = (unsigned int)xs;
+        const int par = (int)(xs & 1);
+        const int wl = w.i != 0xFFFFFFFFu ? (int)(w.i & 63u) : 0;   // the winner's lane (every candidate NaN: lane 0, the record never wins)
+        const unsigned long long b1 = (unsigned long long)__double_as_longlong(readlane_f64(v1, wl));
+        const unsigned int i1 = (unsigned int)__builtin_amdgcn_readlane(id1, wl);
+        const unsigned long long b2 = (unsigned long long)__double_as_longlong(readlane_f64(v2, wl));
+        const unsigned long long b3 = (unsigned long long)__double_as_longlong(readlane_f64(v3, wl));
+        if (lane < 4) {
+            // (independent selects, not a chain on `lane`: a chain compiles to a switch with a branch per slot)
+            const unsigned int ti = (lane == 0 ? w.i : 0u) | (lane == 1 ? i1 : 0u) | (lane == 2 ? myxcc : 0u);
+            xtag2 v;
+            v.x = ((unsigned long long)seq32 << 32) | ti;
+            v.y = (lane == 0 ? (unsigned long long)__double_as_longlong(w.m) : 0ull) | (lane == 1 ? b1 : 0ull) | (lane == 2 ? b2 : 0ull) | (lane == 3 ? b3 : 0ull);
+            xstore(recs + ((size_t)(par * G + g) * kXSlots + 4 * wv + lane), __builtin_bit_cast(xpair, v), fast);
+        }
+        stamp(which * 5 + 2);
+        for (int dl = 0; dl < a.poll_delay; dl++) __builtin_amdgcn_s_sleep(1);
+        const int h = lane & 31;   // half-record h: wave h & 1 of workgroup h >> 1
+        const xpair *src = recs + (size_t)par * G * kXSlots + (h >> 1) * kXSlots + (h & 1) * 4 + 2 * (lane >> 5);
+        xpair got[2];
+        xtag2 t0, t1;
+        int spins = 0;
+        for (;;) {
+            XLoad<2>::run(src, src + 1, got, fast);
+            t0 = __builtin_bit_cast(xtag2, got[0]);
+            t1 = __builtin_bit_cast(xtag2, got[1]);
+            if (__all((unsigned int)(t0.x >> 32) == seq32 && (unsigned int)(t1.x >> 32) == seq32)) break;
+            if (++spins > kXSpinLimit) { dead = true; break; }
+        }
+        stamp(which * 5 + 3);
+        // lanes 0..31: (first index, minimum) and (id, r_q / d_p) of half-record l; lanes 32..63: (XCC id, x_B[p]) and the newest term
+        const double val = got[0].y, val2 = got[1].y;
+        const unsigned int idx = (unsigned int)t0.x, id = (unsigned int)t1.x;
+        double xm = lane < 32 ? val : inf;   // a NaN minimum never wins (v_min_f64)
+        xm = vmin_f64(xm, dpp_f64<0xB1>(xm));
+        xm = vmin_f64(xm, dpp_f64<0x4E>(xm));
+        xm = vmin_f64(xm, dpp_f64<0x141>(xm));
+        xm = vmin_f64(xm, dpp_f64<0x140>(xm));            // every lane of a row holds the row's minimum
+        xm = vmin_f64(xm, bcast_f64<0x142, 0xA>(xm));     // row_bcast:15 -> row 1 holds the minimum of lanes 0..31
+        const double bm = readlane_f64(xm, 31);
+        const bool mine = lane < 32 && val == bm;
+        const unsigned int mk0 = (unsigned int)__ballot(mine);
+        int hw;
+        if (__builtin_popcount(mk0) == 1) hw = __builtin_ctz(mk0);   // (uniform) one record attains the minimum — the usual case
+        else {
+            // smallest first index among the records that attain it (every minimum NaN: none does — record 0, index 0xFFFFFFFF)
+            const unsigned int ki = row_min_u32(mine ? idx : 0xFFFFFFFFu);
+            const unsigned int kmin = min((unsigned int)__builtin_amdgcn_readlane((int)ki, 0), (unsigned int)__builtin_amdgcn_readlane((int)ki, 16));
+            const unsigned int mk = (unsigned int)__ballot(mine && idx == kmin);
+            hw = mk ? __builtin_ctz(mk) : 0;
+        }
+        XWin r;
+        r.m = bm;
+        r.i = (unsigned int)__builtin_amdgcn_readlane((int)idx, hw);
+        r.p0 = readlane_f64(val2, hw);
+        const double wid = (double)__builtin_amdgcn_readlane((int)id, hw);
+        r.p1 = which == 0 ? wid : readlane_f64(val, 32 + hw);
+        r.p2 = wid;
+        r.p3 = readlane_f64(val2, 32 + hw);
+        if (first) {   // slot 2 of every half-record: the XCC the wave runs on
+            fast = !dead && __all(lane < 32 || idx == myxcc);
+            first = false;
+        }
+        stamp(which * 5 + 4);
+        return r;
+    };
     // entering column: (min, q); payload r_q, the entering variable
     auto reduce_cols = [&](const double (&val)[RI]) -> XWin {
         const BtWinG w = wave_first_min(val);
+        if constexpr (WREC) return xchg_wave(0, w, rv[0], nbasv[0], 0.0, vreg[0][0]);
 #pragma unroll
         for (int s = 0; s < RI; s++)
             if ((unsigned int)gidx(s) == w.i) {
@@ -349,6 +435,7 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
     // leaving row: (min, p); payload d_p, x_B[p], the leaving variable
     auto reduce_rows = [&](const double (&val)[RI], const double (&dcol)[RI]) -> XWin {
         const BtWinG w = wave_first_min(val);
+        if constexpr (WREC) return xchg_wave(1, w, dcol[0], basv[0], xbv[0], ureg[0][0]);
 #pragma unroll
         for (int s = 0; s < RI; s++)
             if ((unsigned int)gidx(s) == w.i) {
@@ -610,6 +697,7 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
             npiv += 1;
         }
         kd = k + 1;
+        if constexpr (STAMP) spiv += 1;
     }
     nbe = blk + 1;
     if constexpr (LOOP) {
@@ -636,7 +724,7 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
     if constexpr (STAMP) {
         if (a.stamps && g == 0 && lane == 0) {
             for (int sg = 0; sg < 16; sg++) a.stamps[wv * 16 + sg] += s_acc[wv][sg];
-            if (wv == 0) a.stamps[16 * 16] += (unsigned long long)kd;
+            if (wv == 0) a.stamps[16 * 16] += LOOP ? spiv : (unsigned long long)kd;   // (loop mode: kd counts the last block only)
         }
     }
 #pragma unroll
@@ -676,12 +764,12 @@ __global__ __launch_bounds__(NT) void k_bt_innerG(BTArgs a) {
 // Blocks 0, 8, ..., 8 (G - 1) — one XCD under the round-robin placement of blocks — are the pivot workgroups, every other block
 // of the grid an update workgroup.  All workgroups of the launch must be resident (they wait for each other): the grid is one
 // workgroup per CU (launch_bt_loop), and every wait is bounded.
-template <int G, int NT, int RI, bool STAMP = false, int KB = 8>
+template <int G, int NT, int RI, bool STAMP = false, int KB = 8, bool WREC = false>
 __global__ __launch_bounds__(NT) void k_bt_loop(BTArgs a) {
     const int b = (int)blockIdx.x, x = a.xcd & 7;
     // update workgroups that take part (knob "loop_upd": fewer of them spread a block's traffic over more of the block time)
     const int nupd = (a.upd_cap > 0 && a.upd_cap < (int)gridDim.x - G) ? a.upd_cap : (int)gridDim.x - G;
-    if ((b & 7) == x && (b >> 3) < G) { bt_innerG_body<G, NT, RI, 2 * KB, STAMP, true>(a, b >> 3, nupd); return; }
+    if ((b & 7) == x && (b >> 3) < G) { bt_innerG_body<G, NT, RI, 2 * KB, STAMP, true, WREC>(a, b >> 3, nupd); return; }
     const int before = b <= x ? 0 : min(G, ((b - x - 1) >> 3) + 1);   // pivot blocks in front of block b
     if (b - before >= nupd) return;
     bt_loop_update_role<NT, KB>(a, b - before, nupd, G);
@@ -708,6 +796,8 @@ __global__ __launch_bounds__(NT) void k_bt_innerG_batch(const BatchLP *__restric
 // resp. six 16-byte loads per lane and poll).  Same pivots, but 35.1 instead of 32.3 us per 8 pivots at 2048 rows and 114 instead
 // of 52.6 at 4096: what the workgroup stage costs (stamps: ~1000 cycles in wave 0) the wider poll costs again (1600 instead of
 // 760 cycles from post to "all seen").
+// (Built since for the 16 x 128 instance with HALF-line records, two per workgroup line, so that the poll keeps its two loads per lane
+// over 16 lines: xchg_wave, 11.53 -> 10.28 ms per loop of the metric LP.)
 // Tried and dropped (round 5, loop mode): 16 pivot workgroups of ONE wave, two rows / columns per thread (k_bt_loop<16,64,2,8>: no workgroup
 // stage and no real barrier in front of a post).  Same pivots, 4.45-4.68 instead of 3.87 us per pivot at 2048 rows (grid 256 / 136): the
 // wave's doubled row / column work costs more than the stage saved.
@@ -763,6 +853,8 @@ void launch_bt_inner_groups(const BTArgs &a, hipStream_t s, hipEvent_t e0, hipEv
 }
 // persistent loop kernel: one workgroup per CU (the pivot workgroups among them); only the one-row-per-thread instances
 bool bt_loop_supported(const BtGroupCfg &c) { return c.groups >= 2 && c.ri == 1; }
+static std::atomic<long long> g_wave_rec_launches{0};
+long long bt_loop_wave_rec_launches() { return g_wave_rec_launches.load(); }   // (tests: which exchange form ran)
 void launch_bt_loop(const BTArgs &a, int ncu, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const int G = a.groups;
     const unsigned int grid = (unsigned int)std::max(ncu, 8 * G);
@@ -771,7 +863,16 @@ void launch_bt_loop(const BTArgs &a, int ncu, hipStream_t s, hipEvent_t e0, hipE
         else hipExtLaunchKernelGGL((k_bt_loop<8, 256, 1>), dim3(grid), dim3(256), 0, s, e0, e1, 0, a);
         return;
     }
-    if (G == 16 && a.group_nt == 128) { hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, false, 8>), dim3(std::max(grid, 136u)), dim3(128), 0, s, e0, e1, 0, a); return; }   // up to 2048 rows: 16 x 128 threads, blocks of 8
+    if (G == 16 && a.group_nt == 128) {   // up to 2048 rows: 16 x 128 threads, blocks of 8; one exchange record per wave unless knob loop_wave_rec = 0
+        const dim3 g16(std::max(grid, 136u));
+        if (a.wave_rec) g_wave_rec_launches++;
+        if (a.stamps) {   // diagnostic build (knob bt_stamps = 2)
+            if (a.wave_rec) hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, true, 8, true>), g16, dim3(128), 0, s, e0, e1, 0, a);
+            else hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, true, 8, false>), g16, dim3(128), 0, s, e0, e1, 0, a);
+        } else if (a.wave_rec) hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, false, 8, true>), g16, dim3(128), 0, s, e0, e1, 0, a);
+        else hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, false, 8, false>), g16, dim3(128), 0, s, e0, e1, 0, a);
+        return;
+    }
     if (G == 16 && a.kmax == 12) { hipExtLaunchKernelGGL((k_bt_loop<16, 256, 1, false, 12>), dim3(std::max(grid, 136u)), dim3(256), 0, s, e0, e1, 0, a); return; }   // knob loop_k = 12
     if (G == 16) { hipExtLaunchKernelGGL((k_bt_loop<16, 256, 1, false, 16>), dim3(std::max(grid, 128u)), dim3(256), 0, s, e0, e1, 0, a); return; }   // 4096 rows: 16 x 256 threads, blocks of 16 (pivot blocks: x + 8 j, j < 16, x <= 6)
     if (G == 2) hipExtLaunchKernelGGL((k_bt_loop<2, 512, 1>), dim3(grid), dim3(512), 0, s, e0, e1, 0, a);

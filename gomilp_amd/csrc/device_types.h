@@ -175,6 +175,7 @@ struct BTArgs {
     // and repeats the reference's iteration on fresh solves (Engine::exact_step); a batched relaxation goes to the worker path
     double cguard;
     int32_t exact_once, poll_delay;   // (poll_delay: units of 64 cycles a wave waits between its post and its first poll, knob "poll_delay")
+    int32_t wave_rec, pad_;           // loop kernel of 16 x 128 threads: one exchange record per wave (knob "loop_wave_rec")
 };
 
 // shape of the multi-workgroup block kernel for a tableau (btg_kernels.hip): groups == 0 -> single-workgroup kernels

@@ -104,7 +104,8 @@ int Engine::set(const std::string &key, int64_t v) {
     else if (key == "general_block") general_block_ = v ? 1 : 0;
     else if (key == "general_min_rows") general_min_rows_ = v < 2 ? 2 : v;
     else if (key == "bt_groups") { if (v != -1 && v != 0 && v != 2 && v != 4 && v != 8 && v != 16) return GOMILP_ERR_BAD_SHAPE; bt_groups_ = v; }
-    else if (key == "bt_stamps") bt_stamps_ = v ? 1 : 0;
+    else if (key == "bt_stamps") bt_stamps_ = v < 0 ? 0 : (v > 2 ? 2 : v);   // 2: the loop kernel keeps its production shape (16 x 128 threads up to 2048 rows); 1: 8 x 256
+    else if (key == "loop_wave_rec") loop_wave_rec_ = v ? 1 : 0;
     else if (key == "bt_lag") bt_lag_ = v ? 1 : 0;
     else if (key == "exact_degenerate") { if (v < 0 || v > 3) return GOMILP_ERR_BAD_SHAPE; exact_degenerate_ = v; }   // 3: strict — EVERY pivot decided on fresh gonum-order solves (engine_tableau.cpp exact_step)
     else if (key == "loop_grid") { if (v < 0 || v > 4096) return GOMILP_ERR_BAD_SHAPE; loop_grid_ = v; }

@@ -266,6 +266,7 @@ class Engine {
             loop_upd_ = 0,     // update workgroups of the loop kernel that take part (0: all of the grid's)
             loop_rep_ = 0,     // 1: pivot role with replicated reduced costs (btr_kernels.hip k_bt_loopR: ONE exchange per pivot; bit-identical pivots, measured slower — DESIGN 2.1d) where the shape fits and the engine gets the whole device
             loop_g_ = 0,       // its pivot workgroups (0 / 16: 16 x 128 threads up to 2048 rows, 16 x 256 beyond; 8: 8 x 256 / 8 x 512)
+            loop_wave_rec_ = 1,   // its 16 x 128 instance: one exchange record per wave, no workgroup stage in front of a post (0: one per workgroup)
             loop_k_ = 0,       // its pivots per block (0: 8 up to 2048 rows, 16 beyond; 8 / 16 forced where instantiated)
             exact_degenerate_ = 1,   // 0 never, 1 bases of up to 256 rows and every non-slack start, 2 always: pivots whose winning ratio is (nearly) zero are decided on a fresh gonum-order x_B; 3 strict: EVERY pivot and the stop test are decided on fresh gonum-order solves
             cond_guard_ = 1,   // replay the condition guards of the reference on the host for bases of up to 64 rows
@@ -385,6 +386,7 @@ void launch_bt_loop(const BTArgs &a, int ncu, hipStream_t s, hipEvent_t e0, hipE
 bool bt_loop_rep_supported(int m, int ldt);
 int bt_loop_rep_threads(int m, int ldt);
 long long bt_loop_rep_launches();
+long long bt_loop_wave_rec_launches();
 void launch_bt_loop_rep(const BTArgs &a, int ncu, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 bool bt_batch_supported(int m_max, int ldt_max);
 int bt_batch_k(int m_max, int ldt_max);

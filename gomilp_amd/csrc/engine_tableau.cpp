@@ -479,7 +479,7 @@ int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_
     };
     // (weight: the 128-thread shape shares the device with up to three others, every other shape runs alone — engine.cpp)
     // (the 2048-row class in blocks of 16 — knob loop_k — shares the device too: 256-thread workgroups, two per CU, grid of half the CUs)
-    const bool small_loop = lag && (K == 8 || K == 16) && loop_g_ != 8 && !bt_stamps_ && bt_group_cfg(P.m, ldt_, groups_knob(P)).nt == 256;
+    const bool small_loop = lag && (K == 8 || K == 16) && loop_g_ != 8 && bt_stamps_ != 1 && bt_group_cfg(P.m, ldt_, groups_knob(P)).nt == 256;
     // The pivot role with replicated reduced costs (btr_kernels.hip): 512-thread workgroups that fill a CU each, so the launch must own
     // the device — taken only if nobody else holds a loop slot right now (no waiting: busy means the shared 16 x 128 shape as before)
     const BtGroupCfg gc0 = bt_group_cfg(P.m, ldt_, groups_knob(P));
@@ -547,8 +547,8 @@ int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_
             // 11.47 ms against 11.85 ms per solve of the metric LP for 8 x 256)
             const bool rep = rep_hold.held && ai.groups == 8 && ai.group_nt == 256 && ai.group_ri == 1;
             if (rep) { ai.groups = 16; ai.group_nt = bt_loop_rep_threads(P.m, ldt_); }
-            else if (ai.groups == 8 && ai.group_nt == 256 && ai.group_ri == 1 && loop_g_ != 8 && K == 8 && !bt_stamps_) {
-                ai.groups = 16; ai.group_nt = 128;   // (8 x 128 threads measured the same at 1024 rows: 4.74 against 4.75 ms per loop of C2)
+            else if (ai.groups == 8 && ai.group_nt == 256 && ai.group_ri == 1 && loop_g_ != 8 && K == 8 && bt_stamps_ != 1) {
+                ai.groups = 16; ai.group_nt = 128; ai.wave_rec = loop_wave_rec_ ? 1 : 0;   // (8 x 128 threads measured the same at 1024 rows: 4.74 against 4.75 ms per loop of C2)
             }
             ai.Tbuf[0] = w.T[0]; ai.Tbuf[1] = w.T[1];
             ai.xcd = loop_xcd; ai.upd_cap = (int)loop_upd_; ai.poll_delay = (int)poll_delay_;

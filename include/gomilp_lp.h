@@ -118,7 +118,8 @@ int gomilp_ctx_device(const gomilp_ctx *ctx);
  * workgroups), "bt_old", "bt_stamps", "sample_events"; of the persistent loop kernel: "bt_lag" (0: the launch pairs of round 2),
  * "loop_chunk" (pivots per launch), "loop_g" (8 / 16 pivot workgroups), "loop_k" (8 / 12 / 16 pivots per block), "loop_upd"
  * (update workgroups that take part), "loop_grid", "poll_delay", "loop_rep" (default 0, opt-in: the pivot role with replicated reduced costs, ONE exchange
- * per pivot — bit-identical pivots, measured slower: DESIGN.md section 2.1d); of the bit-exact final solve: "lu_blocked" (3 default: compressed rounds
+ * per pivot — bit-identical pivots, measured slower: DESIGN.md section 2.1d); "loop_wave_rec" (default 1: the 16 x 128 instance posts one exchange record per wave,
+ * 0: one per workgroup — bit-identical pivots: DESIGN.md section 2.1c); "bt_stamps" = 2 stamps that instance instead of the 8 x 256 one; of the bit-exact final solve: "lu_blocked" (3 default: compressed rounds
  * in the look-ahead schedule — one launch per round, the panel beside the previous round's update — for bases beyond 768 rows while the
  * engine holds the device's loop slots, 2: compressed rounds with the whole update behind each panel, 1: blocked panels, 0: one launch per
  * column — all bit-identical), "lu_look" (0: never the look-ahead schedule; a pool sets it on its workers), "lu_large" (default 0;
