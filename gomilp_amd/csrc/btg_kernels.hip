@@ -855,30 +855,30 @@ void launch_bt_inner_groups(const BTArgs &a, hipStream_t s, hipEvent_t e0, hipEv
 bool bt_loop_supported(const BtGroupCfg &c) { return c.groups >= 2 && c.ri == 1; }
 static std::atomic<long long> g_wave_rec_launches{0};
 long long bt_loop_wave_rec_launches() { return g_wave_rec_launches.load(); }   // (tests: which exchange form ran)
-void launch_bt_loop(const BTArgs &a, int ncu, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    const int G = a.groups;
-    const unsigned int grid = (unsigned int)std::max(ncu, 8 * G);
-    if (a.group_nt == 256 && G == 8) {
-        if (a.stamps) hipExtLaunchKernelGGL((k_bt_loop<8, 256, 1, true>), dim3(grid), dim3(256), 0, s, e0, e1, 0, a);   // diagnostic build
-        else hipExtLaunchKernelGGL((k_bt_loop<8, 256, 1>), dim3(grid), dim3(256), 0, s, e0, e1, 0, a);
-        return;
+// one hipExtLaunchKernelGGL line per instance; false: `inst` is none of this file's, or the grid is below what its pivot workgroups need
+bool launch_bt_loop(BtLoop inst, const BTArgs &a, int grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    const BtLoopShape sh = bt_loop_shape(inst);
+    if (sh.groups == 0 || sh.rep || grid < sh.min_grid) return false;
+    const dim3 g((unsigned int)grid), nt((unsigned int)sh.nt);
+    switch (inst) {
+        // (in the order the instances are emitted into the code object)
+        case BtLoop::G8x256Stamped: hipExtLaunchKernelGGL((k_bt_loop<8, 256, 1, true>), g, nt, 0, s, e0, e1, 0, a); break;   // diagnostic build (knob bt_stamps = 1)
+        case BtLoop::G8x256: hipExtLaunchKernelGGL((k_bt_loop<8, 256, 1>), g, nt, 0, s, e0, e1, 0, a); break;
+        // up to 2048 rows: 16 x 128 threads, blocks of 8; one exchange record per wave unless knob loop_wave_rec = 0
+        case BtLoop::G16x128WaveStamped: hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, true, 8, true>), g, nt, 0, s, e0, e1, 0, a); break;
+        case BtLoop::G16x128Stamped: hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, true, 8, false>), g, nt, 0, s, e0, e1, 0, a); break;   // diagnostic build (knob bt_stamps = 2)
+        case BtLoop::G16x128Wave: hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, false, 8, true>), g, nt, 0, s, e0, e1, 0, a); break;
+        case BtLoop::G16x128: hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, false, 8, false>), g, nt, 0, s, e0, e1, 0, a); break;
+        case BtLoop::G16x256K12: hipExtLaunchKernelGGL((k_bt_loop<16, 256, 1, false, 12>), g, nt, 0, s, e0, e1, 0, a); break;   // knob loop_k = 12
+        case BtLoop::G16x256K16: hipExtLaunchKernelGGL((k_bt_loop<16, 256, 1, false, 16>), g, nt, 0, s, e0, e1, 0, a); break;   // 4096 rows: 16 x 256 threads, blocks of 16
+        case BtLoop::G2x512: hipExtLaunchKernelGGL((k_bt_loop<2, 512, 1>), g, nt, 0, s, e0, e1, 0, a); break;
+        case BtLoop::G4x512: hipExtLaunchKernelGGL((k_bt_loop<4, 512, 1>), g, nt, 0, s, e0, e1, 0, a); break;
+        case BtLoop::G8x512K16: hipExtLaunchKernelGGL((k_bt_loop<8, 512, 1, false, 16>), g, nt, 0, s, e0, e1, 0, a); break;   // blocks of 16 pivots
+        case BtLoop::G8x512: hipExtLaunchKernelGGL((k_bt_loop<8, 512, 1>), g, nt, 0, s, e0, e1, 0, a); break;
+        default: return false;
     }
-    if (G == 16 && a.group_nt == 128) {   // up to 2048 rows: 16 x 128 threads, blocks of 8; one exchange record per wave unless knob loop_wave_rec = 0
-        const dim3 g16(std::max(grid, 136u));
-        if (a.wave_rec) g_wave_rec_launches++;
-        if (a.stamps) {   // diagnostic build (knob bt_stamps = 2)
-            if (a.wave_rec) hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, true, 8, true>), g16, dim3(128), 0, s, e0, e1, 0, a);
-            else hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, true, 8, false>), g16, dim3(128), 0, s, e0, e1, 0, a);
-        } else if (a.wave_rec) hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, false, 8, true>), g16, dim3(128), 0, s, e0, e1, 0, a);
-        else hipExtLaunchKernelGGL((k_bt_loop<16, 128, 1, false, 8, false>), g16, dim3(128), 0, s, e0, e1, 0, a);
-        return;
-    }
-    if (G == 16 && a.kmax == 12) { hipExtLaunchKernelGGL((k_bt_loop<16, 256, 1, false, 12>), dim3(std::max(grid, 136u)), dim3(256), 0, s, e0, e1, 0, a); return; }   // knob loop_k = 12
-    if (G == 16) { hipExtLaunchKernelGGL((k_bt_loop<16, 256, 1, false, 16>), dim3(std::max(grid, 128u)), dim3(256), 0, s, e0, e1, 0, a); return; }   // 4096 rows: 16 x 256 threads, blocks of 16 (pivot blocks: x + 8 j, j < 16, x <= 6)
-    if (G == 2) hipExtLaunchKernelGGL((k_bt_loop<2, 512, 1>), dim3(grid), dim3(512), 0, s, e0, e1, 0, a);
-    else if (G == 4) hipExtLaunchKernelGGL((k_bt_loop<4, 512, 1>), dim3(grid), dim3(512), 0, s, e0, e1, 0, a);
-    else if (a.kmax == 16) hipExtLaunchKernelGGL((k_bt_loop<8, 512, 1, false, 16>), dim3(grid), dim3(512), 0, s, e0, e1, 0, a);   // blocks of 16 pivots
-    else hipExtLaunchKernelGGL((k_bt_loop<8, 512, 1>), dim3(grid), dim3(512), 0, s, e0, e1, 0, a);
+    if (sh.wave_rec) g_wave_rec_launches++;
+    return true;
 }
 // batched launch: the whole wave has the shape class of its largest relaxation (8 workgroups; 256 or 512 threads)
 void launch_bt_inner_groups_batch(const BatchLP *lps, const int *ids, const int *count, int nlp, const BtGroupCfg &c, hipStream_t s, hipEvent_t e0, hipEvent_t e1, int xcd_off) {

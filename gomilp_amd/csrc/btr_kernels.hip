@@ -582,23 +582,24 @@ int bt_loop_rep_threads(int m, int ldt) { return (m <= 1024 && ldt <= 1024) ? 25
 template <int NT, int CPT, int KB> static constexpr int rep_lds_bytes() { return (KB * NT * CPT + 2 * KB * (NT * CPT / 16)) * 8; }
 static std::atomic<long long> g_rep_launches{0};
 long long bt_loop_rep_launches() { return g_rep_launches.load(); }   // (tests: which pivot role ran)
-void launch_bt_loop_rep(const BTArgs &a, int ncu, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+template <int NT, bool STAMP>
+static void rep_launch(const BTArgs &a, int grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    constexpr int lds = rep_lds_bytes<NT, 4, 8>();
+    lds_attr_once(reinterpret_cast<const void *>(k_bt_loopR<16, NT, 4, 8, STAMP>), lds);
+    hipExtLaunchKernelGGL((k_bt_loopR<16, NT, 4, 8, STAMP>), dim3((unsigned int)grid), dim3(NT), lds, s, e0, e1, 0, a);
+}
+// false: `inst` is none of this file's, or the grid is below what its pivot workgroups need
+bool launch_bt_loop_rep(BtLoop inst, const BTArgs &a, int grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    const BtLoopShape sh = bt_loop_shape(inst);
+    if (!sh.rep || grid < sh.min_grid) return false;
+    switch (inst) {
+        case BtLoop::Rep16x256: rep_launch<256, false>(a, grid, s, e0, e1); break;
+        case BtLoop::Rep16x512Stamped: rep_launch<512, true>(a, grid, s, e0, e1); break;   // diagnostic build
+        case BtLoop::Rep16x512: rep_launch<512, false>(a, grid, s, e0, e1); break;
+        default: return false;
+    }
     g_rep_launches++;
-    const unsigned int grid = (unsigned int)std::max(std::max(ncu, 8 * 16), 136);
-    if (a.group_nt == 256) {
-        constexpr int lds = rep_lds_bytes<256, 4, 8>();
-        lds_attr_once(reinterpret_cast<const void *>(k_bt_loopR<16, 256, 4, 8>), lds);
-        hipExtLaunchKernelGGL((k_bt_loopR<16, 256, 4, 8>), dim3(grid), dim3(256), lds, s, e0, e1, 0, a);
-        return;
-    }
-    constexpr int lds = rep_lds_bytes<512, 4, 8>();
-    if (a.stamps) {   // diagnostic build
-        lds_attr_once(reinterpret_cast<const void *>(k_bt_loopR<16, 512, 4, 8, true>), lds);
-        hipExtLaunchKernelGGL((k_bt_loopR<16, 512, 4, 8, true>), dim3(grid), dim3(512), lds, s, e0, e1, 0, a);
-    } else {
-        lds_attr_once(reinterpret_cast<const void *>(k_bt_loopR<16, 512, 4, 8>), lds);
-        hipExtLaunchKernelGGL((k_bt_loopR<16, 512, 4, 8>), dim3(grid), dim3(512), lds, s, e0, e1, 0, a);
-    }
+    return true;
 }
 
 }  // namespace gomilp

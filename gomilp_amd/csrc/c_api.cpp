@@ -808,6 +808,24 @@ int gomilp_debug_lu_host_solve(int64_t m, int64_t nd, const int32_t *dl, const i
     return 0;
 }
 
+int gomilp_debug_bt_plan(int64_t m, int64_t ldt, int64_t nknobs, const char *const *keys, const int64_t *values, int64_t ncu, int64_t *out) {
+    if (m < 1 || ldt < 1 || m > (1 << 20) || ldt > (1 << 22) || nknobs < 0 || (nknobs > 0 && (!keys || !values)) || !out) return -GOMILP_ERR_BAD_SHAPE;
+    gomilp::BtKnobs knobs;
+    for (int64_t i = 0; i < nknobs; i++) {
+        const int rc = keys[i] ? knobs.set(keys[i], values[i]) : -1;
+        if (rc != GOMILP_OK) return -GOMILP_ERR_BAD_SHAPE;   // (a key that is none of the plan's knobs included)
+    }
+    const gomilp::BtPlan p = gomilp::BtPlan::make((int)m, (int)ldt, knobs);
+    const gomilp::BtLoopShape sh = gomilp::bt_loop_shape(p.loop), rep = gomilp::bt_loop_shape(p.rep);
+    const int64_t f[GOMILP_BT_PLAN_FIELDS] = {
+        p.pipeline, p.K, p.tiled, p.tiled_forced, p.cfg.groups, p.cfg.nt, p.cfg.ri, p.blocks_per_chunk,
+        (int64_t)p.loop, sh.groups, sh.nt, sh.kb, sh.wave_rec, sh.stamped, sh.min_grid, p.is_loop() ? p.slot_weight : 0, p.upd_cap,
+        p.is_loop() ? p.grid((int)ncu, p.loop) : 0,
+        (int64_t)p.rep, rep.nt, rep.stamped, p.rep_upd_cap, p.rep != gomilp::BtLoop::None ? p.grid((int)ncu, p.rep) : 0};
+    for (int i = 0; i < GOMILP_BT_PLAN_FIELDS; i++) out[i] = f[i];
+    return GOMILP_BT_PLAN_FIELDS;
+}
+
 int64_t gomilp_debug_find_independent_device(gomilp_ctx *ctx, int64_t problem, int64_t *idx_out, int64_t cap) {
     if (!ctx || !idx_out) return -GOMILP_ERR_BAD_SHAPE;
     std::vector<int32_t> idx;

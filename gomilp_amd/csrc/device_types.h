@@ -181,6 +181,42 @@ struct BTArgs {
 // shape of the multi-workgroup block kernel for a tableau (btg_kernels.hip): groups == 0 -> single-workgroup kernels
 struct BtGroupCfg { int groups, nt, ri; };
 
+// The instantiated persistent loop kernels, one entry each: k_bt_loop<G, NT, 1, STAMP, KB, WREC> (btg_kernels.hip) and, Rep*, the pivot role
+// with replicated reduced costs k_bt_loopR<16, NT, 4, 8, STAMP> (btr_kernels.hip).  BtPlan::make (engine_tableau.cpp) names the one a solve
+// runs; launch_bt_loop / launch_bt_loop_rep launch exactly that one.
+enum class BtLoop : int32_t {
+    None = 0,
+    G8x256, G8x256Stamped,
+    G16x128, G16x128Wave, G16x128Stamped, G16x128WaveStamped,   // Wave: one exchange record per wave
+    G16x256K12, G16x256K16,                                     // blocks of 12 / 16 pivots (every other instance: 8)
+    G2x512, G4x512, G8x512, G8x512K16,
+    Rep16x256, Rep16x512, Rep16x512Stamped,
+    Count
+};
+// What follows from the instance alone.  min_grid: all pivot workgroups lie among the first 8 G blocks of the grid; the 16-workgroup
+// instances of blocks of 8 and 12 were measured (and are tested) on 136 workgroups and more
+struct BtLoopShape { int groups, nt, kb; bool wave_rec, stamped, rep; int min_grid; };
+inline BtLoopShape bt_loop_shape(BtLoop i) {
+    switch (i) {
+        case BtLoop::G8x256: return {8, 256, 8, false, false, false, 64};
+        case BtLoop::G8x256Stamped: return {8, 256, 8, false, true, false, 64};
+        case BtLoop::G16x128: return {16, 128, 8, false, false, false, 136};
+        case BtLoop::G16x128Wave: return {16, 128, 8, true, false, false, 136};
+        case BtLoop::G16x128Stamped: return {16, 128, 8, false, true, false, 136};
+        case BtLoop::G16x128WaveStamped: return {16, 128, 8, true, true, false, 136};
+        case BtLoop::G16x256K12: return {16, 256, 12, false, false, false, 136};
+        case BtLoop::G16x256K16: return {16, 256, 16, false, false, false, 128};   // (pivot blocks: x + 8 j, j < 16, x <= 6)
+        case BtLoop::G2x512: return {2, 512, 8, false, false, false, 16};
+        case BtLoop::G4x512: return {4, 512, 8, false, false, false, 32};
+        case BtLoop::G8x512: return {8, 512, 8, false, false, false, 64};
+        case BtLoop::G8x512K16: return {8, 512, 16, false, false, false, 64};
+        case BtLoop::Rep16x256: return {16, 256, 8, false, false, true, 136};
+        case BtLoop::Rep16x512: return {16, 512, 8, false, false, true, 136};
+        case BtLoop::Rep16x512Stamped: return {16, 512, 8, false, true, true, 136};
+        default: return {0, 0, 0, false, false, false, 0};
+    }
+}
+
 // ---- device-batched relaxations (batch_kernels.hip, engine_batch.cpp) ------------------------------------------------
 // One BatchLP per relaxation of a wave, resident in HBM.  `bt` is the argument block of the block kernels for the
 // relaxation's current phase; the control kernel (k_b_ctrl) rewrites it at the phase changes, so the host enqueues a fixed

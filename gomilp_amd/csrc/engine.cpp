@@ -80,12 +80,32 @@ void Engine::loop_release(int dev, int weight, int slot) {
     L.cv.notify_all();
 }
 
+int BtKnobs::set(const std::string &key, int64_t v) {
+    if (key == "chunk") { if (v < 1) return GOMILP_ERR_BAD_SHAPE; chunk = v; }
+    else if (key == "max_pivots") max_pivots = v < 0 ? 0 : v;
+    else if (key == "block_k") { if (v < 0 || v > bt_max_k()) return GOMILP_ERR_BAD_SHAPE; block_k = v; }
+    else if (key == "bt_nt") { if (v != 0 && v != 256 && v != 512 && v != 1024) return GOMILP_ERR_BAD_SHAPE; bt_nt = v; }
+    else if (key == "bt_old") bt_old = v ? 1 : 0;
+    else if (key == "bt_stamps") bt_stamps = v < 0 ? 0 : (v > 2 ? 2 : v);
+    else if (key == "bt_groups") { if (v != -1 && v != 0 && v != 2 && v != 4 && v != 8 && v != 16) return GOMILP_ERR_BAD_SHAPE; bt_groups = v; }
+    else if (key == "bt_lag") bt_lag = v ? 1 : 0;
+    else if (key == "loop_chunk") { if (v < 32) return GOMILP_ERR_BAD_SHAPE; loop_chunk = v; }
+    else if (key == "loop_grid") { if (v < 0 || v > 4096) return GOMILP_ERR_BAD_SHAPE; loop_grid = v; }
+    else if (key == "loop_upd") { if (v < 0) return GOMILP_ERR_BAD_SHAPE; loop_upd = v; }
+    else if (key == "loop_rep") loop_rep = v ? 1 : 0;
+    else if (key == "loop_g") { if (v != 0 && v != 8 && v != 16) return GOMILP_ERR_BAD_SHAPE; loop_g = v; }
+    else if (key == "loop_wave_rec") loop_wave_rec = v ? 1 : 0;
+    else if (key == "loop_k") { if (v != 0 && v != 8 && v != 12 && v != 16) return GOMILP_ERR_BAD_SHAPE; loop_k = v; }
+    else return -1;
+    return GOMILP_OK;
+}
+
 int Engine::set(const std::string &key, int64_t v) {
     std::lock_guard<std::mutex> g(mu_);
-    if (key == "chunk") { if (v < 1) return GOMILP_ERR_BAD_SHAPE; chunk_ = v; }
-    else if (key == "refresh") { if (v < 0) return GOMILP_ERR_BAD_SHAPE; refresh_ = v; }
+    const int bt = bt_knobs_.set(key, v);
+    if (bt >= 0) return bt;
+    if (key == "refresh") { if (v < 0) return GOMILP_ERR_BAD_SHAPE; refresh_ = v; }
     else if (key == "trace") trace_on_ = v ? 1 : 0;
-    else if (key == "max_pivots") max_pivots_ = v < 0 ? 0 : v;
     else if (key == "sample_events") sample_events_ = v < 0 ? 0 : v;
     else if (key == "fused") fused_ = v ? 1 : 0;
     else if (key == "lu_look") lu_look_ = v ? 1 : 0;
@@ -93,8 +113,6 @@ int Engine::set(const std::string &key, int64_t v) {
     else if (key == "lu_blocked") lu_blocked_ = v < 0 ? 0 : (v > 2 ? 3 : v);  // 0 per column, 1 blocked panels, 2 compressed rounds (slot panel), 3 the same with the look-ahead schedule (default; lu_compressed.hip)
     else if (key == "tableau") tableau_ = v ? 1 : 0;
     else if (key == "blocked") blocked_ = v ? 1 : 0;
-    else if (key == "bt_nt") { if (v != 0 && v != 256 && v != 512 && v != 1024) return GOMILP_ERR_BAD_SHAPE; bt_nt_ = v; }
-    else if (key == "bt_old") bt_old_ = v ? 1 : 0;
     else if (key == "bt_upd_valu") bt_upd_valu_ = v ? 1 : 0;
 #ifdef GOMILP_DEBUG
     else if (key == "bt_fault") bt_fault_ = v;   // fault injection, diagnostic flavour only: 1 a workgroup of the block / loop kernels, 2 the U-solve workgroup of the look-ahead LU
@@ -103,21 +121,10 @@ int Engine::set(const std::string &key, int64_t v) {
     else if (key == "lu_cross") lu_cross_ = v < 0 ? -1 : (v > 2 ? 2 : v);   // the panel's rows on the workgroups of one XCD (lu_cross.hip): 0 never, 1 sixteen slots in the plain schedule, 2 thirty-two slots in the schedule lu_blocked names, -1 (default) 2 for bases of 1281 .. 2048 rows
     else if (key == "general_block") general_block_ = v ? 1 : 0;
     else if (key == "general_min_rows") general_min_rows_ = v < 2 ? 2 : v;
-    else if (key == "bt_groups") { if (v != -1 && v != 0 && v != 2 && v != 4 && v != 8 && v != 16) return GOMILP_ERR_BAD_SHAPE; bt_groups_ = v; }
-    else if (key == "bt_stamps") bt_stamps_ = v < 0 ? 0 : (v > 2 ? 2 : v);   // 2: the loop kernel keeps its production shape (16 x 128 threads up to 2048 rows); 1: 8 x 256
-    else if (key == "loop_wave_rec") loop_wave_rec_ = v ? 1 : 0;
-    else if (key == "bt_lag") bt_lag_ = v ? 1 : 0;
     else if (key == "exact_degenerate") { if (v < 0 || v > 3) return GOMILP_ERR_BAD_SHAPE; exact_degenerate_ = v; }   // 3: strict — EVERY pivot decided on fresh gonum-order solves (engine_tableau.cpp exact_step)
-    else if (key == "loop_grid") { if (v < 0 || v > 4096) return GOMILP_ERR_BAD_SHAPE; loop_grid_ = v; }
-    else if (key == "loop_chunk") { if (v < 32) return GOMILP_ERR_BAD_SHAPE; loop_chunk_ = v; }
     else if (key == "cond_guard") cond_guard_ = v ? 1 : 0;
     else if (key == "poll_delay") { if (v < 0 || v > 64) return GOMILP_ERR_BAD_SHAPE; poll_delay_ = v; }
-    else if (key == "loop_upd") { if (v < 0) return GOMILP_ERR_BAD_SHAPE; loop_upd_ = v; }
-    else if (key == "loop_rep") loop_rep_ = v ? 1 : 0;
-    else if (key == "loop_g") { if (v != 0 && v != 8 && v != 16) return GOMILP_ERR_BAD_SHAPE; loop_g_ = v; }
-    else if (key == "loop_k") { if (v != 0 && v != 8 && v != 12 && v != 16) return GOMILP_ERR_BAD_SHAPE; loop_k_ = v; }
     else if (key == "row_chunk") { if (v < 0 || v % 512 != 0 || v > kLdsWindowLd) return GOMILP_ERR_BAD_SHAPE; row_chunk_ = v; }   // (whole 256-double2 steps of wave_dot_row)
-    else if (key == "block_k") { if (v < 0 || v > bt_max_k()) return GOMILP_ERR_BAD_SHAPE; block_k_ = v; }
     else return GOMILP_ERR_BAD_SHAPE;
     return GOMILP_OK;
 }
@@ -634,7 +641,7 @@ int Engine::run_loop(const Problem &P, int phase, double tol, int nn, const doub
     Work &w = *w_;
     DevState &hs = *w.st_host;
     hs.done = 0; hs.status = ST_RUNNING; hs.pivots = 0; hs.q = hs.p = -1; hs.rq = hs.dp = hs.mv = 0;
-    hs.max_pivots = max_pivots_;
+    hs.max_pivots = bt_knobs_.max_pivots;
     hs.lu_singular = 0;
     sync_state_to_device();  // trace_len is cumulative over the solve
     int64_t since_refresh = 0;
@@ -644,7 +651,7 @@ int Engine::run_loop(const Problem &P, int phase, double tol, int nn, const doub
     for (;;) {
         const int64_t before = hs.pivots;
         std::vector<int64_t> sample_t;  // chunk-local pivot index of every sampled pivot
-        for (int64_t t = 0; t < chunk_; t++) {
+        for (int64_t t = 0; t < bt_knobs_.chunk; t++) {
             LPArgs a = make_args(P, phase, tol, nn, cost);
             a.binv_cur = w.binv[(cur_ + t) & 1];
             a.binv_next = w.binv[(cur_ + t + 1) & 1];
@@ -780,8 +787,8 @@ int Engine::run_loop_fused(const Problem &P, int phase, double tol, int nn, cons
     for (;;) {
         const int64_t before = hs.pivots;
         std::vector<int64_t> sample_t;
-        int64_t nlaunch = chunk_;
-        if (max_pivots_ > 0) nlaunch = std::min<int64_t>(nlaunch, std::max<int64_t>(1, max_pivots_ - hs.pivots + 1));
+        int64_t nlaunch = bt_knobs_.chunk;
+        if (bt_knobs_.max_pivots > 0) nlaunch = std::min<int64_t>(nlaunch, std::max<int64_t>(1, bt_knobs_.max_pivots - hs.pivots + 1));
         for (int64_t t = 0; t < nlaunch; t++, tseg++) {
             const int pending = tseg > 0;
             LPArgs a = make_args(P, phase, tol, nn, cost);
@@ -812,7 +819,7 @@ int Engine::run_loop_fused(const Problem &P, int phase, double tol, int nn, cons
         account_samples(st, sample_t, executed + 1, 2);
         const int64_t T = hs.pivots - seg_start;
         if (!hs.done) {
-            if (max_pivots_ > 0 && hs.pivots >= max_pivots_) { cur_ = (c0 + T) & 1; ycur_ = (y0 + T) & 1; ret = GOMILP_ERR_UNSUPPORTED; break; }
+            if (bt_knobs_.max_pivots > 0 && hs.pivots >= bt_knobs_.max_pivots) { cur_ = (c0 + T) & 1; ycur_ = (y0 + T) & 1; ret = GOMILP_ERR_UNSUPPORTED; break; }
             if (refresh_ > 0 && since_refresh >= refresh_) {
                 cur_ = (int)((c0 + T) & 1); ycur_ = (int)((y0 + T) & 1);
                 refresh_xb_y(P, cost);
@@ -866,14 +873,14 @@ int Engine::solve_cold_locked(int64_t id, double tol, const int64_t *initial_bas
                               int64_t *basis_out, gomilp_lp_stats *stats) {
     xchg_timeout_ = false;
     int rc = solve_locked(id, tol, initial_basic, opt_f, opt_x, has_x, basis_out, stats);
-    if (rc == GOMILP_ERR_DEVICE && xchg_timeout_ && bt_groups_ >= 0) {
+    if (rc == GOMILP_ERR_DEVICE && xchg_timeout_ && bt_knobs_.bt_groups >= 0) {
         // The workgroups of the multi-workgroup block kernel wait for each other; when one of them was not resident within the
         // bounded wait (a crowded device) the launch gives up.  That says nothing about the problem: once more on the
         // single-workgroup kernels, which depend on nobody.
-        const int64_t keep = bt_groups_;
-        bt_groups_ = -1;
+        const int64_t keep = bt_knobs_.bt_groups;
+        bt_knobs_.bt_groups = -1;
         rc = solve_locked(id, tol, initial_basic, opt_f, opt_x, has_x, basis_out, stats);
-        bt_groups_ = keep;
+        bt_knobs_.bt_groups = keep;
         if (stats) stats->device_retries = 1;
     }
     return rc;

@@ -75,6 +75,38 @@ struct LuPlan {
 };
 struct LuRoundsEnd { bool gave_up = false, landed = false; int enq = 0; };   // Engine::run_compressed_rounds
 
+// The knobs that decide which block kernel runs a relaxation, and in which shape (gomilp_ctx_set; the routing table of DESIGN.md §2.1).
+struct BtKnobs {
+    int64_t chunk = 32, max_pivots = 0;           // pivots enqueued between host checks; safety cap (0 = none)
+    int64_t block_k = 0, bt_nt = 0, bt_old = 0;   // single-workgroup block kernel: pivots per block and threads (0 = by shape; tests force the 1024-thread instance), first generation only
+    int64_t bt_groups = 0;                        // -1 never several workgroups, 0 by shape, 2 / 4 / 8 forced where the shape fits, 16 the loop shapes also below 600 rows
+    int64_t bt_stamps = 0;                        // diagnostic builds with cycle sums per wave: 1 the 8 x 256 loop instance, 2 the production shape (16 x 128 up to 2048 rows)
+    int64_t bt_lag = 1, loop_chunk = 512;         // persistent loop kernel where the multi-workgroup block kernel runs (0: launch pairs); its pivots per launch
+    int64_t loop_grid = 0, loop_upd = 0;          // its workgroups (0: by shape, one per CU at most); its update workgroups that take part (0: the instance's default)
+    int64_t loop_g = 0, loop_k = 0;               // its pivot workgroups (8 / 16) and pivots per block (8 / 12 / 16) where instantiated, 0 = by shape
+    int64_t loop_wave_rec = 1, loop_rep = 0;      // 16 x 128 instance: one exchange record per wave; opt-in role with replicated reduced costs (btr_kernels.hip)
+    int set(const std::string &key, int64_t v);   // GOMILP_OK, GOMILP_ERR_BAD_SHAPE (value out of range), -1: not one of these knobs
+};
+
+// Which block kernel runs the pivot loop of a relaxation on the blocked tableau, and in which shape (the table of DESIGN.md §2.1): ONE
+// value, a pure function of (m, ldt) and the knobs above (engine_tableau.cpp), made whenever the engine sets ldt_.  Set-up pivots,
+// make_bt_args, the loop and the launchers read it; nothing downstream looks at a knob or calls bt_group_cfg again.
+struct BtPlan {
+    enum Pipeline : int { kSingle, kGroups, kLoop } pipeline = kSingle;   // block kernel of one workgroup / of several + update launches; persistent loop kernel
+    int m = 0, ldt = 0;
+    int K = 8;                                         // pivots per block
+    bool tiled = false, tiled_forced = false;          // T in 4x4 tiles inside the pivot loop; for a block of one forced pivot (set-up, artificial exchange)
+    BtGroupCfg cfg = {0, 0, 0};                        // bt_group_cfg's shape: set-up / forced pivots, make_bt_args (groups 0: one workgroup)
+    BtLoop loop = BtLoop::None;                        // kLoop: the instance that runs,
+    int slot_weight = 4, upd_cap = 0;                  //   the device slots it takes (1 shares the device with up to three others, 4 runs alone) and BTArgs::upd_cap
+    BtLoop rep = BtLoop::None;                         // knob loop_rep: the replicated role that runs INSTEAD if Engine::loop_try_acquire_all gives the device right now
+    int rep_upd_cap = 0;
+    int64_t blocks_per_chunk = 1, loop_grid = 0;       // blocks between two looks at the device state (loop: per launch); knob loop_grid
+    bool is_loop() const { return pipeline == kLoop; }
+    int grid(int ncu, BtLoop inst) const;              // workgroups of a loop launch on a device of ncu CUs
+    static BtPlan make(int m, int ldt, const BtKnobs &k);
+};
+
 class Engine {
    public:
     explicit Engine(int device);
@@ -191,8 +223,8 @@ class Engine {
                       const std::vector<double> *binv_host);
     void bt_layout(const Problem &P, bool tiled);
     BTArgs make_bt_args(const Problem &P, int phase, double tol, int nn, int kmax);
-    // block size and tableau layout of the blocked pipeline for the current ldt_ (knobs block_k / bt_nt / bt_old / bt_groups)
-    void bt_plan(const Problem &P, int *K, bool *tiled, bool *lag = nullptr) const;
+    // the tableau's row length, and with it the plan of the blocked pipeline
+    void set_ldt(const Problem &P, int ldt) { ldt_ = ldt; bt_plan_ = BtPlan::make(P.m, ldt, bt_knobs_); }
     int bt_forced_pivot(const Problem &P, int phase, double tol, int nn, int q, int p, int nocommit);
     int run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_lp_stats *st);
     void account_samples(gomilp_lp_stats *st, const std::vector<int64_t> &sample_t, int64_t executed, int nk);
@@ -230,7 +262,6 @@ class Engine {
                            double *binv_dst, bool *rebuilt, gomilp_lp_stats *st);
     int cond_check(const Problem &P, int nn, double *k1, double *kinf);
     int cond_fresh(const Problem &P, const int32_t *basic_host, double *k1, double *kinf);   // from a fresh host inverse of the basis
-    int groups_knob(const Problem &P) const;
     bool ensure_host_A(const Problem &P);
     // findLinearlyIndependent with the scan on the device (general_kernels.hip) and the last, square step on the host
     int find_independent_device(const Problem &P, std::vector<int32_t> &basic, std::vector<double> *binv_out, bool *binv_on_device = nullptr);
@@ -252,25 +283,18 @@ class Engine {
     double *up_dA_ = nullptr; size_t up_dA_cap_ = 0;
     int32_t *up_stats_ = nullptr; size_t up_stats_cap_ = 0;
     std::unique_ptr<Work> w_;
-    // knobs
+    // knobs (Engine::set)
+    BtKnobs bt_knobs_;             // which block kernel runs, in which shape
+    int64_t refresh_ = 0, trace_on_ = 0, sample_events_ = 0, fused_ = 1, tableau_ = 1, blocked_ = 1, bt_upd_valu_ = 0, bt_fault_ = 0;
+    int64_t poll_delay_ = 0;       // loop kernel: 64-cycle units between a wave's post and its first poll of an exchange
+    int64_t general_device_ = 1, general_block_ = 1, general_min_rows_ = 96, lu_blocked_ = 3, lu_cross_ = -1;
+    int64_t lu_look_ = 1;          // 0 = never the look-ahead schedule (the workers of a pool)
+    int64_t lu_large_ = 0;         // 1 = bases of 4097 .. 16384 rows take the compressed rounds on the eight-workgroup panel with several rows per lane (lu_cross.hip); 0 (default, and the workers of a pool) = one launch per column there
+    int64_t exact_degenerate_ = 1; // 0 never, 1 bases of up to 256 rows and every non-slack start, 2 always: pivots whose winning ratio is (nearly) zero are decided on a fresh gonum-order x_B; 3 strict: EVERY pivot and the stop test are decided on fresh gonum-order solves
+    int64_t cond_guard_ = 1;       // replay the condition guards of the reference on the host for bases of up to 64 rows
+    int64_t row_chunk_ = 0;        // doubles per LDS chunk of the revised-simplex kernels' staged vectors; 0: one-pass staging up to ld = kLdsWindowLd, chunks of kAutoRowChunk beyond
     int64_t lu_look_faults_ = 0;   // final solves repeated with the plain schedule after a look-ahead launch gave up a wait
     int lu_look_fault_ = 0;        // ... in the running solve, one per fall-back (stats.device_retries)
-    int64_t lu_look_ = 1;          // knob lu_look: 0 = never the look-ahead schedule (the workers of a pool)
-    int64_t lu_large_ = 0;         // knob lu_large: 1 = bases of 4097 .. 16384 rows take the compressed rounds on the eight-workgroup panel with several rows per lane (lu_cross.hip); 0 (default, and the workers of a pool) = one launch per column there
-    int64_t chunk_ = 32, refresh_ = 0, trace_on_ = 0, max_pivots_ = 0, sample_events_ = 0, fused_ = 1, lu_blocked_ = 3, tableau_ = 1, blocked_ = 1, block_k_ = 0,  // block_k_ 0 = auto
-            bt_nt_ = 0, bt_old_ = 0, bt_stamps_ = 0, bt_upd_valu_ = 0, bt_fault_ = 0, general_device_ = 1, general_block_ = 1, general_min_rows_ = 96, lu_cross_ = -1, bt_groups_ = 0,   // bt_groups_: -1 never, 0 by shape, 2 / 4 / 8 forced
-            bt_lag_ = 1,       // persistent loop kernel where the multi-workgroup block kernel runs (0: block kernel + update launches)
-            loop_chunk_ = 512, // pivots per launch of the persistent loop kernel
-            loop_grid_ = 0,    // its workgroups (0: one per CU)
-            poll_delay_ = 0,   // loop kernel: 64-cycle units between a wave's post and its first poll of an exchange
-            loop_upd_ = 0,     // update workgroups of the loop kernel that take part (0: all of the grid's)
-            loop_rep_ = 0,     // 1: pivot role with replicated reduced costs (btr_kernels.hip k_bt_loopR: ONE exchange per pivot; bit-identical pivots, measured slower — DESIGN 2.1d) where the shape fits and the engine gets the whole device
-            loop_g_ = 0,       // its pivot workgroups (0 / 16: 16 x 128 threads up to 2048 rows, 16 x 256 beyond; 8: 8 x 256 / 8 x 512)
-            loop_wave_rec_ = 1,   // its 16 x 128 instance: one exchange record per wave, no workgroup stage in front of a post (0: one per workgroup)
-            loop_k_ = 0,       // its pivots per block (0: 8 up to 2048 rows, 16 beyond; 8 / 16 forced where instantiated)
-            exact_degenerate_ = 1,   // 0 never, 1 bases of up to 256 rows and every non-slack start, 2 always: pivots whose winning ratio is (nearly) zero are decided on a fresh gonum-order x_B; 3 strict: EVERY pivot and the stop test are decided on fresh gonum-order solves
-            cond_guard_ = 1,   // replay the condition guards of the reference on the host for bases of up to 64 rows
-            row_chunk_ = 0;    // doubles per LDS chunk of the revised-simplex kernels' staged vectors; 0: one-pass staging up to ld = kLdsWindowLd, chunks of kAutoRowChunk beyond
     bool lds_window_only_ = false;   // refuse problems beyond the one-pass LDS window, as before the chunked form (pool workers)
     bool badly_scaled_ = false;   // the current problem's entries span more than nine decades (Problem::scale_span): guard on, tableau checked
     bool gen_binv_dev_ = false;   // the searched basis' B^-1 = R^-1 Q^T is resident in the first B^-1 buffer (the device judged the square step): no upload
@@ -279,14 +303,15 @@ class Engine {
     double lp_guard_ = 0.0;       // LPArgs::guard of that loop (0 for every other solve): the exact steps of Engine::run_loop
     std::vector<double> exact_xb_;   // the fresh x_B of the last exact step (exact_iter)
     bool xchg_timeout_ = false;   // the last pivot loop ended in ST_XCHG_TIMEOUT (Engine::solve repeats the solve once)
-    bool shadow_trace_ = false;   // this solve records its pivots for the replay even when the caller did not ask for a trace   // developer knobs of the block kernels (per context: tests force the 1024-thread instance)
+    bool shadow_trace_ = false;   // this solve records its pivots for the replay even when the caller did not ask for a trace
     // per-solve state
     int cur_ = 0;   // which Binv buffer is current
     int ycur_ = 0;  // which y buffer is current
     int grid_ratio_ = 1;
-    int tcur_ = 0, rcur_ = 0, ldt_ = 0;
+    int tcur_ = 0, rcur_ = 0, ldt_ = 0;   // tableau pipelines: current T / r buffer, row length of T (set_ldt)
+    BtPlan bt_plan_;         // blocked tableau: the plan for (the problem being solved, ldt_)
     bool t_tiled_ = false;   // layout of T[tcur_]: 4x4 tiles (blocked pipeline, register-resident kernel) or row-major
-    bool use_bt_ = false;  // blocked tableau (deferred rank-K updates) instead of one launch per pivot  // tableau pipeline: current T / r buffer, row length of T  // workgroups of the last ratio-test kernel (partials to reduce)
+    bool use_bt_ = false;    // blocked tableau (deferred rank-K updates) instead of one launch per pivot
     int64_t launches_ = 0;
     double fs_device_ = 0, fs_host_ = 0;
     int64_t lu_dense_ = 0, lu_rounds_ = 0;
@@ -381,13 +406,13 @@ void launch_bt_tile(const double *src, double *dst, int m, int ldt, bool to_tile
 void launch_bt_inner(const BTArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 void launch_bt_update(const BTArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 bool bt_loop_supported(const BtGroupCfg &c);
-void launch_bt_loop(const BTArgs &a, int ncu, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+bool launch_bt_loop(BtLoop inst, const BTArgs &a, int grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1);   // false: not an instance of k_bt_loop, or a grid below BtLoopShape::min_grid
 // btr_kernels.hip
 bool bt_loop_rep_supported(int m, int ldt);
 int bt_loop_rep_threads(int m, int ldt);
 long long bt_loop_rep_launches();
 long long bt_loop_wave_rec_launches();
-void launch_bt_loop_rep(const BTArgs &a, int ncu, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+bool launch_bt_loop_rep(BtLoop inst, const BTArgs &a, int grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1);   // (the Rep* instances)
 bool bt_batch_supported(int m_max, int ldt_max);
 int bt_batch_k(int m_max, int ldt_max);
 void launch_bt_inner_batch(const BatchLP *lps, const int *ids, const int *count, int nlp, int m_max, int ldt_max, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, int xcd_off = 0);

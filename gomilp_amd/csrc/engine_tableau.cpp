@@ -110,6 +110,7 @@ int Engine::run_loop_tab(const Problem &P, int phase, double tol, int nn, gomilp
     HIP_TRY(hipEventRecord(w.ev[0], stream_));
     int ret = GOMILP_OK;
     const bool sampling = sample_events_ > 0;
+    const int64_t max_pivots = bt_knobs_.max_pivots;
     int c0 = tcur_, r0 = rcur_;
     long long tseg = 0;          // next kernel index in the segment
     int64_t applied = 0;         // pending launches enqueued in the segment
@@ -118,8 +119,8 @@ int Engine::run_loop_tab(const Problem &P, int phase, double tol, int nn, gomilp
     for (;;) {
         const int64_t before = hs.pivots;
         std::vector<int64_t> sample_t;
-        int64_t nlaunch = chunk_;
-        if (max_pivots_ > 0) nlaunch = std::min<int64_t>(nlaunch, std::max<int64_t>(1, max_pivots_ - hs.pivots + 1));
+        int64_t nlaunch = bt_knobs_.chunk;
+        if (max_pivots > 0) nlaunch = std::min<int64_t>(nlaunch, std::max<int64_t>(1, max_pivots - hs.pivots + 1));
         const int64_t applied_before = applied;
         for (int64_t t = 0; t < nlaunch; t++, tseg++) {
             const int pending = (tseg > 0 || first_pending) ? 1 : 0;
@@ -153,7 +154,7 @@ int Engine::run_loop_tab(const Problem &P, int phase, double tol, int nn, gomilp
         }
         const int64_t T = hs.pivots - seg_start;  // pivots applied and committed in this segment
         if (!hs.done) {
-            if (max_pivots_ > 0 && hs.pivots >= max_pivots_) { tcur_ = (c0 + T) & 1; rcur_ = (r0 + T) & 1; ret = GOMILP_ERR_UNSUPPORTED; break; }
+            if (max_pivots > 0 && hs.pivots >= max_pivots) { tcur_ = (c0 + T) & 1; rcur_ = (r0 + T) & 1; ret = GOMILP_ERR_UNSUPPORTED; break; }
             continue;
         }
         tcur_ = (int)((c0 + T) & 1);
@@ -196,38 +197,84 @@ void Engine::bt_layout(const Problem &P, bool tiled) {
     t_tiled_ = tiled;
 }
 
-// knob "bt_groups" as the shape functions see it: by default (0) relaxations of 600..1024 rows also take the loop-kernel shapes
-// (value 16) — the persistent kernel's 3.75 us per pivot with the update hidden beat the single-workgroup block kernel's 3.1 us +
-// update + two launch boundaries per 8 pivots (loop of C2: 5.27 -> 4.74 ms; 600 rows: 1.24 -> 1.13; 700: 2.56 -> 2.35; 900: 2.73 ->
-// 2.48); at 512 rows the two are level (1.21 ms both) and the 520-row children of the 512-row trees keep the single-workgroup kernel
-int Engine::groups_knob(const Problem &P) const {
-    if (bt_groups_ != 0 || !bt_lag_ || bt_stamps_ || block_k_ != 0 || max_pivots_ != 0) return (int)bt_groups_;
-    const int need = std::max(P.m, ldt_);
-    return (P.m >= 600 && need <= 1024) ? 16 : 0;
+// The one place that says which block kernel runs a relaxation of m rows and ldt tableau columns, in which shape (the
+// routing table; tests/test_bt_plan.py).  No HIP call, no Engine: shape functions of the kernel files and the knobs.
+BtPlan BtPlan::make(int m, int ldt, const BtKnobs &k) {
+    BtPlan p;
+    p.m = m; p.ldt = ldt; p.loop_grid = k.loop_grid;
+    const int need = std::max(m, ldt);
+    const bool stamps = k.bt_stamps != 0, g8 = k.loop_g == 8;
+    const bool loop_allowed = k.bt_lag && k.block_k == 0 && k.max_pivots == 0;
+    // by default relaxations of 600..1024 rows also take the loop-kernel shapes (bt_group_cfg's knob value 16) — the persistent kernel's
+    // 3.75 us per pivot with the update hidden beat the single-workgroup block kernel's 3.1 us + update + two launch boundaries per 8
+    // pivots (loop of C2: 5.27 -> 4.74 ms; 600 rows: 1.24 -> 1.13; 700: 2.56 -> 2.35; 900: 2.73 -> 2.48); at 512 rows the two are level
+    // (1.21 ms both) and the 520-row children of the 512-row trees keep the single-workgroup kernel
+    const bool promote = k.bt_groups == 0 && loop_allowed && !stamps && m >= 600 && need <= 1024;
+    p.cfg = k.bt_old ? BtGroupCfg{0, 0, 0} : bt_group_cfg(m, ldt, promote ? 16 : (int)k.bt_groups);
+    if (!p.cfg.groups) {
+        // block size: 8 when the block's rank-1 terms fit in registers (bt_kernels.hip), else 16
+        p.K = k.block_k > 0 ? (int)k.block_k : (bt_reg_k(m, ldt, (int)k.bt_nt) > 0 ? 8 : 16);
+        p.tiled = bt_tiled(m, ldt, p.K, (int)k.bt_nt, k.bt_old != 0);
+    } else {   // multi-workgroup block kernel: 16 terms per row / column in registers, tiled layout
+        p.pipeline = kGroups; p.tiled = true;
+        p.K = k.block_k > 0 ? (int)std::min<int64_t>(k.block_k, 16) : 16;
+    }
+    p.tiled_forced = p.tiled || bt_tiled(m, ldt, 1, (int)k.bt_nt, k.bt_old != 0);
+    // persistent loop kernel (default, btg_kernels.hip k_bt_loop): blocks of 8 pivots, 8 lagging + 8 current terms, the rank-8 update of
+    // block t applied by the other workgroups of the same launch beside block t+1; only the one-row-per-thread shapes (bt_loop_supported),
+    // and of the diagnostic builds only those of the 256-thread class exist
+    if (p.cfg.groups && loop_allowed && (!stamps || p.cfg.nt == 256) && bt_loop_supported(p.cfg)) {
+        p.pipeline = kLoop; p.K = 8;
+        int upd_default = 0;
+        if (p.cfg.nt == 512 && p.cfg.groups == 8) {   // 2049..4096 rows (or knob bt_groups = 8)
+            // blocks of 16: there the rank-8 update of a 134 MB tableau takes longer than 8 pivots, and 16 + 16 terms still fit the 256
+            // registers of a 512-thread workgroup.  16 pivot workgroups of 256 threads (one wave per SIMD: the per-pivot chain of the
+            // 2048-row shape) instead of 8 of 512 — inside the loop kernel only; set-up pivots and the batched schedule keep cfg
+            if (k.loop_k == 8) p.loop = BtLoop::G8x512;
+            else if (g8) { p.loop = BtLoop::G8x512K16; p.K = 16; }
+            else if (k.loop_k == 12) { p.loop = BtLoop::G16x256K12; p.K = 12; }
+            else { p.loop = BtLoop::G16x256K16; p.K = 16; }
+            // beyond 2048 rows the tableau pair (268 MB at 4096 x 4096) no longer fits the Infinity Cache: all 240 update workgroups
+            // stream a block at the full HBM rate in 51 of its 84 us and the pivot workgroups' dependent tableau reads queue behind
+            // them; 112 spread the same bytes over ~60 us (measured per solve of C4: 240: 50.3 ms, 170: 49.0, 140: 47.8, 110: 47.0, 90: 48.9,
+            // 70: 57.9 — update-bound from there)
+            if (bt_loop_shape(p.loop).groups == 16) upd_default = 112;
+        } else if (p.cfg.nt == 512) {   // knob bt_groups = 2 / 4
+            p.loop = p.cfg.groups == 2 ? BtLoop::G2x512 : BtLoop::G4x512;
+        } else if (g8 || k.bt_stamps == 1) {   // up to 2048 rows, knobs: the 8 x 256 shape of cfg itself
+            p.loop = stamps ? BtLoop::G8x256Stamped : BtLoop::G8x256;
+        } else if (k.loop_k == 16 && !stamps) {
+            // knob loop_k = 16 on the 1025..2048-row class: blocks of 16 on 16 x 256 threads (the 4096-row instance) — half the update
+            // traffic per pivot, which is what several such loop kernels side by side run out of (gomilp_frontier_solve_roots, large_loop).
+            // It shares the device like the 128-thread shape: 256-thread workgroups, two per CU, grid of half the CUs
+            p.loop = BtLoop::G16x256K16; p.K = 16; p.slot_weight = 1;
+        } else {
+            // up to 2048 rows: 16 x 128 threads (two waves per workgroup: a cheaper workgroup stage in front of every exchange; measured
+            // 11.47 ms against 11.85 ms per solve of the metric LP for 8 x 256; 8 x 128 threads measured the same at 1024 rows: 4.74
+            // against 4.75 ms per loop of C2).  The 128-thread shape shares the device with up to three others (engine.cpp loop_acquire)
+            p.loop = k.loop_wave_rec ? (stamps ? BtLoop::G16x128WaveStamped : BtLoop::G16x128Wave) : (stamps ? BtLoop::G16x128Stamped : BtLoop::G16x128);
+            p.slot_weight = 1;
+        }
+        p.upd_cap = k.loop_upd ? (int)k.loop_upd : upd_default;
+        // The pivot role with replicated reduced costs (btr_kernels.hip): 512-thread workgroups that fill a CU each, so the launch must
+        // own the device — run_loop_bt takes it only if nobody else holds a loop slot right now (no waiting: busy means p.loop as before)
+        if (k.loop_rep && !g8 && p.K == 8 && p.cfg.nt == 256 && bt_loop_rep_supported(m, ldt)) {
+            const bool wide = bt_loop_rep_threads(m, ldt) == 512;
+            p.rep = wide ? (stamps ? BtLoop::Rep16x512Stamped : BtLoop::Rep16x512) : BtLoop::Rep16x256;
+            p.rep_upd_cap = k.loop_upd ? (int)k.loop_upd : (wide ? 0 : 112);   // (112: what the 16 x 256 threads of this instance got from the rule above)
+        }
+    }
+    // one launch of the loop kernel per chunk of loop_chunk pivots; block + update launches: chunk pivots between two looks at the state
+    p.blocks_per_chunk = p.is_loop() ? std::max<int64_t>(4, k.loop_chunk / p.K) : std::max<int64_t>(1, k.chunk / p.K);
+    return p;
 }
 
-void Engine::bt_plan(const Problem &P, int *K, bool *tiled, bool *lag) const {
-    const BtGroupCfg gc = bt_old_ ? BtGroupCfg{0, 0, 0} : bt_group_cfg(P.m, ldt_, groups_knob(P));
-    if (lag) *lag = false;
-    if (gc.groups) {   // multi-workgroup block kernel: 16 terms per row / column in registers, tiled layout
-        *K = block_k_ > 0 ? (int)std::min<int64_t>(block_k_, 16) : 16;
-        *tiled = true;
-        // persistent loop kernel (default, btg_kernels.hip k_bt_loop): blocks of 8 pivots, 8 lagging + 8 current terms, the rank-8
-        // update of block t applied by the other workgroups of the same launch beside block t+1
-        // (512-thread shapes — beyond 2048 rows — run blocks of 16: there the rank-8 update of a 134 MB tableau takes longer than 8
-        // pivots, and 16 + 16 terms still fit the 256 registers of a 512-thread workgroup)
-        if (lag && bt_lag_ && block_k_ == 0 && max_pivots_ == 0 && (!bt_stamps_ || gc.nt == 256) && bt_loop_supported(gc)) {
-            *lag = true;
-            *K = (gc.nt == 512 && gc.groups == 8 && loop_k_ != 8) ? (loop_k_ == 12 && loop_g_ != 8 ? 12 : 16) : 8;
-            // knob loop_k = 16 on the 1025..2048-row class: blocks of 16 on 16 x 256 threads (the 4096-row instance) — half the update
-            // traffic per pivot, which is what several such loop kernels side by side run out of (gomilp_frontier_solve_roots, large_loop)
-            if (gc.nt == 256 && gc.groups == 8 && loop_k_ == 16 && loop_g_ != 8 && !bt_stamps_) *K = 16;
-        }
-        return;
-    }
-    // block size: 8 when the block's rank-1 terms fit in registers (bt_kernels.hip), else 16
-    *K = block_k_ > 0 ? (int)block_k_ : (bt_reg_k(P.m, ldt_, (int)bt_nt_) > 0 ? 8 : 16);
-    *tiled = bt_tiled(P.m, ldt_, *K, (int)bt_nt_, bt_old_ != 0);
+// workgroups of a loop launch: the instance's pivot blocks + update workgroups for 256 KB of tableau each, at most one per CU (measured
+// at 2048 x 2048: 128 workgroups 12.0 ms per solve, 256: 12.4, 512: 13.6; at 4096 x 4096: 256 64.3 ms, 128 68.4 — and a grid beyond
+// one 512-thread workgroup per CU is not resident as a whole: the launch gives up after its bounded waits)
+int BtPlan::grid(int ncu, BtLoop inst) const {
+    const int64_t g = loop_grid > 0 ? loop_grid : std::min<int64_t>(ncu, std::max<int64_t>(64, (int64_t)m * ldt * 8 / (256 << 10)));
+    return (int)std::max<int64_t>(g, bt_loop_shape(inst).min_grid);
 }
 
 BTArgs Engine::make_bt_args(const Problem &P, int phase, double tol, int nn, int kmax) {
@@ -240,8 +287,8 @@ BTArgs Engine::make_bt_args(const Problem &P, int phase, double tol, int nn, int
     a.basic = w.basic; a.nonbasic = w.nonbasic; a.st = w.st;
     a.trace = (trace_on_ || shadow_trace_) ? w.trace : nullptr; a.trace_cap = w.trace_cap;
     a.forced_q = a.forced_p = -1; a.forced_nocommit = 0;
-    a.nt_force = (int)bt_nt_; a.old_only = bt_old_ ? 1 : 0;
-    a.stamps = bt_stamps_ ? w.stamps : nullptr;
+    a.nt_force = (int)bt_knobs_.bt_nt; a.old_only = bt_knobs_.bt_old ? 1 : 0;
+    a.stamps = bt_knobs_.bt_stamps ? w.stamps : nullptr;
     a.upd_valu = bt_upd_valu_ ? 1 : 0;
     a.fault = bt_fault_ == 1 ? 1 : 0;
     // degenerate vertices decided on a fresh gonum-order x_B: by default for bases of up to 256 rows, and for
@@ -253,8 +300,8 @@ BTArgs Engine::make_bt_args(const Problem &P, int phase, double tol, int nn, int
     a.guard = exact_degenerate_ == 3 ? std::numeric_limits<double>::infinity()
                                      : (exact_degenerate_ == 2 || (exact_degenerate_ == 1 && (P.m <= 256 || gen_start_ || badly_scaled_))) ? 1e-9 : 0.0;
     a.cguard = (cond_guard_ && !gen_start_ && P.m > 64) ? 1e-9 : 0.0;   // (<= 64 rows: the per-pivot replay of Engine::solve; general starts: the guard above is on)
-    if (a.tiled && !bt_old_) {
-        const BtGroupCfg gc = bt_group_cfg(P.m, ldt_, groups_knob(P));
+    if (a.tiled) {   // (never under knob bt_old: BtPlan::make)
+        const BtGroupCfg &gc = bt_plan_.cfg;
         a.groups = gc.groups; a.group_ri = gc.ri; a.group_nt = gc.nt; a.xbuf = w.xbuf;
     }
     return a;
@@ -266,7 +313,7 @@ int Engine::bt_forced_pivot(const Problem &P, int phase, double tol, int nn, int
     DevState &hs = *w.st_host;
     hs.done = 0; hs.status = ST_RUNNING; hs.kdone = 0;
     sync_state_to_device();
-    { int K1; bool tiled1; bt_plan(P, &K1, &tiled1); bt_layout(P, tiled1 || bt_tiled(P.m, ldt_, 1, (int)bt_nt_, bt_old_ != 0)); }
+    bt_layout(P, bt_plan_.tiled_forced);
     BTArgs a = make_bt_args(P, phase, tol, nn, 1);
     a.forced_q = q; a.forced_p = p; a.forced_nocommit = nocommit;
     launch_bt_inner(a, stream_, nullptr, nullptr);
@@ -462,40 +509,40 @@ int Engine::exact_iter(const Problem &P, int phase, double tol, int nn, double *
     return -GOMILP_ERR_BLAND;                   // :382
 }
 
-// Pivot loop: blocks of block_k_ pivots (one single-workgroup launch) followed by one rank-K update launch.
+// Pivot loop of the blocked tableau, as bt_plan_ says: blocks of K pivots (one block-kernel launch) each followed by one rank-K update
+// launch, or launches of the persistent loop kernel that run both.
 int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_lp_stats *st) {
     Work &w = *w_;
     DevState &hs = *w.st_host;
     hs.done = 0; hs.status = ST_RUNNING; hs.pivots = 0; hs.kdone = 0; hs.bland_steps = 0; hs.lu_singular = 0;
-    int K; bool tiled_plan, lag;
-    bt_plan(P, &K, &tiled_plan, &lag);
+    const BtPlan plan = bt_plan_;
+    const int K = plan.K;
+    const bool lag = plan.is_loop();
+    const int64_t max_pivots = bt_knobs_.max_pivots;
     // The persistent loop kernel needs all its workgroups resident (they wait for each other) and takes one slot on every CU:
     // one at a time per device.  Concurrent solves of large LPs queue up here for the duration of their pivot loops (set-up and
     // final solve still overlap); many large LPs at once belong in the device-batched schedule (gomilp_frontier_solve_roots).
+    // The replicated role (plan.rep) must own the device: taken only if nobody else holds a loop slot right now, no waiting — busy
+    // means plan.loop on a slot of the plan's weight
     struct LoopSlot {
-        int dev, weight, slot = -1;
-        LoopSlot(int d, int w2, bool on) : dev(d), weight(w2) { if (on) slot = Engine::loop_acquire(d, w2); }
+        int dev, weight = 4, slot = -1; bool rep = false;
+        LoopSlot(int d, const BtPlan &p) : dev(d) {
+            if (!p.is_loop()) return;
+            rep = p.rep != BtLoop::None && Engine::loop_try_acquire_all(d);
+            slot = rep ? 0 : Engine::loop_acquire(d, weight = p.slot_weight);
+        }
         ~LoopSlot() { if (slot >= 0) Engine::loop_release(dev, weight, slot); }
-    };
-    // (weight: the 128-thread shape shares the device with up to three others, every other shape runs alone — engine.cpp)
-    // (the 2048-row class in blocks of 16 — knob loop_k — shares the device too: 256-thread workgroups, two per CU, grid of half the CUs)
-    const bool small_loop = lag && (K == 8 || K == 16) && loop_g_ != 8 && bt_stamps_ != 1 && bt_group_cfg(P.m, ldt_, groups_knob(P)).nt == 256;
-    // The pivot role with replicated reduced costs (btr_kernels.hip): 512-thread workgroups that fill a CU each, so the launch must own
-    // the device — taken only if nobody else holds a loop slot right now (no waiting: busy means the shared 16 x 128 shape as before)
-    const BtGroupCfg gc0 = bt_group_cfg(P.m, ldt_, groups_knob(P));
-    const bool rep_ok = lag && K == 8 && loop_rep_ && loop_g_ != 8 && gc0.groups == 8 && gc0.nt == 256 && gc0.ri == 1 && bt_loop_rep_supported(P.m, ldt_);
-    struct RepHold {
-        int dev; bool held;
-        RepHold(int d, bool want) : dev(d), held(want && Engine::loop_try_acquire_all(d)) {}
-        ~RepHold() { if (held) Engine::loop_release(dev, 4, 0); }
-    } rep_hold(device_, rep_ok);
-    LoopSlot loop_slot(device_, small_loop ? 1 : 4, lag && !rep_hold.held);
-    const int loop_xcd = (small_loop && loop_slot.slot > 0) ? 2 * loop_slot.slot : 0;
-    bt_layout(P, tiled_plan);
+    } loop_slot(device_, plan);
+    // the instance that runs, for every launch of this loop; concurrent loop kernels keep their pivot workgroups on XCDs of their own
+    const BtLoop loop_inst = loop_slot.rep ? plan.rep : plan.loop;
+    const BtLoopShape loop_shape = bt_loop_shape(loop_inst);
+    const int loop_upd_cap = loop_slot.rep ? plan.rep_upd_cap : plan.upd_cap;
+    const int loop_xcd = (loop_slot.weight == 1 && loop_slot.slot > 0) ? 2 * loop_slot.slot : 0;
+    bt_layout(P, plan.tiled);
     // persistent loop kernel: DevState::tsel2 hands the buffer that holds the tableau from launch to launch
     hs.tsel2[0] = hs.tsel2[1] = tcur_; hs.kdone2[0] = hs.kdone2[1] = 0; hs.loop_blocks = 0;
     sync_state_to_device();
-    if (bt_stamps_) {   // diagnostic build of the block kernel: cycle sums per wave and pivot segment
+    if (bt_knobs_.bt_stamps) {   // diagnostic build of the block kernel: cycle sums per wave and pivot segment
         const size_t nb = (size_t)(16 * kBtStampSegs + 8) * sizeof(unsigned long long);
         if (!w.stamps) {
             HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.stamps), nb));
@@ -505,9 +552,8 @@ int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_
     }
     const double t_loop0 = now_s();
     int ret = GOMILP_OK;
-    // persistent loop kernel: one launch per chunk of loop_chunk_ pivots (the host learns the buffer choice from the state it
-    // reads anyway)
-    const int64_t blocks_per_chunk = lag ? std::max<int64_t>(4, loop_chunk_ / K) : std::max<int64_t>(1, chunk_ / K);
+    // persistent loop kernel: one launch per chunk (the host learns the buffer choice from the state it reads anyway)
+    const int64_t blocks_per_chunk = plan.blocks_per_chunk;
     const bool sampling = sample_events_ > 0;
     int64_t block_no = 0;
     // launch parity: a launch reads the counter bases / buffer choice the PREVIOUS launch of this context wrote (whichever loop
@@ -538,25 +584,9 @@ int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_
         if (lag) {   // the whole chunk is one launch
             BTArgs ai = make_bt_args(P, phase, tol, nn, K);
             ai.loop = 1; ai.nblocks = (int)nblocks; ai.par = (int)(launch_no & 1);
-            // 2049..4096 rows: 16 pivot workgroups of 256 threads (one wave per SIMD: the per-pivot chain of the 2048-row shape)
-            // instead of 8 of 512 — inside the loop kernel only; set-up pivots and the batched schedule keep bt_group_cfg's shape
-            if (ai.groups == 8 && ai.group_nt == 512 && ai.group_ri == 1 && loop_g_ != 8 && (K == 16 || K == 12)) { ai.groups = 16; ai.group_nt = 256; }
-            const bool k16_small = ai.groups == 8 && ai.group_nt == 256 && ai.group_ri == 1 && loop_g_ != 8 && K == 16;
-            if (k16_small) ai.groups = 16;   // (16 x 256 threads, blocks of 16: the instance of the 4096-row class)
-            // 1025..2048 rows: 16 x 128 threads (two waves per workgroup: a cheaper workgroup stage in front of every exchange; measured
-            // 11.47 ms against 11.85 ms per solve of the metric LP for 8 x 256)
-            const bool rep = rep_hold.held && ai.groups == 8 && ai.group_nt == 256 && ai.group_ri == 1;
-            if (rep) { ai.groups = 16; ai.group_nt = bt_loop_rep_threads(P.m, ldt_); }
-            else if (ai.groups == 8 && ai.group_nt == 256 && ai.group_ri == 1 && loop_g_ != 8 && K == 8 && bt_stamps_ != 1) {
-                ai.groups = 16; ai.group_nt = 128; ai.wave_rec = loop_wave_rec_ ? 1 : 0;   // (8 x 128 threads measured the same at 1024 rows: 4.74 against 4.75 ms per loop of C2)
-            }
+            ai.groups = loop_shape.groups; ai.group_nt = loop_shape.nt; ai.wave_rec = loop_shape.wave_rec ? 1 : 0;   // (make_bt_args: the shape of set-up pivots)
             ai.Tbuf[0] = w.T[0]; ai.Tbuf[1] = w.T[1];
-            ai.xcd = loop_xcd; ai.upd_cap = (int)loop_upd_; ai.poll_delay = (int)poll_delay_;
-            // beyond 2048 rows the tableau pair (268 MB at 4096 x 4096) no longer fits the Infinity Cache: all 240 update workgroups
-            // stream a block at the full HBM rate in 51 of its 84 us and the pivot workgroups' dependent tableau reads queue behind
-            // them; 112 spread the same bytes over ~60 us (measured per solve of C4: 240: 50.3 ms, 170: 49.0, 140: 47.8, 110: 47.0, 90: 48.9,
-            // 70: 57.9 — update-bound from there)
-            if (ai.upd_cap == 0 && ai.groups == 16 && ai.group_nt == 256 && !k16_small) ai.upd_cap = 112;
+            ai.xcd = loop_xcd; ai.upd_cap = loop_upd_cap; ai.poll_delay = (int)poll_delay_;
             ai.exact_once = exact_pending ? 1 : 0; exact_pending = false;
             ai.forced_q = forced_q_pending; ai.forced_p = forced_p_pending; forced_q_pending = forced_p_pending = -1;
             hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -565,13 +595,8 @@ int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_
                 e0 = w.sample_ev[samp_total * 6]; e1 = w.sample_ev[samp_total * 6 + 1];
                 samp_total++; info[slot].nsamp++;
             }
-            // workgroups: the 8 G pivot blocks + update workgroups for 256 KB of tableau each, at most one per CU (measured at
-            // 2048 x 2048: 128 workgroups 12.0 ms per solve, 256: 12.4, 512: 13.6; at 4096 x 4096: 256 64.3 ms, 128 68.4 — and a
-            // grid beyond one 512-thread workgroup per CU is not resident as a whole: the launch gives up after its bounded waits)
-            int grid = (int)std::min<int64_t>(ncu_, std::max<int64_t>(64, (int64_t)P.m * ldt_ * 8 / (256 << 10)));
-            if (loop_grid_ > 0) grid = (int)loop_grid_;
-            if (rep) launch_bt_loop_rep(ai, grid, stream_, e0, e1);
-            else launch_bt_loop(ai, grid, stream_, e0, e1);
+            const int grid = plan.grid(ncu_, loop_inst);
+            if (!(loop_shape.rep ? launch_bt_loop_rep(loop_inst, ai, grid, stream_, e0, e1) : launch_bt_loop(loop_inst, ai, grid, stream_, e0, e1))) return GOMILP_ERR_DEVICE;
             launch_no++; block_no += nblocks; launches_++;
             HIP_TRY(hipMemcpyAsync(w.pipe_state[slot], w.st, sizeof(DevState), hipMemcpyDeviceToHost, stream_));
             HIP_TRY(hipEventRecord(w.pipe_ev[slot], stream_));
@@ -579,7 +604,7 @@ int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_
         }
         for (int64_t bkk = 0; bkk < nblocks; bkk++, block_no++) {
             int kmax = K;
-            if (max_pivots_ > 0) kmax = (int)std::max<int64_t>(1, std::min<int64_t>(K, max_pivots_ - before_pred - bkk * K));
+            if (max_pivots > 0) kmax = (int)std::max<int64_t>(1, std::min<int64_t>(K, max_pivots - before_pred - bkk * K));
             BTArgs a = make_bt_args(P, phase, tol, nn, kmax);
             a.kmax = K;  // the update kernel is instantiated for the configured block size
             BTArgs ai = a; ai.kmax = kmax;
@@ -613,7 +638,7 @@ int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_
         // keep one chunk in flight behind the one whose state is awaited (not past a pivot budget)
         // (not behind the very first chunk: short loops — B&B children — usually end inside it, and the speculative
         // chunk would be pure no-op launches)
-        const bool more = !(max_pivots_ > 0 && pred >= max_pivots_);
+        const bool more = !(max_pivots > 0 && pred >= max_pivots);
         const bool speculate = more && seen > seg0;
         if (speculate) { int rc1 = enqueue_chunk(cur ^ 1, pred, blocks_per_chunk); if (rc1 != GOMILP_OK) return rc1; pred += blocks_per_chunk * K; }
         HIP_TRY(hipEventSynchronize(w.pipe_ev[cur]));
@@ -641,7 +666,7 @@ int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_
         seen = hs.pivots;
         last_par = ci.par;
         if (!hs.done) {
-            if (max_pivots_ > 0 && hs.pivots >= max_pivots_) { ret = GOMILP_ERR_UNSUPPORTED; break; }
+            if (max_pivots > 0 && hs.pivots >= max_pivots) { ret = GOMILP_ERR_UNSUPPORTED; break; }
             if (!more) { ret = GOMILP_ERR_UNSUPPORTED; break; }
             if (!speculate) { int rc1 = enqueue_chunk(cur ^ 1, pred, blocks_per_chunk); if (rc1 != GOMILP_OK) return rc1; pred += blocks_per_chunk * K; }
             cur ^= 1;
@@ -695,7 +720,7 @@ int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_
     }
     // host clock from the first launch to the arrival of the final state: no extra event / sync per loop (the loop is
     // GPU-bound: the host only waits for chunk states)
-    if (bt_stamps_ && w.stamps) {
+    if (bt_knobs_.bt_stamps && w.stamps) {
         const size_t nb = (size_t)(16 * kBtStampSegs + 8) * sizeof(unsigned long long);
         HIP_TRY(hipMemcpyAsync(w.stamps_host, w.stamps, nb, hipMemcpyDeviceToHost, stream_));
         HIP_TRY(sync_stream());
@@ -737,17 +762,16 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
     std::vector<double> art(P.ld, 0.0);  // Phase-I artificial column (simplex.go:533-542)
     bool binv_on_device = gen_binv_dev_;   // (the device search left B^-1 = R^-1 Q^T in place: engine.cpp find_independent_device)
     auto set_up_T = [&](int nn) -> int {  // T = B^-1 A_N
-        ldt_ = tab_ld(nn);
+        set_ldt(P, tab_ld(nn));
+        // straight into the layout the block kernels want: no conversion pass before the first pivot
+        t_tiled_ = use_bt_ && bt_plan_.tiled;
         if (!binv_host) {  // slack basis: B^-1 is the permutation rho
-            // straight into the layout the block kernels want: no conversion pass before the first pivot
-            { int K0; bool tl0; bt_plan(P, &K0, &tl0); t_tiled_ = use_bt_ && tl0; }
             launch_tab_gather(P.dAt, P.ld, m, nn, w.nonbasic, w.rho, w.T[0], ldt_, t_tiled_, stream_);
             launches_++;
             return GOMILP_OK;
         }
         // general basis: B^-1 from the host (engine_general.cpp), T = B^-1 A_N as a device GEMM over the resident columns
-        // (At row n holds the Phase-I artificial column); straight into the layout the block kernels want
-        { int K0; bool tl0; bt_plan(P, &K0, &tl0); t_tiled_ = use_bt_ && tl0; }
+        // (At row n holds the Phase-I artificial column)
         if (!binv_on_device) {
             HIP_TRY(hipMemcpy2DAsync(w.binv[0], (size_t)P.ld * sizeof(double), binv_host->data(), (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
                                      hipMemcpyHostToDevice, stream_));
@@ -911,7 +935,7 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
         launch_tab_permute_cols(w.T[tcur_], ldt_, w.T[tcur_ ^ 1], ldt2, m, nn2, w.srcpos, t_tiled_, stream_);
         launches_++;
         tcur_ ^= 1;
-        ldt_ = ldt2;
+        set_ldt(P, ldt2);
         nn = nn2;
         if ((rc = upload_index_lists(basic, nonbasic)) != GOMILP_OK) return rc;
     } else {

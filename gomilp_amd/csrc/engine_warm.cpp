@@ -238,7 +238,7 @@ int Engine::run_dual_loop(const Problem &P, double tol, int nn, int dual_budget,
         const int64_t before = hs.pivots;
         // children usually need a handful of dual pivots: a short first chunk (no-op launches behind the end cost a launch each);
         // never more than the budget + 1 (the launch that sees the budget spent)
-        const int64_t nt = std::min<int64_t>(before == 0 ? 4 : chunk_, dual_budget - before + 1);
+        const int64_t nt = std::min<int64_t>(before == 0 ? 4 : bt_knobs_.chunk, dual_budget - before + 1);
         for (int64_t t = 0; t < nt; t++) {
             LPArgs a = make_args(P, 3, tol, nn, P.dc);
             a.binv_cur = w.binv[(cur_ + t) & 1];

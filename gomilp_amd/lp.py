@@ -72,7 +72,7 @@ class FrontierStats(C.Structure):
 
 EXPORTS = [
     "gomilp_lp_solve_warm", "gomilp_frontier_solve_warm", "gomilp_pool_release_warm",
-    "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond", "gomilp_debug_lu_host_solve",
+    "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond", "gomilp_debug_lu_host_solve", "gomilp_debug_bt_plan",
     "gomilp_lp_simplex", "gomilp_ctx_create", "gomilp_ctx_destroy", "gomilp_ctx_device", "gomilp_ctx_set",
     "gomilp_lp_upload", "gomilp_lp_free", "gomilp_lp_solve_resident", "gomilp_lp_last_trace", "gomilp_version",
     "gomilp_device_count", "gomilp_compiled_arch", "gomilp_comm_unique_id", "gomilp_comm_create", "gomilp_comm_destroy",
@@ -132,6 +132,8 @@ def lib():
     L.gomilp_debug_gonum_lu_cond.argtypes = [dp, C.c_int64, C.c_int, C.POINTER(C.c_double)]
     L.gomilp_debug_lu_host_solve.restype = C.c_int
     L.gomilp_debug_lu_host_solve.argtypes = [C.c_int64, C.c_int64, i32p, i32p, dp, dp, C.c_int, dp, dp]
+    L.gomilp_debug_bt_plan.restype = C.c_int
+    L.gomilp_debug_bt_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_char_p), ip, C.c_int64, ip]
     L.gomilp_debug_find_independent.restype = C.c_int64
     L.gomilp_debug_find_independent_device.restype = C.c_int64
     L.gomilp_debug_find_independent_device.argtypes = [C.c_void_p, C.c_int64, ip, C.c_int64]
@@ -573,6 +575,29 @@ def debug_lu_host_solve(dl, phys, diag, W, rhs, coupled: bool = False):
     if rc < 0:
         raise ValueError("bad shape")
     return x, bool(rc)
+
+
+# the integers of gomilp_debug_bt_plan, in order.  pipeline: 0 single-workgroup block kernel + update launches, 1 multi-workgroup block
+# kernel + update launches, 2 persistent loop kernel; loop / rep: BT_LOOP_INSTANCES (0: none); the loop_* and rep_* fields are 0 without one
+BT_PLAN_FIELDS = ["pipeline", "K", "tiled", "tiled_forced", "cfg_groups", "cfg_nt", "cfg_ri", "blocks_per_chunk",
+                  "loop", "loop_groups", "loop_nt", "loop_kb", "loop_wave_rec", "loop_stamped", "loop_min_grid", "slot_weight", "upd_cap", "grid",
+                  "rep", "rep_nt", "rep_stamped", "rep_upd_cap", "rep_grid"]
+BT_LOOP_INSTANCES = [None, "8x256", "8x256_stamped", "16x128", "16x128_wave", "16x128_stamped", "16x128_wave_stamped", "16x256_k12", "16x256_k16",
+                     "2x512", "4x512", "8x512", "8x512_k16", "rep_16x256", "rep_16x512", "rep_16x512_stamped"]
+
+
+def debug_bt_plan(m: int, ldt: int, ncu: int = 256, **knobs) -> dict:
+    """The engine's BtPlan (gomilp_amd/csrc/engine.hpp) for a relaxation of m rows and ldt tableau columns under `knobs` — host only
+    (no device).  ValueError for a key that is no knob of the plan, or a value gomilp_ctx_set would refuse."""
+    keys = (C.c_char_p * max(1, len(knobs)))(*[k.encode() for k in knobs])
+    vals = (C.c_int64 * max(1, len(knobs)))(*[int(v) for v in knobs.values()])
+    out = (C.c_int64 * len(BT_PLAN_FIELDS))()
+    n = lib().gomilp_debug_bt_plan(m, ldt, len(knobs), keys, vals, ncu, out)
+    if n != len(BT_PLAN_FIELDS):
+        raise ValueError("bad shape, key or value: %r" % ((m, ldt, knobs),))
+    plan = dict(zip(BT_PLAN_FIELDS, out))
+    plan["loop"], plan["rep"] = BT_LOOP_INSTANCES[plan["loop"]], BT_LOOP_INSTANCES[plan["rep"]]
+    return plan
 
 
 def debug_cond_estimate(B, inf: bool = False) -> float:

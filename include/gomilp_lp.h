@@ -115,7 +115,9 @@ int gomilp_ctx_device(const gomilp_ctx *ctx);
  * "trace" (1 = record pivots), "max_pivots" (safety cap, 0 = none).  Developer knobs of the pivot pipelines (tests force
  * kernel instances with them; results do not depend on them): "tableau", "blocked", "block_k", "bt_nt" (threads of the
  * single-workgroup block kernel), "bt_groups" (-1: single-workgroup block kernels only, 0: by shape, 2 / 4 / 8: that many
- * workgroups), "bt_old", "bt_stamps", "sample_events"; of the persistent loop kernel: "bt_lag" (0: the launch pairs of round 2),
+ * workgroups, 16: the loop-kernel shapes also below 600 rows), "bt_old", "bt_stamps", "sample_events" — which block kernel a shape takes under
+ * which of these and of the loop kernel's knobs is ONE table, DESIGN.md section 2.1 ("BtPlan"; probe: gomilp_debug_bt_plan below);
+ * of the persistent loop kernel: "bt_lag" (0: the launch pairs of round 2),
  * "loop_chunk" (pivots per launch), "loop_g" (8 / 16 pivot workgroups), "loop_k" (8 / 12 / 16 pivots per block), "loop_upd"
  * (update workgroups that take part), "loop_grid", "poll_delay", "loop_rep" (default 0, opt-in: the pivot role with replicated reduced costs, ONE exchange
  * per pivot — bit-identical pivots, measured slower: DESIGN.md section 2.1d); "loop_wave_rec" (default 1: the 16 x 128 instance posts one exchange record per wave,
@@ -381,6 +383,13 @@ int gomilp_debug_gonum_lu_cond(const double *M, int64_t n, int transposed, doubl
  * LU.Solve's Det() == 0 test fires (mat/lu.go:301; x is zeroed), 0 when not, -1 for bad arguments.  Tests compare it with the checker's SolveVec. */
 int gomilp_debug_lu_host_solve(int64_t m, int64_t nd, const int32_t *dl, const int32_t *phys, const double *diag, const double *W, int coupled,
                                const double *rhs, double *x);
+/* Diagnostic (host only, no device): which block kernel the blocked tableau would run for a relaxation of m rows and ldt tableau columns
+ * under the given knobs (nknobs key / value pairs, taken through the same range checks as gomilp_ctx_set; only the knobs of the routing
+ * table) on a device of ncu compute units — the fields of the engine's BtPlan (gomilp_amd/csrc/engine.hpp) as
+ * integers, in the order of BT_PLAN_FIELDS in gomilp_amd/lp.py.  out has room for GOMILP_BT_PLAN_FIELDS entries; returns their count, or
+ * -GOMILP_ERR_BAD_SHAPE for a bad shape, key or value. */
+#define GOMILP_BT_PLAN_FIELDS 23
+int gomilp_debug_bt_plan(int64_t m, int64_t ldt, int64_t nknobs, const char *const *keys, const int64_t *values, int64_t ncu, int64_t *out);
 
 /* Library / device probes (no compute): used by the loader checks and by __graft_entry__. */
 const char *gomilp_version(void);
