@@ -6,11 +6,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
-#include <deque>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -19,135 +17,14 @@
 #include <vector>
 
 #include "engine.hpp"
-#include "engine_batch.hpp"
-#include "engine_batch_revised.hpp"
+#include "frontier_pool.hpp"
 #include "lu_host.h"
 
 using gomilp::BatchEngine;
 using gomilp::Engine;
-using gomilp::RevBatchEngine;
 
 struct gomilp_ctx {
     std::unique_ptr<Engine> eng;
-};
-
-// One worker = one Engine (stream + work buffers) with its own resident copy of the root and a persistent host thread;
-// the pivot loops of a wave run device-batched on the pool's BatchEngine (engine_batch.hpp), the workers take what is
-// left per relaxation: the final gonum-order solve of a finished basis, or a whole solve where the batched schedule
-// hands a relaxation back.
-struct gomilp_pool {
-    int device = 0;
-    std::vector<std::unique_ptr<Engine>> eng;
-    std::vector<int64_t> root;  // root problem id inside each engine
-    int64_t m0 = 0, n0 = 0;
-    int batched = 1;            // knob: 0 = every relaxation through a worker's single-relaxation engine (round-1 path)
-    std::unique_ptr<BatchEngine> batch;
-    std::unique_ptr<BatchEngine> batch2;   // second schedule (split waves, waves of large relaxations; created on first use)
-    std::unique_ptr<BatchEngine> batchx[2];   // third and fourth schedule for waves of large relaxations (split_large)
-    int cond_guard = 1, exact_degenerate = 1, sample_batch = 0, batch_loop = 1, batch_res = 0, batch_virt = 1;   // knob values kept for batch2: both halves of a split wave decide alike
-    int split_large = 1;        // knob: waves of >= 4 large relaxations run as two interleaved schedules
-    int split_phase = 1;        // knob: relaxations that start feasible (Phase II from the slack basis: the long pivot chains of a wave) and
-                                // relaxations that need Phase I (on a B&B frontier mostly proved infeasible within a few pivots) run as two
-                                // schedules side by side: a block step of the wide group (hundreds of tableaus gathered / updated) no longer
-                                // sits between two blocks of a long chain
-    int large_loop = 0;         // knob: relaxations of 1025..2048 rows / columns run on the workers' persistent loop kernels (four at a
-                                // time, each with its pivot workgroups on an XCD of its own) instead of the batched launch pairs.  Off:
-                                // measured 342 k pivots/s for 4 metric LPs against 391 k batched — four updates streaming at once
-                                // raise the latency of every chain's agent-scope reads and polls
-    int batch_revised = 1;      // knob: wide waves (n - m >= 2m) that the workers would run on the unguarded revised pipelines take the
-                                // device-batched revised simplex (engine_batch_revised.hpp); 0: every such wave on the workers
-    int warm_revised = 0;       // knob (opt-in): a gomilp_frontier_solve_warm call whose wave passes the wide routing test runs on the batched
-                                // revised simplex too, with warm starts and keeping; 0: such a call goes to the workers, cold
-    int rev_exchange = 1;       // knob: on the batched revised simplex a relaxation whose Phase I ends with the artificial basic at level zero
-                                // exchanges it on the device (batch_revised.hip: k_rv_exch) instead of going to a worker's whole solve — the same
-                                // column, bit-identical results; 0: the hand-over (host_fallbacks)
-    int rev_roots = 1;          // knob: a wide wave that uses several roots, or a root other than the set_root problem (gomilp_frontier_solve_roots),
-                                // runs on the batched revised simplex when every root it uses passes that schedule's test — one schedule for the
-                                // wave, bit-identical results; 0: such a wave on the workers, whole
-    int64_t refresh = 0, max_pivots = 0;   // the workers' knobs of these names, as the batched revised simplex needs them
-    std::unique_ptr<RevBatchEngine> rev;   // created on first use
-    gomilp::WarmStore warm;     // final states kept for warm starts (gomilp_frontier_solve_warm), shared by both schedules
-    Engine::RootView view;      // of eng[0]'s root (all workers hold the same data)
-    // further roots (gomilp_pool_add_root): resident in worker 0's engine only, read in place by the others
-    std::vector<int64_t> extra_root;
-    std::vector<std::unique_ptr<Engine::RootView>> extra_view;
-    std::mutex call_mu;         // one wave at a time per pool
-    // A schedule that runs beside the calling thread's (the wide half of a split wave, the second half of a wave of large LPs) gets a
-    // thread that LIVES with the pool: a std::thread per wave cost, once in ~50 waves, milliseconds (stack mapped and unmapped in a
-    // process full of pinned and device-mapped memory: 6-10 ms waves among 4.0 ms ones in tools/wave_outliers.py).
-    struct Aux {
-        std::thread th;
-        std::mutex mu;
-        std::condition_variable cv;
-        std::function<void()> task;
-        bool has = false, done = true, stop = false;
-        void loop() {
-            for (;;) {
-                std::function<void()> f;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return stop || has; });
-                    if (stop && !has) return;
-                    f = std::move(task); has = false;
-                }
-                f();
-                { std::lock_guard<std::mutex> lk(mu); done = true; }
-                cv.notify_all();
-            }
-        }
-        void run(std::function<void()> f) {
-            { std::lock_guard<std::mutex> lk(mu); task = std::move(f); has = true; done = false; }
-            if (!th.joinable()) th = std::thread([this] { loop(); });
-            cv.notify_all();
-        }
-        void wait() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return done; }); }
-        ~Aux() {
-            { std::lock_guard<std::mutex> lk(mu); stop = true; }
-            cv.notify_all();
-            if (th.joinable()) th.join();
-        }
-    };
-    Aux aux[3];
-    // persistent workers
-    std::vector<std::thread> threads;
-    std::mutex mu;
-    std::condition_variable cv, cv_idle;
-    std::deque<std::function<void(int)>> queue;
-    int busy = 0;
-    bool stop = false;
-
-    void worker(int w) {
-        for (;;) {
-            std::function<void(int)> task;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || !queue.empty(); });
-                if (stop && queue.empty()) return;
-                task = std::move(queue.front());
-                queue.pop_front();
-                busy++;
-            }
-            task(w);
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                busy--;
-                if (queue.empty() && busy == 0) cv_idle.notify_all();
-            }
-        }
-    }
-    void submit(std::function<void(int)> f) {
-        { std::lock_guard<std::mutex> lk(mu); queue.push_back(std::move(f)); }
-        cv.notify_one();
-    }
-    void drain() {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_idle.wait(lk, [&] { return queue.empty() && busy == 0; });
-    }
-    ~gomilp_pool() {
-        { std::lock_guard<std::mutex> lk(mu); stop = true; }
-        cv.notify_all();
-        for (auto &t : threads) t.join();
-    }
 };
 
 #ifdef GOMILP_DEBUG
@@ -232,62 +109,17 @@ void gomilp_pool_destroy(gomilp_pool *pool) { delete pool; }
 int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value) {
     if (!pool || !key) return GOMILP_ERR_BAD_SHAPE;
     std::lock_guard<std::mutex> g(pool->call_mu);
-    if (std::string(key) == "batched") { pool->batched = value ? 1 : 0; return GOMILP_OK; }
-    if (std::string(key) == "batch_revised") { pool->batch_revised = value ? 1 : 0; return GOMILP_OK; }
-    if (std::string(key) == "warm_revised") { pool->warm_revised = value ? 1 : 0; return GOMILP_OK; }
-    if (std::string(key) == "rev_exchange") { pool->rev_exchange = value ? 1 : 0; return GOMILP_OK; }
-    if (std::string(key) == "rev_roots") { pool->rev_roots = value ? 1 : 0; return GOMILP_OK; }
-    if (std::string(key) == "split_large") { pool->split_large = value ? 1 : 0; return GOMILP_OK; }
-    if (std::string(key) == "split_phase") { pool->split_phase = value ? 1 : 0; return GOMILP_OK; }
-    if (std::string(key) == "batch_virt") {   // wide waves on virtual tableaus for their first block (default 1)
-        pool->batch_virt = value ? 1 : 0;
-        pool->batch->set_virt(value != 0);
-        if (pool->batch2) pool->batch2->set_virt(value != 0);
-        for (auto &bx : pool->batchx) if (bx) bx->set_virt(value != 0);
-        return GOMILP_OK;
-    }
-    if (std::string(key) == "batch_res") {   // block steps of narrow waves in the register-resident kernel (opt-in, default 0: k_b_loop / launch pairs)
-        pool->batch_res = value ? 1 : 0;
-        pool->batch->set_res(value != 0);
-        if (pool->batch2) pool->batch2->set_res(value != 0);
-        for (auto &bx : pool->batchx) if (bx) bx->set_res(value != 0);
-        return GOMILP_OK;
-    }
-    if (std::string(key) == "batch_loop") {   // block steps of narrow waves in the persistent loop kernel (default 1)
-        pool->batch_loop = value ? 1 : 0;
-        pool->batch->set_loop(value != 0);
-        if (pool->batch2) pool->batch2->set_loop(value != 0);
-        for (auto &bx : pool->batchx) if (bx) bx->set_loop(value != 0);
-        return GOMILP_OK;
-    }
-    if (std::string(key) == "large_loop") { pool->large_loop = value ? 1 : 0; return GOMILP_OK; }
-    if (std::string(key) == "lu_large") return GOMILP_OK;   // accepted, and left at 0 on the workers (gomilp_pool_create)
-    if (std::string(key) == "sample_batch") {
-        pool->sample_batch = value != 0;
-        pool->batch->set_sampling(value != 0);
-        if (pool->batch2) pool->batch2->set_sampling(value != 0);
-        for (auto &bx : pool->batchx) if (bx) bx->set_sampling(value != 0);
-        return GOMILP_OK;
-    }
-#ifdef GOMILP_DEBUG
-    if (std::string(key) == "bt_fault") { pool->batch->set_fault((int)value); if (pool->batch2) pool->batch2->set_fault((int)value); }   // (and the workers' engines below)
-#endif
-    if (std::string(key) == "cond_guard") {
-        pool->cond_guard = (int)value;
-        pool->batch->set_cond_guard((int)value);
-        if (pool->batch2) pool->batch2->set_cond_guard((int)value);
-        for (auto &bx : pool->batchx) if (bx) bx->set_cond_guard((int)value);
-    }
-    if (std::string(key) == "exact_degenerate") {   // (and the workers' engines below)
-        pool->exact_degenerate = (int)value;
-        pool->batch->set_exact_degenerate((int)value);
-        if (pool->batch2) pool->batch2->set_exact_degenerate((int)value);
-        for (auto &bx : pool->batchx) if (bx) bx->set_exact_degenerate((int)value);
+    using Scope = gomilp::PoolKnobs::Scope;
+    const Scope sc = gomilp::PoolKnobs::scope(key);
+    if (sc == Scope::Pool || sc == Scope::PoolAndWorkers) {
+        pool->knobs.set(key, value);
+        pool->apply_knobs(*pool->batch);
+        if (pool->batch2) pool->apply_knobs(*pool->batch2);
+        if (sc == Scope::Pool) return GOMILP_OK;
     }
     int rc = GOMILP_OK;
     for (auto &e : pool->eng) { const int r = e->set(key, value); if (r != GOMILP_OK) rc = r; }
-    if (rc == GOMILP_OK && std::string(key) == "refresh") pool->refresh = value;
-    if (rc == GOMILP_OK && std::string(key) == "max_pivots") pool->max_pivots = value < 0 ? 0 : value;
+    if (rc == GOMILP_OK && sc == Scope::WorkersFirst) pool->knobs.set(key, value);
     return rc;
 }
 
@@ -335,383 +167,10 @@ int gomilp_pool_set_root(gomilp_pool *pool, const double *c0, const double *A0, 
     return GOMILP_OK;
 }
 
-}  // extern "C"
-
-// warm: parent / tag / keep per relaxation (each nullable), budget; null: a cold wave
-struct WarmArgs { const int64_t *parent, *tag; const int32_t *keep; int32_t budget; };
-static int frontier_solve_impl(gomilp_pool *pool, int64_t count, const int32_t *root_of, const int64_t *koff, const int32_t *var,
-                               const double *sign, const double *rhs, double tol, double *z_out, double *x_out, int64_t ldx,
-                               int32_t *status_out, int32_t *has_x_out, gomilp_frontier_stats *stats, const WarmArgs *wa) {
-    if (!pool || count < 0 || !koff || !z_out || !x_out || !status_out || !has_x_out) return GOMILP_ERR_BAD_SHAPE;
-    for (auto r : pool->root) if (r < 0) return GOMILP_ERR_BAD_SHAPE;
-    std::lock_guard<std::mutex> call_guard(pool->call_mu);
-    const auto t0 = std::chrono::steady_clock::now();
-    const int nroots = 1 + (int)pool->extra_root.size();
-    std::vector<const Engine::RootView *> views(nroots);
-    views[0] = &pool->view;
-    for (int r = 1; r < nroots; r++) views[r] = pool->extra_view[r - 1].get();
-    for (int64_t i = 0; i < count; i++) {
-        const int ri = root_of ? root_of[i] : 0;
-        if (ri < 0 || ri >= nroots || views[ri]->n > ldx) return GOMILP_ERR_BAD_SHAPE;
-    }
-    auto rootn = [&](int64_t i) -> int64_t { return views[root_of ? root_of[i] : 0]->n; };
-    // child i of root r on worker w: root 0 lives in every worker's engine, the others in worker 0's
-    auto upload_child = [&](int w, int64_t i) -> int64_t {
-        const int ri = root_of ? root_of[i] : 0;
-        const int64_t k0 = koff[i], K = koff[i + 1] - koff[i];
-        Engine &E = *pool->eng[w];
-        if (ri == 0) return E.upload_child(pool->root[w], (int)K, var + k0, sign + k0, rhs + k0);
-        return E.upload_child_of(*pool->eng[0], pool->extra_root[ri - 1], (int)K, var + k0, sign + k0, rhs + k0);
-    };
-    const int W = (int)pool->eng.size();
-    std::vector<gomilp_frontier_stats> ws(W);
-    for (auto &S : ws) S = gomilp_frontier_stats();
-    for (int64_t i = 0; i < count; i++) { z_out[i] = NAN; has_x_out[i] = 0; status_out[i] = GOMILP_ERR_DEVICE; }
-    auto busy_since = [](std::chrono::steady_clock::time_point s0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - s0).count(); };
-    // a whole relaxation on worker w's engine (the round-1 path; also the fall-back of the batched schedule)
-    auto full_solve = [&](int w, int64_t i) {
-        const auto s0 = std::chrono::steady_clock::now();
-        Engine &E = *pool->eng[w];
-        gomilp_frontier_stats &S = ws[w];
-        const int64_t K = koff[i + 1] - koff[i], n0 = rootn(i);
-        int64_t id = upload_child(w, i);
-        if (id < 0) { status_out[i] = (int32_t)-id; return; }
-        std::vector<double> x((size_t)(n0 + K), 0.0);
-        gomilp_lp_stats st;
-        int32_t hx = 0;
-        double z = NAN;
-        const int rc = E.solve(id, tol, nullptr, &z, x.data(), &hx, nullptr, &st);
-        E.free_problem(id);
-        status_out[i] = rc; z_out[i] = z; has_x_out[i] = hx;
-        if (hx) for (int64_t j = 0; j < n0; j++) x_out[i * ldx + j] = x[j];  // subproblem.go:157-159
-        S.relaxations++; S.pivots_phase1 += st.pivots_phase1; S.pivots_phase2 += st.pivots_phase2;
-        S.bland_steps += st.bland_steps; S.phase1_runs += st.phase1_used; S.kernel_launches += st.kernel_launches;
-        S.seconds_busy_sum += busy_since(s0);
-    };
-    // the epilogue of a relaxation whose pivot loops ran device-batched: final gonum-order solve of its basis
-    auto finish = [&](int w, int64_t i, const int32_t *basic, const double *xb, int loop_rc) {
-        const auto s0 = std::chrono::steady_clock::now();
-        Engine &E = *pool->eng[w];
-        gomilp_frontier_stats &S = ws[w];
-        const int64_t K = koff[i + 1] - koff[i], n0 = rootn(i);
-        int64_t id = upload_child(w, i);
-        if (id < 0) { status_out[i] = (int32_t)-id; return; }
-        std::vector<double> x((size_t)(n0 + K), 0.0);
-        gomilp_lp_stats st;
-        int32_t hx = 0;
-        double z = NAN;
-        const double t_up = busy_since(s0);
-        const int rc = E.finish_from_basis(id, basic, xb, loop_rc, &z, x.data(), &hx, nullptr, &st);
-        E.free_problem(id);
-        if (GOMILP_DBG_ENV("GOMILP_DEBUG_TASKS") && busy_since(s0) > 5e-3)
-            fprintf(stderr, "slow finish: worker %d child %lld upload %.2f ms finish %.2f ms (device %.2f host %.2f) rounds %lld dense %lld\n", w, (long long)i, 1e3 * t_up,
-                    1e3 * st.seconds_total, 1e3 * st.seconds_final_device, 1e3 * st.seconds_final_host, (long long)st.lu_rounds, (long long)st.lu_dense_steps);
-        status_out[i] = rc; z_out[i] = z; has_x_out[i] = hx;
-        if (hx) for (int64_t j = 0; j < n0; j++) x_out[i * ldx + j] = x[j];
-        S.kernel_launches += st.kernel_launches;
-        S.seconds_busy_sum += busy_since(s0);
-    };
-    int K_max = 0;
-    for (int64_t i = 0; i < count; i++) K_max = std::max<int>(K_max, (int)(koff[i + 1] - koff[i]));
-    gomilp_frontier_stats agg = gomilp_frontier_stats();
-    BatchEngine::Stats bs;
-    bool use_batch = pool->batched && count > 0;
-    bool any_p1 = false;
-    for (int r = 0; r < nroots && !any_p1; r++) {
-        if (views[r]->gen && !views[r]->unit_basis) any_p1 = true;
-        for (double v : views[r]->hb) if (v < -1e-13) { any_p1 = true; break; }
-    }
-    for (int64_t k = koff[0]; k < koff[count] && !any_p1; k++) if (rhs[k] < -1e-13) any_p1 = true;
-    for (int r = 0; r < nroots && use_batch; r++) use_batch = pool->batch->eligible(*views[r], K_max, any_p1);
-    {
-        // 1025..2048 rows / columns, knob "large_loop": the workers' persistent loop kernels instead (four share the device,
-        // Engine::loop_acquire)
-        int m_big = 0, nn_big = 0;
-        for (int r = 0; r < nroots; r++) { m_big = std::max(m_big, views[r]->m + K_max); nn_big = std::max(nn_big, views[r]->n - views[r]->m + (any_p1 ? 1 : 0)); }
-        const int need = std::max(m_big, gomilp::batch_ldt(nn_big));
-        if (use_batch && pool->large_loop && need > 1024 && need <= 2048) use_batch = false;
-    }
-    // Wide waves: the device-batched revised simplex, where every relaxation of the wave is one that a worker's Engine::solve runs on the
-    // revised pipelines without the exact-step guard (slack starts; a periodic refresh stays on the workers).  Cold calls, and with the
-    // knob warm_revised the warm call: relaxations whose parent's kept state is of this schedule start from it (section 2.6b).
-    // The test runs over the roots the WAVE uses, each with the K range of its own children; roots the pool merely holds do not count.
-    // One used root that fails (narrow, no slack basis, a guarded size, a verify verdict) sends the wave where it went before, whole.
-    bool use_rev = false;
-    if (!use_batch && pool->batched && pool->batch_revised && count > 0 && (!wa || pool->warm_revised) && pool->refresh == 0) {
-        std::vector<int> k_lo((size_t)nroots, INT32_MAX), k_hi((size_t)nroots, -1);
-        bool other_root = false;   // the wave uses more than one root, or a root other than the set_root problem
-        for (int64_t i = 0; i < count; i++) {
-            const int ri = root_of ? root_of[i] : 0, K = (int)(koff[i + 1] - koff[i]);
-            k_lo[(size_t)ri] = std::min(k_lo[(size_t)ri], K); k_hi[(size_t)ri] = std::max(k_hi[(size_t)ri], K);
-            if (ri != 0) other_root = true;
-        }
-        use_rev = pool->rev_roots || !other_root;
-        for (int r = 0; r < nroots && use_rev; r++)
-            if (k_hi[(size_t)r] >= 0) use_rev = RevBatchEngine::eligible(*views[r], k_lo[(size_t)r], k_hi[(size_t)r], pool->exact_degenerate, pool->cond_guard);
-        // (a branch row on one of its root's slack columns: the child has no slack basis)
-        for (int64_t i = 0; i < count && use_rev; i++) {
-            const Engine::RootView &V = *views[root_of ? root_of[i] : 0];
-            const int64_t first_slack = (int64_t)V.n - V.m;
-            for (int64_t k = koff[i]; k < koff[i + 1] && use_rev; k++) if (var[k] < 0 || var[k] >= first_slack) use_rev = false;
-        }
-    }
-    if (use_rev) {
-        if (!pool->rev) pool->rev.reset(new RevBatchEngine(pool->device));
-        auto on_done = [&](int64_t i, const BatchEngine::Outcome &o, const int32_t *basic, const double *xb) {   // (called on this thread)
-            if (o.warm) { agg.warm_started++; agg.pivots_dual += o.pivd; }
-            if (o.stage == gomilp::BS_COLD) { agg.warm_fallbacks++; return; }   // (the schedule solves it cold in the same run and reports it again)
-            if (o.stage != gomilp::BS_DONE) {   // the |x_art| band; with rev_exchange = 0 the zero-level artificial exchange
-                agg.host_fallbacks++;
-                pool->submit([&full_solve, i](int w) { full_solve(w, i); });
-                return;
-            }
-            agg.relaxations++; agg.batched_relaxations++;
-            agg.pivots_phase1 += o.piv1; agg.pivots_phase2 += o.piv2; agg.bland_steps += o.bland; agg.phase1_runs += o.phase1_used;
-            agg.art_exchanges += o.art_exchanges;
-            if (basic) {
-                const int rc0 = o.status;
-                pool->submit([&finish, i, basic, xb, rc0](int w) { finish(w, i, basic, xb, rc0); });
-            } else {
-                status_out[i] = o.status;
-                if (o.status == GOMILP_ERR_UNBOUNDED) z_out[i] = -INFINITY;   // simplex.go:261-263
-            }
-        };
-        RevBatchEngine::Stats rs;
-        bool fits = true;
-        pool->rev->set_exchange(pool->rev_exchange != 0);
-        gomilp::WarmSpec wspec;
-        if (wa) {
-            wspec.store = &pool->warm; wspec.parent = wa->parent; wspec.tag = wa->tag; wspec.keep = wa->keep; wspec.dual_budget = wa->budget;
-        }
-        const int rc = pool->rev->run(views.data(), nroots, root_of, count, koff, var, sign, rhs, tol, pool->max_pivots, on_done, &rs, &fits, wa ? &wspec : nullptr);
-        pool->drain();
-        if (rc != GOMILP_OK) return rc;
-        if (fits) { bs.launches = rs.launches; bs.supersteps = rs.supersteps; bs.seconds_total = rs.seconds_total; bs.warm_kept = rs.warm_kept; }
-        else use_rev = false;   // the wave's buffers do not fit the free device memory: the workers take it, whole
-    }
-    if (use_rev) {
-        // (done above)
-    } else if (use_batch) {
-        std::mutex agg_mu;
-        std::vector<int64_t> cold_again;   // warm starts that spent their dual-pivot budget: solved cold by this same call
-        auto on_done_at = [&](int64_t i, const BatchEngine::Outcome &o, const int32_t *basic, const double *xb) {
-            std::lock_guard<std::mutex> lk(agg_mu);
-            if (o.warm) { agg.warm_started++; agg.pivots_dual += o.pivd; }
-            if (o.stage == gomilp::BS_COLD) { agg.warm_fallbacks++; cold_again.push_back(i); return; }
-            if (o.stage != gomilp::BS_DONE) {   // a path the device schedule does not cover
-                agg.host_fallbacks++;
-                pool->submit([&full_solve, i](int w) { full_solve(w, i); });
-                return;
-            }
-            agg.relaxations++; agg.batched_relaxations++;
-            agg.pivots_phase1 += o.piv1; agg.pivots_phase2 += o.piv2; agg.bland_steps += o.bland; agg.phase1_runs += o.phase1_used;
-            if (o.status == GOMILP_OK || o.status == GOMILP_ERR_BLAND) {
-                const int rc0 = o.status;
-                pool->submit([&finish, i, basic, xb, rc0](int w) { finish(w, i, basic, xb, rc0); });
-            } else {
-                status_out[i] = o.status;
-                if (o.status == GOMILP_ERR_UNBOUNDED) z_out[i] = -INFINITY;   // simplex.go:261-263
-            }
-        };
-        auto on_done = [&](int64_t i, const BatchEngine::Outcome &o, const int32_t *basic, const double *xb) { on_done_at(i, o, basic, xb); };
-        // Large relaxations (8-workgroup block kernel, rank-16 update): a block step of one schedule is [block kernels of all its
-        // relaxations side by side] then [their updates one after the other]; two schedules of half the wave each, on two
-        // streams, put one half's updates under the other half's block kernels.
-        int m_big = 0, nn_big = 0;
-        for (int r = 0; r < nroots; r++) { m_big = std::max(m_big, views[r]->m + K_max); nn_big = std::max(nn_big, views[r]->n - views[r]->m + (any_p1 ? 1 : 0)); }
-        const bool two = pool->split_large && count >= 4 && gomilp::bt_batch_k(m_big, gomilp::batch_ldt(nn_big)) == 16 && !wa;
-        int rc = GOMILP_OK;
-        auto make_batch2 = [&] {
-            if (!pool->batch2) {
-                pool->batch2.reset(new BatchEngine(pool->device));
-                pool->batch2->set_cond_guard(pool->cond_guard);
-                pool->batch2->set_exact_degenerate(pool->exact_degenerate);
-                pool->batch2->set_sampling(pool->sample_batch != 0);
-                pool->batch2->set_loop(pool->batch_loop != 0);
-                pool->batch2->set_res(pool->batch_res != 0);
-                pool->batch2->set_virt(pool->batch_virt != 0);
-            }
-        };
-        auto merge_stats = [&](const BatchEngine::Stats &bs2, bool serial) {
-            bs.launches += bs2.launches; bs.blocks += bs2.blocks; bs.blocks_sampled += bs2.blocks_sampled;
-            bs.supersteps = serial ? bs.supersteps + bs2.supersteps : std::max(bs.supersteps, bs2.supersteps);
-            bs.seconds_inner += bs2.seconds_inner; bs.seconds_update += bs2.seconds_update;
-            bs.seconds_total = serial ? bs.seconds_total + bs2.seconds_total : std::max(bs.seconds_total, bs2.seconds_total);
-            bs.warm_kept += bs2.warm_kept;
-        };
-        // a subset of the wave as a schedule of its own (the schedules take contiguous lists)
-        struct Group { std::vector<int32_t> root_of, var, keep; std::vector<int64_t> koff, parent, tag; std::vector<double> sign, rhs; };
-        // (sized once, rows copied in runs: an 8192-wide wave has 100 k branch rows — element-wise push_backs were 1.5 ms of it, in front of
-        // the first kernel)
-        auto gather = [&](const std::vector<int64_t> &idx, Group &g) {
-            const size_t ng = idx.size();
-            size_t tot = 0;
-            for (int64_t i : idx) tot += (size_t)(koff[i + 1] - koff[i]);
-            g.koff.resize(ng + 1); g.root_of.resize(ng); g.parent.resize(ng); g.tag.resize(ng); g.keep.resize(ng);
-            g.var.resize(std::max<size_t>(tot, 1)); g.sign.resize(std::max<size_t>(tot, 1)); g.rhs.resize(std::max<size_t>(tot, 1));   // (valid pointers for K = 0 everywhere)
-            g.var[0] = 0; g.sign[0] = 0; g.rhs[0] = 0;
-            size_t at = 0;
-            g.koff[0] = 0;
-            for (size_t t = 0; t < ng; t++) {
-                const int64_t i = idx[t];
-                const size_t K = (size_t)(koff[i + 1] - koff[i]);
-                g.root_of[t] = root_of ? root_of[i] : 0;
-                if (K) {
-                    memcpy(&g.var[at], var + koff[i], K * sizeof(int32_t));
-                    memcpy(&g.sign[at], sign + koff[i], K * sizeof(double));
-                    memcpy(&g.rhs[at], rhs + koff[i], K * sizeof(double));
-                }
-                at += K;
-                g.koff[t + 1] = (int64_t)at;
-                g.parent[t] = wa && wa->parent ? wa->parent[i] : -1;
-                g.tag[t] = wa && wa->tag ? wa->tag[i] : -1;
-                g.keep[t] = wa && wa->keep && wa->tag && wa->tag[i] >= 0 ? wa->keep[i] : 0;
-            }
-        };
-        auto run_group = [&](BatchEngine &be, const std::vector<int64_t> &idx, const Group &g, bool start_warm, BatchEngine::Stats *bsx) -> int {
-            gomilp::WarmSpec ws;
-            ws.store = &pool->warm; ws.parent = g.parent.data(); ws.tag = g.tag.data(); ws.keep = g.keep.data();
-            ws.dual_budget = wa ? wa->budget : 0; ws.start_warm = start_warm;
-            auto od = [&, idxp = &idx](int64_t i, const BatchEngine::Outcome &o, const int32_t *basic, const double *xb) { on_done_at((*idxp)[(size_t)i], o, basic, xb); };
-            return be.run_roots(views.data(), nroots, g.root_of.data(), (int64_t)idx.size(), g.koff.data(), g.var.data(), g.sign.data(), g.rhs.data(), tol, od, bsx,
-                                wa ? &ws : nullptr);
-        };
-        // ---- warm starts first: the relaxations whose parent's final state is resident
-        std::vector<int64_t> cold_idx;
-        bool subset = false;   // the cold part is a proper subset of the call (or carries keep flags): gathered lists
-        if (wa) {
-            std::vector<int64_t> warm_idx;
-            for (int64_t i = 0; i < count; i++) {
-                const bool w = wa->parent && wa->parent[i] >= 0 && koff[i + 1] - koff[i] >= 1 && [&] { auto e = pool->warm.find(wa->parent[i]); return e && e->kind == gomilp::WK_TABLEAU; }();
-                (w ? warm_idx : cold_idx).push_back(i);
-            }
-            subset = true;
-            if (!warm_idx.empty()) {
-                Group gw;
-                gather(warm_idx, gw);
-                rc = run_group(*pool->batch, warm_idx, gw, true, &bs);
-                if (rc != GOMILP_OK) { pool->drain(); return rc; }
-                std::lock_guard<std::mutex> lk(agg_mu);
-                for (int64_t i : cold_again) cold_idx.push_back(i);
-                cold_again.clear();
-                std::sort(cold_idx.begin(), cold_idx.end());
-            }
-        }
-        // relaxations that start feasible (slack basis, b >= 0, every branch right-hand side >= 0: Phase II at once) against those that
-        // need Phase I
-        std::vector<int64_t> grp_f, grp_p;
-        const int64_t ncold = subset ? (int64_t)cold_idx.size() : count;
-        if (pool->split_phase && !two && ncold >= 16) {
-            std::vector<char> root_ok(nroots, 0);
-            for (int r = 0; r < nroots; r++) {
-                bool ok = views[r]->unit_basis;
-                for (double v : views[r]->hb) if (v < -1e-13) { ok = false; break; }
-                root_ok[r] = ok ? 1 : 0;
-            }
-            for (int64_t t = 0; t < ncold; t++) {
-                const int64_t i = subset ? cold_idx[(size_t)t] : t;
-                bool f = root_ok[root_of ? root_of[i] : 0] != 0;
-                for (int64_t k = koff[i]; k < koff[i + 1] && f; k++) if (rhs[k] < -1e-13) f = false;
-                (f ? grp_f : grp_p).push_back(i);
-            }
-        }
-        BatchEngine::Stats bsc;   // the cold part
-        if (ncold == 0) {
-            // (every relaxation of the call was a warm start that stayed warm)
-        } else if (!grp_f.empty() && !grp_p.empty()) {
-            Group gf, gp;
-            gather(grp_f, gf);   // (the wide group's lists are put together on its own thread, below: the long chains start at once)
-            make_batch2();
-            BatchEngine::Stats bs2;
-            int rc2 = GOMILP_OK;
-            pool->batch->set_low_priority(true);   // the wide group yields to the long chains
-            pool->batch->set_loop_share(2); pool->batch2->set_loop_share(2);   // two schedules with persistent launches: half the loop slots each
-            // (the long chains on the calling thread: they are the critical path of the wave and start without waiting for a thread to come up)
-            pool->aux[0].run([&] {
-                hipSetDevice(pool->device);
-                gather(grp_p, gp);
-                rc = run_group(*pool->batch, grp_p, gp, false, &bsc);
-            });
-            rc2 = run_group(*pool->batch2, grp_f, gf, false, &bs2);
-            pool->aux[0].wait();
-            pool->batch->set_low_priority(false);
-            pool->batch->set_loop_share(1); pool->batch2->set_loop_share(1);
-            if (rc == GOMILP_OK) rc = rc2;
-            merge_stats(bsc, true); merge_stats(bs2, false);
-        } else if (subset) {
-            Group gc;
-            gather(cold_idx, gc);
-            rc = run_group(*pool->batch, cold_idx, gc, false, &bsc);
-            merge_stats(bsc, true);
-        } else if (two) {
-            // up to four schedules, each with a contiguous quarter of the wave, each on its own stream and host thread, their block kernels on
-            // XCDs of their own (BatchEngine::set_xcd_offset): one schedule's updates and control steps run under the other schedules' blocks
-            make_batch2();
-            const int nsched = (int)std::min<int64_t>(2, count);   // (four schedules — one per LP of a wave of four — measured 363 k pivots / s against 408-440 k for one or two: the chains slow each other through the memory system)
-            BatchEngine *be[4] = {pool->batch.get(), pool->batch2.get(), nullptr, nullptr};
-            for (int t = 2; t < nsched; t++) {
-                if (!pool->batchx[t - 2]) {
-                    pool->batchx[t - 2].reset(new BatchEngine(pool->device));
-                    pool->batchx[t - 2]->set_cond_guard(pool->cond_guard);
-                    pool->batchx[t - 2]->set_exact_degenerate(pool->exact_degenerate);
-                    pool->batchx[t - 2]->set_sampling(pool->sample_batch != 0);
-                    pool->batchx[t - 2]->set_loop(pool->batch_loop != 0);
-                    pool->batchx[t - 2]->set_res(pool->batch_res != 0);
-                    pool->batchx[t - 2]->set_virt(pool->batch_virt != 0);
-                }
-                be[t] = pool->batchx[t - 2].get();
-            }
-            int64_t lo[5];
-            for (int t = 0; t <= nsched; t++) lo[t] = count * t / nsched;
-            BatchEngine::Stats bsx[4];
-            int rcx[4] = {GOMILP_OK, GOMILP_OK, GOMILP_OK, GOMILP_OK};
-            auto run_part = [&](int t) {
-                hipSetDevice(pool->device);
-                const int64_t off = lo[t];
-                auto od = [&, off](int64_t i, const BatchEngine::Outcome &o, const int32_t *basic, const double *xb) { on_done_at(i + off, o, basic, xb); };
-                be[t]->set_xcd_offset((int)((2 * t) & 7));
-                rcx[t] = be[t]->run_roots(views.data(), nroots, root_of ? root_of + off : nullptr, lo[t + 1] - off, koff + off, var, sign, rhs, tol, od, &bsx[t]);
-                be[t]->set_xcd_offset(0);
-            };
-            for (int t = 1; t < nsched; t++) pool->aux[t - 1].run([&run_part, t] { run_part(t); });
-            run_part(0);
-            for (int t = 1; t < nsched; t++) pool->aux[t - 1].wait();
-            bs = bsx[0];
-            for (int t = 0; t < nsched; t++) { if (rc == GOMILP_OK) rc = rcx[t]; if (t) merge_stats(bsx[t], false); }
-        } else {
-            rc = pool->batch->run_roots(views.data(), nroots, root_of, count, koff, var, sign, rhs, tol, on_done, &bs);
-        }
-        agg.warm_kept = bs.warm_kept;
-        pool->drain();
-        if (rc != GOMILP_OK) return rc;
-    } else {
-        for (int64_t i = 0; i < count; i++) pool->submit([&full_solve, i](int w) { full_solve(w, i); });
-        pool->drain();
-    }
-    if (stats) {
-        *stats = agg;
-        for (auto &S : ws) {
-            stats->relaxations += S.relaxations; stats->pivots_phase1 += S.pivots_phase1; stats->pivots_phase2 += S.pivots_phase2;
-            stats->bland_steps += S.bland_steps; stats->phase1_runs += S.phase1_runs; stats->kernel_launches += S.kernel_launches;
-            stats->seconds_busy_sum += S.seconds_busy_sum;
-        }
-        stats->kernel_launches += bs.launches;
-        stats->supersteps = bs.supersteps; stats->seconds_batch = bs.seconds_total;
-        stats->blocks = bs.blocks; stats->blocks_sampled = bs.blocks_sampled;
-        stats->seconds_inner_kernels = bs.seconds_inner; stats->seconds_update_kernels = bs.seconds_update;
-        stats->warm_kept = bs.warm_kept;
-        stats->workers = W; stats->device_id = pool->device;
-        stats->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return GOMILP_OK;
-}
-
-extern "C" {
-
 int gomilp_frontier_solve_roots(gomilp_pool *pool, int64_t count, const int32_t *root_of, const int64_t *koff, const int32_t *var,
                                 const double *sign, const double *rhs, double tol, double *z_out, double *x_out, int64_t ldx,
                                 int32_t *status_out, int32_t *has_x_out, gomilp_frontier_stats *stats) {
-    return frontier_solve_impl(pool, count, root_of, koff, var, sign, rhs, tol, z_out, x_out, ldx, status_out, has_x_out, stats, nullptr);
+    return gomilp::frontier_solve(pool, gomilp::WaveArgs{count, root_of, koff, var, sign, rhs}, tol, z_out, x_out, ldx, status_out, has_x_out, stats, nullptr);
 }
 
 int gomilp_frontier_solve_warm(gomilp_pool *pool, int64_t count, const int64_t *koff, const int32_t *var, const double *sign,
@@ -719,8 +178,8 @@ int gomilp_frontier_solve_warm(gomilp_pool *pool, int64_t count, const int64_t *
                                double tol, double *z_out, double *x_out, int32_t *status_out, int32_t *has_x_out,
                                gomilp_frontier_stats *stats) {
     if (!pool) return GOMILP_ERR_BAD_SHAPE;
-    WarmArgs wa{parent, tag, keep, dual_budget};
-    return frontier_solve_impl(pool, count, nullptr, koff, var, sign, rhs, tol, z_out, x_out, pool->n0, status_out, has_x_out, stats, &wa);
+    gomilp::WarmArgs wa{parent, tag, keep, dual_budget};
+    return gomilp::frontier_solve(pool, gomilp::WaveArgs{count, nullptr, koff, var, sign, rhs}, tol, z_out, x_out, pool->n0, status_out, has_x_out, stats, &wa);
 }
 
 int gomilp_pool_release_warm(gomilp_pool *pool, int64_t tag) {
@@ -824,6 +283,62 @@ int gomilp_debug_bt_plan(int64_t m, int64_t ldt, int64_t nknobs, const char *con
         (int64_t)p.rep, rep.nt, rep.stamped, p.rep_upd_cap, p.rep != gomilp::BtLoop::None ? p.grid((int)ncu, p.rep) : 0};
     for (int i = 0; i < GOMILP_BT_PLAN_FIELDS; i++) out[i] = f[i];
     return GOMILP_BT_PLAN_FIELDS;
+}
+
+// diagnostic (host only, no device): the routing of one frontier wave.  The root views are made here from the fields WavePlan reads; a
+// General made on the host holds null pointers, which its destructor leaves alone.
+int gomilp_debug_wave_plan(int64_t nroots, const int64_t *root_m, const int64_t *root_n, const int32_t *root_flags, const double *root_scale_span,
+                           int64_t count, const int32_t *root_of, const int64_t *koff, const int32_t *var, const double *rhs, int32_t warm_call,
+                           const int32_t *warm, int64_t nspent, const int64_t *spent, int64_t nknobs, const char *const *keys, const int64_t *values,
+                           int32_t *route, int32_t *cut, int32_t *group, int32_t *pos) {
+    if (nroots < 1 || nroots > 64 || !root_m || !root_n || !root_flags || !root_scale_span || count < 0 || count > (1 << 20) || !koff || !var || !rhs ||
+        (warm_call && !warm) || nspent < 0 || (nspent > 0 && (!spent || !warm_call)) || nknobs < 0 || (nknobs > 0 && (!keys || !values)) || !route || !cut || !group || !pos)
+        return -GOMILP_ERR_BAD_SHAPE;
+    std::vector<Engine::RootView> roots((size_t)nroots);
+    std::vector<const Engine::RootView *> views((size_t)nroots);
+    for (int64_t r = 0; r < nroots; r++) {
+        if (root_m[r] < 1 || root_n[r] < 1 || root_m[r] > (1 << 20) || root_n[r] > (1 << 20)) return -GOMILP_ERR_BAD_SHAPE;
+        Engine::RootView &V = roots[(size_t)r];
+        V.m = (int)root_m[r]; V.n = (int)root_n[r]; V.scale_span = root_scale_span[r];
+        V.unit_basis = (root_flags[r] & GOMILP_WP_ROOT_UNIT_BASIS) != 0;
+        if (root_flags[r] & GOMILP_WP_ROOT_GENERAL) V.gen = std::make_shared<Engine::RootView::General>();
+        V.hb.assign((size_t)V.m, 1.0);
+        if (root_flags[r] & GOMILP_WP_ROOT_B_NEGATIVE) V.hb[0] = -1.0;
+        V.verify_status = (root_flags[r] & GOMILP_WP_ROOT_VERIFY_BAD) ? GOMILP_ERR_BAD_SHAPE : GOMILP_OK;
+        views[(size_t)r] = &V;
+    }
+    if (koff[0] < 0) return -GOMILP_ERR_BAD_SHAPE;
+    for (int64_t i = 0; i < count; i++)
+        if (koff[i + 1] < koff[i] || (root_of && (root_of[i] < 0 || root_of[i] >= nroots))) return -GOMILP_ERR_BAD_SHAPE;
+    gomilp::PoolKnobs knobs;
+    for (int64_t i = 0; i < nknobs; i++) if (!keys[i] || !knobs.set(keys[i], values[i])) return -GOMILP_ERR_BAD_SHAPE;   // (a key that is none of the pool's knobs included)
+    const gomilp::WaveArgs w{count, root_of, koff, var, nullptr, rhs};
+    const gomilp::WavePlan plan = gomilp::WavePlan::make(views.data(), (int)nroots, w, warm_call != 0, knobs);
+    *route = plan.route; *cut = gomilp::WavePlan::NONE;
+    for (int64_t i = 0; i < count; i++) { group[i] = GOMILP_WP_GROUP_WHOLE; pos[i] = (int32_t)i; }
+    if (plan.route != gomilp::WavePlan::TABLEAU) return GOMILP_OK;
+    std::vector<int64_t> warm_idx, cold_idx;
+    if (warm_call) {
+        std::vector<int64_t> parent((size_t)count);
+        std::vector<char> resident((size_t)count);
+        for (int64_t i = 0; i < count; i++) { parent[(size_t)i] = warm[i] ? 0 : -1; resident[(size_t)i] = warm[i] != 0; }
+        plan.warm_groups(w, parent.data(), resident.data(), &warm_idx, &cold_idx);
+        for (size_t t = 0; t < warm_idx.size(); t++) { group[warm_idx[t]] = GOMILP_WP_GROUP_WARM; pos[warm_idx[t]] = (int32_t)t; }
+        for (int64_t s = 0; s < nspent; s++) {   // as the wave does after the warm run
+            if (spent[s] < 0 || spent[s] >= count || group[spent[s]] != GOMILP_WP_GROUP_WARM) return -GOMILP_ERR_BAD_SHAPE;
+            group[spent[s]] = GOMILP_WP_GROUP_WHOLE;
+            cold_idx.push_back(spent[s]);
+        }
+        if (!warm_idx.empty()) std::sort(cold_idx.begin(), cold_idx.end());
+    }
+    const gomilp::WavePlan::ColdCut c = plan.cut_cold(views.data(), (int)nroots, w, cold_idx, knobs);
+    *cut = c.cut;
+    if (c.cut == gomilp::WavePlan::ONE_GATHERED) for (size_t t = 0; t < cold_idx.size(); t++) pos[cold_idx[t]] = (int32_t)t;
+    for (size_t t = 0; t < c.feasible.size(); t++) { group[c.feasible[t]] = GOMILP_WP_GROUP_FEASIBLE; pos[c.feasible[t]] = (int32_t)t; }
+    for (size_t t = 0; t < c.phase1.size(); t++) { group[c.phase1[t]] = GOMILP_WP_GROUP_PHASE1; pos[c.phase1[t]] = (int32_t)t; }
+    if (c.cut == gomilp::WavePlan::HALVES)
+        for (int64_t i = 0; i < count; i++) { group[i] = i < c.half ? GOMILP_WP_GROUP_HALF0 : GOMILP_WP_GROUP_HALF1; pos[i] = (int32_t)(i < c.half ? i : i - c.half); }
+    return GOMILP_OK;
 }
 
 int64_t gomilp_debug_find_independent_device(gomilp_ctx *ctx, int64_t problem, int64_t *idx_out, int64_t cap) {

@@ -72,7 +72,7 @@ class FrontierStats(C.Structure):
 
 EXPORTS = [
     "gomilp_lp_solve_warm", "gomilp_frontier_solve_warm", "gomilp_pool_release_warm",
-    "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond", "gomilp_debug_lu_host_solve", "gomilp_debug_bt_plan",
+    "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond", "gomilp_debug_lu_host_solve", "gomilp_debug_bt_plan", "gomilp_debug_wave_plan",
     "gomilp_lp_simplex", "gomilp_ctx_create", "gomilp_ctx_destroy", "gomilp_ctx_device", "gomilp_ctx_set",
     "gomilp_lp_upload", "gomilp_lp_free", "gomilp_lp_solve_resident", "gomilp_lp_last_trace", "gomilp_version",
     "gomilp_device_count", "gomilp_compiled_arch", "gomilp_comm_unique_id", "gomilp_comm_create", "gomilp_comm_destroy",
@@ -134,6 +134,9 @@ def lib():
     L.gomilp_debug_lu_host_solve.argtypes = [C.c_int64, C.c_int64, i32p, i32p, dp, dp, C.c_int, dp, dp]
     L.gomilp_debug_bt_plan.restype = C.c_int
     L.gomilp_debug_bt_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_char_p), ip, C.c_int64, ip]
+    L.gomilp_debug_wave_plan.restype = C.c_int
+    L.gomilp_debug_wave_plan.argtypes = [C.c_int64, ip, ip, i32p, dp, C.c_int64, i32p, ip, i32p, dp, C.c_int32, i32p, C.c_int64, ip, C.c_int64,
+                                         C.POINTER(C.c_char_p), ip, i32p, i32p, i32p, i32p]
     L.gomilp_debug_find_independent.restype = C.c_int64
     L.gomilp_debug_find_independent_device.restype = C.c_int64
     L.gomilp_debug_find_independent_device.argtypes = [C.c_void_p, C.c_int64, ip, C.c_int64]
@@ -598,6 +601,43 @@ def debug_bt_plan(m: int, ldt: int, ncu: int = 256, **knobs) -> dict:
     plan = dict(zip(BT_PLAN_FIELDS, out))
     plan["loop"], plan["rep"] = BT_LOOP_INSTANCES[plan["loop"]], BT_LOOP_INSTANCES[plan["rep"]]
     return plan
+
+
+# gomilp_debug_wave_plan: root flags in, route / cut / group ids out (include/gomilp_lp.h)
+WP_UNIT_BASIS, WP_GENERAL, WP_B_NEGATIVE, WP_VERIFY_BAD = 1, 2, 4, 8
+WP_ROUTES = ["WORKERS", "REVISED", "TABLEAU"]
+WP_CUTS = ["NONE", "ONE", "ONE_GATHERED", "PHASE_SPLIT", "HALVES"]
+WP_GROUPS = ["whole", "warm", "feasible", "phase1", "half0", "half1"]
+
+
+def debug_wave_plan(roots, children, root_of=None, warm=None, spent=(), **knobs) -> dict:
+    """Where a pool holding `roots` — (m, n, flags) or (m, n, flags, scale_span) each, flags of WP_* — sends the wave `children`
+    (constraint lists [(var, sign, rhs), ...], root_of[i] their roots) under the pool knobs `knobs`: the engine's WavePlan
+    (gomilp_amd/csrc/frontier_pool.hpp), host only (no device).  warm: None for a cold call, else per child whether it names a parent
+    whose kept tableau is resident (a solve_warm call); spent: warm starts that come back cold.  Returns route, cut (names of
+    WP_ROUTES / WP_CUTS), groups (a name of WP_GROUPS per child) and pos (the child's place in its group's list).  ValueError for a bad shape, list or key."""
+    i32p = C.POINTER(C.c_int32)
+    rm = np.array([r[0] for r in roots], dtype=np.int64)
+    rn = np.array([r[1] for r in roots], dtype=np.int64)
+    rf = np.array([r[2] for r in roots], dtype=np.int32)
+    rs = np.array([r[3] if len(r) > 3 else 1.0 for r in roots], dtype=np.float64)
+    pk = pack_children(children)
+    rof = None if root_of is None else np.ascontiguousarray(root_of, dtype=np.int32)
+    wm = None if warm is None else np.ascontiguousarray(warm, dtype=np.int32)
+    sp = np.ascontiguousarray(list(spent), dtype=np.int64)
+    keys = (C.c_char_p * max(1, len(knobs)))(*[k.encode() for k in knobs])
+    vals = (C.c_int64 * max(1, len(knobs)))(*[int(v) for v in knobs.values()])
+    route, cut = C.c_int32(-1), C.c_int32(-1)
+    group = np.full(max(pk.count, 1), -1, dtype=np.int32)
+    pos = np.full(max(pk.count, 1), -1, dtype=np.int32)
+    rc = lib().gomilp_debug_wave_plan(len(roots), _ip(rm), _ip(rn), rf.ctypes.data_as(i32p), _dp(rs), pk.count,
+                                      None if rof is None else rof.ctypes.data_as(i32p), _ip(pk.koff), pk.var.ctypes.data_as(i32p), _dp(pk.rhs),
+                                      0 if wm is None else 1, None if wm is None else wm.ctypes.data_as(i32p), sp.size, _ip(sp) if sp.size else None,
+                                      len(knobs), keys, vals, C.byref(route), C.byref(cut), group.ctypes.data_as(i32p), pos.ctypes.data_as(i32p))
+    if rc != OK:
+        raise ValueError("bad shape, list or key: %r" % (knobs,))
+    return {"route": WP_ROUTES[route.value], "cut": WP_CUTS[cut.value], "groups": [WP_GROUPS[g] for g in group[: pk.count]],
+            "pos": [int(v) for v in pos[: pk.count]]}
 
 
 def debug_cond_estimate(B, inf: bool = False) -> float:

@@ -391,6 +391,24 @@ int gomilp_debug_lu_host_solve(int64_t m, int64_t nd, const int32_t *dl, const i
 #define GOMILP_BT_PLAN_FIELDS 23
 int gomilp_debug_bt_plan(int64_t m, int64_t ldt, int64_t nknobs, const char *const *keys, const int64_t *values, int64_t ncu, int64_t *out);
 
+/* Diagnostic (host only, no device): where a pool that holds the given roots would send one frontier wave under the given pool knobs
+ * (nknobs key / value pairs of gomilp_pool_set's own keys) — the routing table of DESIGN.md section 2.5f.  A root is its m, n,
+ * scale_span and GOMILP_WP_ROOT_* flags (a root with B_NEGATIVE has some b_i < 0); the wave is count / root_of (NULL: all of root 0) /
+ * koff / var / rhs as gomilp_frontier_solve_roots takes them.  warm_call: the wave comes through gomilp_frontier_solve_warm; then warm[i]
+ * != 0 says that relaxation i names a parent whose kept tableau is resident, and spent[0 .. nspent) lists warm starts that spend their
+ * dual budget and come back into the cold part.  Out: *route (0 workers, 1 batched revised simplex, 2 tableau schedule), *cut (how the
+ * tableau schedule cuts the cold part: 0 none, 1 one run on the caller's arrays, 2 one run on gathered lists, 3 feasible starts beside
+ * Phase-I starts, 4 two halves), group[i], a GOMILP_WP_GROUP_* per relaxation, and pos[i], its place in the list of that group as the
+ * schedule gets it.  Returns GOMILP_OK, or
+ * -GOMILP_ERR_BAD_SHAPE for a bad shape, key or list. */
+enum { GOMILP_WP_ROOT_UNIT_BASIS = 1, GOMILP_WP_ROOT_GENERAL = 2, GOMILP_WP_ROOT_B_NEGATIVE = 4, GOMILP_WP_ROOT_VERIFY_BAD = 8 };
+enum { GOMILP_WP_GROUP_WHOLE = 0, GOMILP_WP_GROUP_WARM = 1, GOMILP_WP_GROUP_FEASIBLE = 2, GOMILP_WP_GROUP_PHASE1 = 3, GOMILP_WP_GROUP_HALF0 = 4,
+       GOMILP_WP_GROUP_HALF1 = 5 };
+int gomilp_debug_wave_plan(int64_t nroots, const int64_t *root_m, const int64_t *root_n, const int32_t *root_flags, const double *root_scale_span,
+                           int64_t count, const int32_t *root_of, const int64_t *koff, const int32_t *var, const double *rhs, int32_t warm_call,
+                           const int32_t *warm, int64_t nspent, const int64_t *spent, int64_t nknobs, const char *const *keys, const int64_t *values,
+                           int32_t *route, int32_t *cut, int32_t *group, int32_t *pos);
+
 /* Library / device probes (no compute): used by the loader checks and by __graft_entry__. */
 const char *gomilp_version(void);
 int gomilp_device_count(void);
