@@ -120,7 +120,11 @@ def solve_milp(c, A, b, G, h, integrality, *, max_nodes: int = 255, workers: int
     context (an lp.Context): the tree runs node by node on that one context instead of a pool — the root uploaded once, every node
     the root's child with its branch rows, freed when done; with warm, a node starts from its parent's kept state
     (gomilp_lp_solve_warm) and keeps its own while it has unsolved children.  Same node order, decisions and outputs as the pool
-    path.  The only way to run a tree on MILPs beyond 8192 rows: pools refuse them."""
+    path.
+
+    MILPs beyond 8192 rows: a default pool refuses them.  Pass pool=lp.FrontierPool(large_rows=1): its wide waves (n - m >= 2m, slack
+    bases) run device-batched on the chunked revised-simplex kernels, with warm=True and the pool knob warm_revised=1 from the parents'
+    kept bases; waves that do not fit the device memory run on the pool's workers.  Or pass a context: the tree then runs node by node."""
     c = np.asarray(c, dtype=np.float64)
     integrality = list(integrality)
     if G is not None:

@@ -8,6 +8,12 @@
 // across relaxations and no kernel waits for another workgroup: kernels communicate across launch boundaries only.
 // Every field of a RevLP that a kernel reads was written by an earlier launch of the stream (RevLP::flips / flips_k2); the one
 // exception, RevLP::x_best in k_rv_exch, only saves work.
+//
+// Every kernel that stages an m-long vector in LDS comes in two forms, as in simplex_kernels.hip: one pass (the vector staged whole: rows
+// up to the 64 KB window) and the chunked form *_ck (the vector streamed through LDS ck2 double2 at a time: kernels_common.h dot_group /
+// stage_chunk; pool knob large_rows, or wherever the pool's row_chunk forces it).  The two forms of a pair differ in their staging and
+// row loops only, so a relaxation's values do not depend on the chunk size either.  The chunked loops run to workgroup-uniform bounds
+// (the relaxation's own m, nn and ld): every thread of a workgroup reaches every barrier.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -243,6 +249,40 @@ __global__ __launch_bounds__(kBlock) void k_rv_price(RevLP *__restrict__ lps, co
     publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
 }
 
+// the chunked form of k_rv_price (k_price_ck)
+__global__ __launch_bounds__(kBlock) void k_rv_price_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[1];
+    const RevLP *d = lps + act[blockIdx.y];
+    if (d->run != RR_LOOP || d->bl) return;
+    DevState *st = d->st;
+    if (!price_gate(st)) return;
+    const int ld = d->ld, nn = d->nn;
+    const double *At = d->At, *cost = d->cost, *y = d->y;
+    double *rvec = d->rvec;
+    const int32_t *nonbasic = d->nonbasic;
+    unsigned long long *pk = d->pk_price;
+    unsigned int *pi = d->pi_price;
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    const int kmax = (nn + nwaves - 1) / nwaves;
+    unsigned long long bk = ~0ull, b2 = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        double dot[kCkRows][1];
+        dot_group<1>(At, ld, nonbasic, nn, k0, wave, nwaves, {y}, svec, ck2, lane, dot);
+#pragma unroll
+        for (int r = 0; r < kCkRows; r++) {
+            const int pos = wave + (k0 + r) * nwaves;
+            if (pos < nn) price_elem<false>(cost, rvec, pos, nonbasic[pos], dot[r][0], lane, bk, bi, b2);
+        }
+    }
+    publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
+}
+
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_price) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
@@ -275,6 +315,50 @@ __global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, co
     unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
     for (int i = wave; i < m; i += nwaves) ratio_elem<false>(xb, dvec, move, i, wave_dot_row(binv_cur + (size_t)i * ld, svec, ld2, lane), lane, bk, bi, b2);
+    publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
+}
+
+// the chunked form of k_rv_ftran (k_ftran_ck)
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_rv_ftran_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_price, int ck2) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[1];
+    RevLP *d = lps + act[blockIdx.y];
+    if (d->run != MODE) return;
+    DevState *st = d->st;
+    const int m = d->m, ld = d->ld, flips = d->flips;
+    int forced_pos, forced_var;
+    if constexpr (MODE == RR_DUAL) { forced_pos = kDualPick; forced_var = -1; }
+    else { forced_pos = MODE == RR_FORCED ? d->f_pos : (d->bl ? d->bl_pos : -1); forced_var = MODE == RR_FORCED ? d->f_var : -1; }
+    const double tol = d->tol;
+    const double *At = d->At, *binv_cur = d->binv[flips & 1], *xb = d->xb;
+    double *rvec = d->rvec, *dvec = d->dvec, *move = d->move;
+    const int32_t *nonbasic = d->nonbasic;
+    const unsigned long long *pkp = d->pk_price;
+    const unsigned int *pip = d->pi_price;
+    unsigned long long *pk = d->pk_ratio;
+    unsigned int *pi = d->pi_ratio;
+    int var;
+    if (!pick_entering<false>(st, pkp, pip, nparts_price, rvec, nonbasic, tol, 0.0, forced_pos, forced_var, sk, si, ss, var)) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) d->flips_k2 = flips;   // K3 of this pivot reads the parity K2 worked on
+    const double *col = At + (size_t)var * ld;
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    const int kmax = (m + nwaves - 1) / nwaves;
+    unsigned long long bk = ~0ull, b2 = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        double dot[kCkRows][1];
+        dot_group<1>(binv_cur, ld, nullptr, m, k0, wave, nwaves, {col}, svec, ck2, lane, dot);
+#pragma unroll
+        for (int r = 0; r < kCkRows; r++) {
+            const int i = wave + (k0 + r) * nwaves;
+            if (i < m) ratio_elem<false>(xb, dvec, move, i, dot[r][0], lane, bk, bi, b2);
+        }
+    }
     publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
 }
 
@@ -333,6 +417,60 @@ __global__ __launch_bounds__(kBlock) void k_rv_update(RevLP *__restrict__ lps, c
     for (int i = wave; i < m; i += nwaves) update_row(binv_cur, binv_next, ld, dvec, i, p, dpv, svec, 0, ld2, lane);
     if (blockIdx.x == 0) {
         commit_pivot(st, xb, y, dvec, move, basic, nonbasic, nullptr, 0, phase, m, ld, p, dpv, reinterpret_cast<const double *>(svec), no_swap, bland);
+        if (threadIdx.x == 0) {
+            d->flips = flips + 1;
+            if (bland) d->bland += 1;
+        }
+    }
+}
+
+// the chunked form of k_rv_update (k_update_ck): elementwise, its chunks are only bounds; old row p is read where it lies for the commit
+// (binv_cur is only read here)
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_rv_update_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_ratio, int ck2) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[1];
+    RevLP *d = lps + act[blockIdx.y];
+    if (d->run != MODE) return;
+    DevState *st = d->st;
+    const int m = d->m, ld = d->ld, flips = d->flips_k2, phase = d->phase;
+    int forced_p, no_swap, bland;
+    if constexpr (MODE == RR_DUAL) { forced_p = kDualPick; no_swap = 0; bland = 0; }
+    else { forced_p = MODE == RR_FORCED ? d->f_p : -1; no_swap = MODE == RR_FORCED ? d->f_noswap : 0; bland = MODE == RR_FORCED ? 0 : d->bl; }
+    const double *binv_cur = d->binv[flips & 1];
+    double *binv_next = d->binv[(flips + 1) & 1];
+    double *xb = d->xb, *y = d->y, *dvec = d->dvec, *move = d->move;
+    int32_t *basic = d->basic, *nonbasic = d->nonbasic;
+    const unsigned long long *pk = d->pk_ratio;
+    const unsigned int *pi = d->pi_ratio;
+    int p;
+    if (bland) {
+        if (!bland_leaving(st, pk, pi, nparts_ratio, move, m, sk, si, p)) return;
+    } else if (!pick_leaving<false>(st, pk, pi, nparts_ratio, move, dvec, 0.0, forced_p, sk, si, ss, p)) {
+        return;
+    }
+    const double dpv = dvec[p];
+    const int ld2 = ld >> 1;
+    const double *rowp_g = binv_cur + (size_t)p * ld;   // old row p
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    const int kmax = (m + nwaves - 1) / nwaves;
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        for (int c0 = 0; c0 < ld2; c0 += ck2) {
+            const int c1 = min(c0 + ck2, ld2);
+            stage_chunk<1>(svec, ck2, {rowp_g}, c0, c1);
+#pragma unroll
+            for (int r = 0; r < kCkRows; r++) {
+                const int i = wave + (k0 + r) * nwaves;
+                if (i < m) update_row(binv_cur, binv_next, ld, dvec, i, p, dpv, svec, c0, c1, lane);
+            }
+        }
+    }
+    if (blockIdx.x == 0) {
+        commit_pivot(st, xb, y, dvec, move, basic, nonbasic, nullptr, 0, phase, m, ld, p, dpv, rowp_g, no_swap, bland);
         if (threadIdx.x == 0) {
             d->flips = flips + 1;
             if (bland) d->bland += 1;
@@ -407,6 +545,45 @@ __global__ __launch_bounds__(kBlock) void k_rv_dual_price(RevLP *__restrict__ lp
     publish_partials(bk, bi, sk, si, pk, pi);
 }
 
+// the chunked form of k_rv_dual_price (k_dual_price_ck): y and rho streamed through LDS ck2 double2 each at a time, ck2 <= kRevDualLd / 2
+// (2 * ck2 double2 of LDS: 64 KB at most)
+__global__ __launch_bounds__(kBlock) void k_rv_dual_price_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    const RevLP *d = lps + act[blockIdx.y];
+    if (d->run != RR_DUAL) return;
+    const DevState *st = d->st;
+    if (st->done) return;
+    const int ld = d->ld, nn = d->nn;
+    const double *At = d->At, *cost = d->cost, *y = d->y;
+    double *rvec = d->rvec;
+    const int32_t *nonbasic = d->nonbasic;
+    unsigned long long *pk = d->pk_price;
+    unsigned int *pi = d->pi_price;
+    const double *rho = d->binv[d->flips & 1] + (size_t)st->p * ld;
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    const int kmax = (nn + nwaves - 1) / nwaves;
+    unsigned long long bk = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        double dot[kCkRows][2];
+        dot_group<2>(At, ld, nonbasic, nn, k0, wave, nwaves, {y, rho}, svec, ck2, lane, dot);
+#pragma unroll
+        for (int r = 0; r < kCkRows; r++) {
+            const int pos = wave + (k0 + r) * nwaves;
+            if (pos < nn) {
+                const double rr = cost[nonbasic[pos]] - dot[r][0], da = dot[r][1];
+                if (lane == 0) rvec[pos] = rr;
+                amin_take(bk, bi, ordkey(da < -1e-13 ? rr / (-da) : __builtin_inf()), (unsigned int)pos);
+            }
+        }
+    }
+    publish_partials(bk, bi, sk, si, pk, pi);
+}
+
 // ------------------------------------------------------------------------------------------------
 // set-up launches behind the forced pivot: index lists, refreshes, the check that starts the loop
 // ------------------------------------------------------------------------------------------------
@@ -458,6 +635,29 @@ __global__ __launch_bounds__(kBlock) void k_rv_matvec(RevLP *__restrict__ lps, c
     for (int i = wave; i < m; i += nwaves) {
         const double v = wave_dot_row(M + (size_t)i * ld, svec, ld2, lane);
         if (lane == 0) out[i] = v;
+    }
+}
+
+// the chunked form of k_rv_matvec (k_matvec_rows_ck)
+__global__ __launch_bounds__(kBlock) void k_rv_matvec_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    const RevLP *d = lps + act[blockIdx.y];
+    if (d->do_refresh != 1 || d->stage != RS_RUN) return;
+    const int m = d->m, ld = d->ld;
+    const double *M = d->binv[d->flips & 1], *vec = d->b;
+    double *out = d->xb;
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    const int kmax = (m + nwaves - 1) / nwaves;
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        double dot[kCkRows][1];
+        dot_group<1>(M, ld, nullptr, m, k0, wave, nwaves, {vec}, svec, ck2, lane, dot);
+#pragma unroll
+        for (int r = 0; r < kCkRows; r++) {
+            const int i = wave + (k0 + r) * nwaves;
+            if (i < m && lane == 0) out[i] = dot[r][0];
+        }
     }
 }
 
@@ -661,6 +861,62 @@ __global__ __launch_bounds__(kBlock) void k_rv_exch(RevLP *__restrict__ lps, con
     atomicMin(&d->x_best, (unsigned int)j);
 }
 
+// the chunked form of k_rv_exch: a_j streamed through LDS ck2 double2 at a time.  d_added first, as one row's chunked dot by every wave
+// (the same bits in each); a candidate that fails there costs one row.  The other rows kCkRows per wave at a time (dot_group with the
+// workgroup's own kWavesPerBlock waves: row i = w, w + 4, ... as the one-pass loop takes them).
+__global__ __launch_bounds__(kBlock) void k_rv_exch_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
+    extern __shared__ __attribute__((aligned(16))) double2 svec[];
+    __shared__ double smax[kWavesPerBlock];
+    RevLP *d = lps + act[blockIdx.y];
+    if (d->run != RR_EXCH) return;
+    const int m = d->m, n = d->n, ld = d->ld, added = d->x_added, pos = blockIdx.x;
+    if (pos >= d->nn) return;
+    const int j = d->nonbasic[pos];
+    if (j < 0 || j >= n) return;   // (row n of At is the artificial: never a candidate)
+    __shared__ unsigned int seen;
+    if (threadIdx.x == 0) seen = __atomic_load_n(&d->x_best, __ATOMIC_RELAXED);
+    __syncthreads();
+    if (seen < (unsigned int)j) return;   // (workgroup-uniform)
+    const double *binv_cur = d->binv[d->flips & 1], *xb = d->xb;
+    const double *col = d->At + (size_t)j * ld;
+    const int ld2 = ld >> 1;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    DotAcc acc[1] = {{0, 0, 0, 0}};
+    for (int c0 = 0; c0 < ld2; c0 += ck2) {
+        const int c1 = min(c0 + ck2, ld2);
+        stage_chunk<1>(svec, ck2, {col}, c0, c1);
+        wave_dot_chunk<1>(binv_cur + (size_t)added * ld, svec, ck2, c0, c1, ld2, lane, acc);
+    }
+    const double dpv = wave_dot_finish(acc[0]);   // (every wave: the same bits, workgroup-uniform)
+    if (!(fabs(dpv) > 1e-9)) return;
+    const double theta = xb[added] / dpv;
+    double dmax = 0;
+    int bad = 0;
+    const int kmax = (m + kWavesPerBlock - 1) / kWavesPerBlock;
+    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+        double dot[kCkRows][1];
+        dot_group<1>(binv_cur, ld, nullptr, m, k0, w, kWavesPerBlock, {col}, svec, ck2, lane, dot);
+#pragma unroll
+        for (int r = 0; r < kCkRows; r++) {
+            const int i = w + (k0 + r) * kWavesPerBlock;
+            if (i < m) {
+                const double di = dot[r][0];
+                const double a = fabs(di);
+                if (dmax < a) dmax = a;
+                const double v = (i == added) ? theta : xb[i] - theta * di;
+                if (v < -1e-13) bad = 1;
+            }
+        }
+    }
+    if (lane == 0) smax[w] = dmax;
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x != 0 || bad) return;
+#pragma unroll
+    for (int t = 0; t < kWavesPerBlock; t++) if (dmax < smax[t]) dmax = smax[t];
+    if (!(fabs(dpv) > 1e-9 * (1.0 < dmax ? dmax : 1.0))) return;
+    atomicMin(&d->x_best, (unsigned int)j);
+}
+
 // the scan's verdict: the forced pivot of the exchange — the worker's launch_ftran(column j) / launch_update(row added, no swap) on a
 // loop state that runs again — with j into the basis list (do_lists = 3), then the orders of the Phase-II start; no candidate passed:
 // infeasible, no x (simplex.go:606).  The exchange is a pivot of neither phase: piv1 stands as k_rv_ctrl took it.
@@ -688,17 +944,32 @@ void launch_rv_assemble(const RevLP *lps, int count, int n_max, hipStream_t s) {
 void launch_rv_init(RevLP *lps, int count, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_init, dim3(count), dim3(kBlock), 0, s, lps);
 }
-void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL(k_rv_ftran<RR_FORCED>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, 0);
-    hipLaunchKernelGGL(k_rv_update<RR_FORCED>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
+// (ck2 > 0: the chunked forms, ck2 double2 of dynamic LDS; 0: the one-pass forms with `lds` bytes)
+void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, int ck2, hipStream_t s) {
+    const size_t ldc = (size_t)ck2 * sizeof(double2);
+    if (ck2 > 0) {
+        hipLaunchKernelGGL(k_rv_ftran_ck<RR_FORCED>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, 0, ck2);
+        hipLaunchKernelGGL(k_rv_update_ck<RR_FORCED>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gr, ck2);
+    } else {
+        hipLaunchKernelGGL(k_rv_ftran<RR_FORCED>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, 0);
+        hipLaunchKernelGGL(k_rv_update<RR_FORCED>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
+    }
     hipLaunchKernelGGL(k_rv_lists, dim3(nact), dim3(kBlock), 0, s, lps, act);
-    hipLaunchKernelGGL(k_rv_matvec, dim3(gr, nact), dim3(kBlock), lds, s, lps, act);
+    if (ck2 > 0) hipLaunchKernelGGL(k_rv_matvec_ck, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, ck2);
+    else hipLaunchKernelGGL(k_rv_matvec, dim3(gr, nact), dim3(kBlock), lds, s, lps, act);
     hipLaunchKernelGGL(k_rv_y_partial, dim3((ld_max + kBlock - 1) / kBlock, 64, nact), dim3(kBlock), 0, s, lps, act);
     hipLaunchKernelGGL(k_rv_y_reduce, dim3((ld_max + kBlock - 1) / kBlock, nact), dim3(kBlock), 0, s, lps, act);
     hipLaunchKernelGGL(k_rv_check, dim3(nact), dim3(kBlock), 0, s, lps, act);
 }
-void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, hipStream_t s) {
+void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int ck2, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_bland, dim3(nact), dim3(kBlock), 0, s, lps, act);
+    if (ck2 > 0) {
+        const size_t ldc = (size_t)ck2 * sizeof(double2);
+        hipLaunchKernelGGL(k_rv_price_ck, dim3(gp, nact), dim3(kBlock), ldc, s, lps, act, ck2);
+        hipLaunchKernelGGL(k_rv_ftran_ck<RR_LOOP>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gp, ck2);
+        hipLaunchKernelGGL(k_rv_update_ck<RR_LOOP>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gr, ck2);
+        return;
+    }
     hipLaunchKernelGGL(k_rv_price, dim3(gp, nact), dim3(kBlock), lds, s, lps, act);
     hipLaunchKernelGGL(k_rv_ftran<RR_LOOP>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp);
     hipLaunchKernelGGL(k_rv_update<RR_LOOP>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
@@ -706,16 +977,25 @@ void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_
 void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_ctrl, dim3(nact), dim3(kBlock), 0, s, lps, act, out);
 }
-void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL(k_rv_exch, dim3(nn_max, nact), dim3(kBlock), lds, s, lps, act);
+void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, int ck2, hipStream_t s) {
+    if (ck2 > 0) hipLaunchKernelGGL(k_rv_exch_ck, dim3(nn_max, nact), dim3(kBlock), (size_t)ck2 * sizeof(double2), s, lps, act, ck2);
+    else hipLaunchKernelGGL(k_rv_exch, dim3(nn_max, nact), dim3(kBlock), lds, s, lps, act);
     hipLaunchKernelGGL(k_rv_exch_pick, dim3(nact), dim3(64), 0, s, lps, act);
 }
 void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_warm_binv, dim3(m_max, count), dim3(kBlock), 0, s, lps);
 }
-void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, hipStream_t s) {
+// (ck2d > 0: the chunked pricing kernel, its TWO vectors ck2d double2 each; ck2: K2 / K3 as in launch_rv_pivot)
+void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, int ck2, int ck2d, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_dual_leave, dim3(nact), dim3(kBlock), 0, s, lps, act);
-    hipLaunchKernelGGL(k_rv_dual_price, dim3(gp, nact), dim3(kBlock), lds2, s, lps, act);
+    if (ck2d > 0) hipLaunchKernelGGL(k_rv_dual_price_ck, dim3(gp, nact), dim3(kBlock), (size_t)2 * ck2d * sizeof(double2), s, lps, act, ck2d);
+    else hipLaunchKernelGGL(k_rv_dual_price, dim3(gp, nact), dim3(kBlock), lds2, s, lps, act);
+    if (ck2 > 0) {
+        const size_t ldc = (size_t)ck2 * sizeof(double2);
+        hipLaunchKernelGGL(k_rv_ftran_ck<RR_DUAL>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gp, ck2);
+        hipLaunchKernelGGL(k_rv_update_ck<RR_DUAL>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gr, ck2);
+        return;
+    }
     hipLaunchKernelGGL(k_rv_ftran<RR_DUAL>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp);
     hipLaunchKernelGGL(k_rv_update<RR_DUAL>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
 }

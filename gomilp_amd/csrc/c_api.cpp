@@ -96,7 +96,7 @@ gomilp_pool *gomilp_pool_create(int device, int workers, int *status) {
         // 8 CUs of one XCD with nearly all of their LDS; side by side they would hold each other off until the bounded polls give up)
         p->eng.back()->set("lu_large", 0);
         // pools (frontier waves, batched schedules, warm starts) keep the row limit of one-pass LDS staging: roots and children
-        // beyond 8192 rows are refused as GOMILP_ERR_UNSUPPORTED
+        // beyond 8192 rows are refused as GOMILP_ERR_UNSUPPORTED — until the pool knob large_rows lifts it (gomilp_pool_set)
         p->eng.back()->limit_rows_to_lds_window();
     }
     p->batch.reset(new BatchEngine(device));
@@ -111,6 +111,15 @@ int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value) {
     std::lock_guard<std::mutex> g(pool->call_mu);
     using Scope = gomilp::PoolKnobs::Scope;
     const Scope sc = gomilp::PoolKnobs::scope(key);
+    if (std::string(key) == "large_rows") {
+        // the workers take what a context takes beyond the LDS window, or keep the window; a pool that holds a root beyond it keeps the knob
+        if (!value) {
+            bool beyond = pool->root[0] >= 0 && pool->view.ld > gomilp::kLdsWindowLd;
+            for (auto &v : pool->extra_view) beyond = beyond || v->ld > gomilp::kLdsWindowLd;
+            if (beyond) return GOMILP_ERR_BAD_SHAPE;
+        }
+        for (auto &e : pool->eng) e->limit_rows_to_lds_window(value == 0);
+    }
     if (sc == Scope::Pool || sc == Scope::PoolAndWorkers) {
         pool->knobs.set(key, value);
         pool->apply_knobs(*pool->batch);
@@ -139,6 +148,11 @@ int gomilp_pool_set_root(gomilp_pool *pool, const double *c0, const double *A0, 
     }
     pool->m0 = m0; pool->n0 = n0;
     if (!pool->eng[0]->root_view(pool->root[0], &pool->view)) return GOMILP_ERR_DEVICE;
+    // (knob large_rows) beyond the LDS window only slack-basis roots, as on a context: the general start's search stages m-long rows
+    if (pool->view.ld > gomilp::kLdsWindowLd && !pool->view.unit_basis && pool->view.verify_status == GOMILP_OK) {
+        for (size_t w = 0; w < pool->eng.size(); w++) { pool->eng[w]->free_problem(pool->root[w]); pool->root[w] = -1; }
+        return GOMILP_ERR_UNSUPPORTED;
+    }
     if (!pool->view.unit_basis && pool->view.verify_status == GOMILP_OK) pool->eng[0]->root_general(pool->root[0], &pool->view);   // equality rows: one column search per root
     // first-touch allocations of every worker (work buffers, child slot, final-solve workspace) happen here, not inside the
     // first waves: each worker finishes one dummy child (8 slack rows x_0 <= 1e30) from its slack basis
@@ -213,6 +227,10 @@ int gomilp_pool_add_root(gomilp_pool *pool, const double *c, const double *A, in
     if (id < 0) return (int)id;
     std::unique_ptr<Engine::RootView> v(new Engine::RootView);
     if (!pool->eng[0]->root_view(id, v.get())) return -GOMILP_ERR_DEVICE;
+    if (v->ld > gomilp::kLdsWindowLd && !v->unit_basis && v->verify_status == GOMILP_OK) {
+        pool->eng[0]->free_problem(id);
+        return -GOMILP_ERR_UNSUPPORTED;
+    }
     if (!v->unit_basis && v->verify_status == GOMILP_OK) pool->eng[0]->root_general(id, v.get());
     pool->extra_root.push_back(id);
     pool->extra_view.push_back(std::move(v));

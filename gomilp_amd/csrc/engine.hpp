@@ -200,7 +200,8 @@ class Engine {
     int debug_find_independent(int64_t id, std::vector<int32_t> &idxs);
 
     // pools, batched waves and warm starts keep the row limit of one-pass LDS staging (ld <= kLdsWindowLd)
-    void limit_rows_to_lds_window() { lds_window_only_ = true; }
+    // (a pool lifts it with its knob large_rows: the workers then take what a context takes)
+    void limit_rows_to_lds_window(bool on = true) { std::lock_guard<std::mutex> g(mu_); lds_window_only_ = on; }
 
    private:
     struct Work;  // device work buffers, sized for the largest problem seen

@@ -60,14 +60,15 @@ void RevBatchEngine::release() {
     b_->free_all();
 }
 
-bool RevBatchEngine::eligible(const Engine::RootView &R, int K_min, int K_max, int exact_degenerate, int cond_guard) {
+bool RevBatchEngine::eligible(const Engine::RootView &R, int K_min, int K_max, int exact_degenerate, int cond_guard, int large_rows) {
     if (R.verify_status != GOMILP_OK || !R.unit_basis) return false;
     const int m_lo = R.m + K_min, m_hi = R.m + K_max, n_hi = R.n + K_max;
     if (m_hi >= n_hi || (R.n - R.m) < 2 * m_hi) return false;   // the revised formulation (engine.cpp: use_tab's n - m < 2m rule)
     // the exact-step guard is off for every shape (exact_wanted): the blocked tableau with exact steps stays on the workers
     if (!(exact_degenerate == 0 || (exact_degenerate == 1 && m_lo > 256 && !(R.scale_span > 1e9)))) return false;
     if (cond_guard && m_lo <= 64) return false;                  // the replay of gonum's condition guards runs in Engine::solve only
-    if (((m_hi + 1) & ~1) > kLdsWindowLd) return false;          // pools keep the row limit of one-pass LDS staging
+    // pools keep the row limit of one-pass LDS staging unless the knob large_rows lifts it (the chunked kernels of batch_revised.hip)
+    if (!large_rows && ((m_hi + 1) & ~1) > kLdsWindowLd) return false;
     return true;
 }
 
@@ -102,7 +103,8 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
     std::vector<Plan> plan((size_t)count);
     size_t wj_tot = 0;
     int64_t nwarm = 0;
-    if (warm && warm->store && warm->start_warm && warm->parent && ld_max <= kRevDualLd) {
+    // (the one-pass dual pricing stages two vectors whole: without large_rows, waves beyond kRevDualLd run cold, with keeping)
+    if (warm && warm->store && warm->start_warm && warm->parent && (ld_max <= kRevDualLd || large_rows_)) {
         for (int64_t i = 0; i < count; i++) {
             const int K = (int)(koff[i + 1] - koff[i]);
             if (warm->parent[i] < 0 || K < 1) continue;
@@ -278,7 +280,14 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
     // depend on the grid it gets)
     const int gp = grid_for_rows(nn1_max + K_max), gr = grid_for_rows(m_max);
     const int nn_max = nn1_max;
-    const size_t lds = (size_t)ld_max * sizeof(double);
+    // the chunk of the staged vectors, in double2 (0: the one-pass kernels, exactly the launches of a pool without large_rows): the pool's
+    // row_chunk where large_rows is on and it is set, else kAutoRowChunk beyond the LDS window; the dual pricing kernel stages two
+    // vectors, so it goes chunked beyond kRevDualLd, or wherever the primal chunk is forced, with at most kRevDualLd / 2 per vector
+    int ck2 = 0;
+    if (large_rows_ && row_chunk_ > 0) ck2 = (int)(row_chunk_ / 2);
+    else if (ld_max > kLdsWindowLd) ck2 = kAutoRowChunk / 2;
+    const int ck2d = ck2 > 0 ? std::min(ck2, kRevDualLd / 2) : (ld_max > kRevDualLd ? kRevDualLd / 2 : 0);
+    const size_t lds = ck2 > 0 ? 0 : (size_t)ld_max * sizeof(double);
     std::vector<int> act((size_t)count), done_now;
     std::vector<char> is_warm((size_t)count, 0), in_dual((size_t)count, 0);   // started warm (and still is) / the dual loop runs or is ordered
     std::vector<char> in_scan((size_t)count, 0);                              // the candidate scan of the artificial exchange is ordered
@@ -296,12 +305,12 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
         bool any_dual = false, any_primal = false, any_scan = false;
         for (int id : act) { (in_dual[(size_t)id] ? any_dual : any_primal) = true; if (in_scan[(size_t)id]) any_scan = true; }
         // (the scan's verdict orders the forced pivot that the set-up launches behind it run: an exchange costs no superstep of its own)
-        if (any_scan) { launch_rv_exchange(b.d_lps, b.d_act, nact, nn_max, lds, stream_); launches += 2; }
-        launch_rv_setup(b.d_lps, b.d_act, nact, gr, ld_max, lds, stream_);
+        if (any_scan) { launch_rv_exchange(b.d_lps, b.d_act, nact, nn_max, lds, ck2, stream_); launches += 2; }
+        launch_rv_setup(b.d_lps, b.d_act, nact, gr, ld_max, lds, ck2, stream_);
         const int chunk = steps < 2 ? kFirstChunk : kChunk;
         for (int t = 0; t < chunk; t++) {
-            if (any_dual) launch_rv_dual_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, 2 * lds, stream_);
-            if (any_primal) launch_rv_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, stream_);
+            if (any_dual) launch_rv_dual_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, 2 * lds, ck2, ck2d, stream_);
+            if (any_primal) launch_rv_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, ck2, stream_);
         }
         launch_rv_ctrl(b.d_lps, b.d_act, nact, b.d_out, stream_);
         launches += 7 + 4 * chunk * ((any_dual ? 1 : 0) + (any_primal ? 1 : 0)) + 1;

@@ -21,7 +21,8 @@ class RevBatchEngine {
     ~RevBatchEngine();
     // do children of this root with K_min..K_max branch rows run on the revised pipelines, unguarded, on a worker with these knobs?
     // (the predicate of Engine::solve_locked: use_tab / exact_wanted / shadow_trace_)
-    static bool eligible(const Engine::RootView &R, int K_min, int K_max, int exact_degenerate, int cond_guard);
+    // large_rows (the pool knob): the row limit of one-pass LDS staging (ld <= kLdsWindowLd) is dropped, every other condition stays
+    static bool eligible(const Engine::RootView &R, int K_min, int K_max, int exact_degenerate, int cond_guard, int large_rows = 0);
     // The wave (relaxation i is a child of roots[root_of[i]] — root_of null: of roots[0] — with rows koff[i]..koff[i+1] of var / sign /
     // rhs; every root the wave uses must pass `eligible` with its own children's K range).  One schedule for the whole wave: each
     // relaxation carries its own root's shape and data, the grids and staged vectors are sized for the wave's largest relaxation, and a
@@ -32,8 +33,9 @@ class RevBatchEngine {
     // parent[i] names when its branch rows extend that state's rows (a bitwise prefix) by J >= 1 — B^-1 = [[B_p^-1, 0], [R, I_J]], the
     // dual loop, then Phase II — and cold otherwise, in the same run; a relaxation with keep[i] that ends BS_DONE with GOMILP_OK leaves
     // its B^-1 and basis list in the store under tag[i].  A warm start that spends its dual budget is reported once with stage BS_COLD
-    // (warm = 1, pivd), re-initialised in place and solved cold by the same run: its second report has warm = 0.  Waves with
-    // ld_max > kRevDualLd run cold, with keeping.  A kept state serves children of the root it was kept under only (root_serial).
+    // (warm = 1, pivd), re-initialised in place and solved cold by the same run: its second report has warm = 0.  Without large_rows,
+    // waves with ld_max > kRevDualLd run cold, with keeping; with it they start warm and price through the chunked dual kernel.
+    // A kept state serves children of the root it was kept under only (root_serial).
     int run(const Engine::RootView *const *roots, int nroots, const int32_t *root_of, int64_t count, const int64_t *koff, const int32_t *var,
             const double *sign, const double *rhs, double tol, int64_t max_pivots, const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits,
             const WarmSpec *warm = nullptr);
@@ -44,6 +46,11 @@ class RevBatchEngine {
     // (1e-13 < |x_art| < 1e-11) is BS_HOST either way: its verdict needs a fresh gonum-order solve.
     void set_exchange(bool on) { exchange_ = on; }
 
+    // pool knobs large_rows / row_chunk: with large_rows the kernels that stage an m-long vector run in their chunked forms (*_ck of
+    // batch_revised.hip) — row_chunk doubles at a time where the pool set it (any row count), else kAutoRowChunk beyond the LDS window —
+    // and warm starts are not limited to kRevDualLd.  Bit-identical to the one-pass forms.  Off (default): row_chunk is not looked at.
+    void set_large_rows(bool on, int64_t row_chunk) { large_rows_ = on; row_chunk_ = row_chunk; }
+
     // gives the wave buffers back (they grow with the largest wave seen: 5 MB per 300 x 1500 relaxation); the pool calls it when the
     // root changes
     void release();
@@ -52,6 +59,8 @@ class RevBatchEngine {
     struct Buf;
     int device_;
     bool exchange_ = true;
+    bool large_rows_ = false;
+    int64_t row_chunk_ = 0;
     hipStream_t stream_ = nullptr;
     Buf *b_;
 };

@@ -20,13 +20,13 @@ namespace gomilp {
 PoolKnobs::Scope PoolKnobs::scope(const char *key) {
     const std::string k(key);
     for (const char *p : {"batched", "batch_revised", "warm_revised", "rev_exchange", "rev_roots", "split_large", "split_phase", "large_loop",
-                          "batch_virt", "batch_res", "batch_loop", "sample_batch", "lu_large"})
+                          "batch_virt", "batch_res", "batch_loop", "sample_batch", "lu_large", "large_rows"})
         if (k == p) return Scope::Pool;
 #ifdef GOMILP_DEBUG
     if (k == "bt_fault") return Scope::PoolAndWorkers;
 #endif
     if (k == "cond_guard" || k == "exact_degenerate") return Scope::PoolAndWorkers;
-    if (k == "refresh" || k == "max_pivots") return Scope::WorkersFirst;
+    if (k == "refresh" || k == "max_pivots" || k == "row_chunk") return Scope::WorkersFirst;
     return Scope::Workers;
 }
 
@@ -35,7 +35,8 @@ bool PoolKnobs::set(const char *key, int64_t value) {
     struct { const char *name; int *at; } flags[] = {
         {"batched", &batched}, {"batch_revised", &batch_revised}, {"warm_revised", &warm_revised}, {"rev_exchange", &rev_exchange},
         {"rev_roots", &rev_roots}, {"split_large", &split_large}, {"split_phase", &split_phase}, {"large_loop", &large_loop},
-        {"batch_virt", &batch_virt}, {"batch_res", &batch_res}, {"batch_loop", &batch_loop}, {"sample_batch", &sample_batch}};
+        {"batch_virt", &batch_virt}, {"batch_res", &batch_res}, {"batch_loop", &batch_loop}, {"sample_batch", &sample_batch},
+        {"large_rows", &large_rows}};
     for (auto &f : flags) if (k == f.name) { *f.at = value ? 1 : 0; return true; }
     if (k == "lu_large") return true;
     if (k == "cond_guard") { cond_guard = (int)value; return true; }
@@ -45,6 +46,11 @@ bool PoolKnobs::set(const char *key, int64_t value) {
 #endif
     if (k == "refresh") { refresh = value; return true; }
     if (k == "max_pivots") { max_pivots = value < 0 ? 0 : value; return true; }
+    if (k == "row_chunk") {   // (the value checks of gomilp_ctx_set)
+        if (value < 0 || value % 512 != 0 || value > kLdsWindowLd) return false;
+        row_chunk = value;
+        return true;
+    }
     return false;
 }
 
@@ -90,6 +96,7 @@ WavePlan WavePlan::make(const Engine::RootView *const *views, int nroots, const 
     // ---- Wide waves: the device-batched revised simplex, where every relaxation of the wave is one that a worker's Engine::solve runs on the
     // revised pipelines without the exact-step guard (slack starts; a periodic refresh stays on the workers).  Cold calls, and with the
     // knob warm_revised the warm call: relaxations whose parent's kept state is of this schedule start from it (section 2.6b).
+    // Rows beyond the LDS window (ld > 8192) only with the knob large_rows: the chunked kernels of batch_revised.hip.
     // The test runs over the roots the WAVE uses, each with the K range of its own children; roots the pool merely holds do not count.
     // One used root that fails (narrow, no slack basis, a guarded size, a verify verdict) sends the wave where it went before, whole.
     if (!knobs.batch_revised || (warm_call && !knobs.warm_revised) || knobs.refresh != 0) return p;
@@ -102,7 +109,7 @@ WavePlan WavePlan::make(const Engine::RootView *const *views, int nroots, const 
     }
     bool use_rev = knobs.rev_roots || !other_root;
     for (int r = 0; r < nroots && use_rev; r++)
-        if (k_hi[(size_t)r] >= 0) use_rev = RevBatchEngine::eligible(*views[r], k_lo[(size_t)r], k_hi[(size_t)r], knobs.exact_degenerate, knobs.cond_guard);
+        if (k_hi[(size_t)r] >= 0) use_rev = RevBatchEngine::eligible(*views[r], k_lo[(size_t)r], k_hi[(size_t)r], knobs.exact_degenerate, knobs.cond_guard, knobs.large_rows);
     // (a branch row on one of its root's slack columns: the child has no slack basis)
     for (int64_t i = 0; i < count && use_rev; i++) {
         const Engine::RootView &V = *views[w.root(i)];
@@ -333,6 +340,7 @@ struct Wave {
         if (!pool->rev) pool->rev.reset(new RevBatchEngine(pool->device));
         RevBatchEngine::Stats rs;
         pool->rev->set_exchange(pool->knobs.rev_exchange != 0);
+        pool->rev->set_large_rows(pool->knobs.large_rows != 0, pool->knobs.row_chunk);
         gomilp::WarmSpec wspec;
         if (wa) {
             wspec.store = &pool->warm; wspec.parent = wa->parent; wspec.tag = wa->tag; wspec.keep = wa->keep; wspec.dual_budget = wa->budget;

@@ -40,11 +40,18 @@ struct PoolKnobs {
                                                 // (WavePlan reads cond_guard here, BatchEngine::run_roots its own copy: the defaults are equal and
                                                 // gomilp_pool::apply_knobs is the only writer of the copy — keep the two in step)
     int64_t refresh = 0;        // the workers' knob of this name: a periodic refresh stays on the workers
+    int large_rows = 0;         // (opt-in) roots and children beyond the 64 KB LDS window (ld > 8192): the workers accept what a context accepts
+                                // there (slack-basis roots that fit the device memory), and wide waves of such relaxations run on the batched
+                                // revised simplex in its chunked kernels (batch_revised.hip: *_ck); warm starts of that schedule are no longer
+                                // limited to 4096 rows.  0: pools keep the row limit of one-pass LDS staging
     // ---- kept and handed on (BatchEngine: gomilp_pool::apply_knobs; RevBatchEngine: per run)
     int rev_exchange = 1;       // on the batched revised simplex a relaxation whose Phase I ends with the artificial basic at level zero
                                 // exchanges it on the device (batch_revised.hip: k_rv_exch) instead of going to a worker's whole solve — the same
                                 // column, bit-identical results; 0: the hand-over (host_fallbacks)
     int64_t max_pivots = 0;     // the workers' knob of this name, as the batched revised simplex needs it (negative: 0)
+    int64_t row_chunk = 0;      // the workers' knob of this name (doubles per LDS chunk, a multiple of 512 up to 8192; 0: automatic): with
+                                // large_rows = 1 the batched revised simplex stages in chunks of it too, at any row count; with large_rows = 0 that
+                                // schedule never looks at it
     int batch_virt = 1;         // wide waves on virtual tableaus for their first block
     int batch_res = 0;          // block steps of narrow waves in the register-resident kernel (opt-in: k_b_loop / launch pairs otherwise)
     int batch_loop = 1;         // block steps of narrow waves in the persistent loop kernel

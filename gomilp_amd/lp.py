@@ -361,7 +361,7 @@ class FrontierPool:
         waves runs on the batched revised simplex with warm starts; default 0), "rev_exchange" (1: that schedule exchanges a zero-level
         artificial on the device, stats art_exchanges; 0: the relaxation goes to a worker, host_fallbacks), "rev_roots" (1, default: a
         wide wave of several roots — solve(children, roots=...) — runs on the batched revised simplex as one schedule; 0: on the workers),
-        the other pool knobs of include/gomilp_lp.h, or any Context knob."""
+        "large_rows" (1: roots and children beyond 8192 rows, wide waves on that schedule's chunked kernels; default 0: refused), the other pool knobs of include/gomilp_lp.h, or any Context knob."""
         rc = lib().gomilp_pool_set(self._h, key.encode(), int(value))
         if rc != OK:
             raise ValueError("bad knob %s=%s" % (key, value))

@@ -155,8 +155,11 @@ int gomilp_ctx_device(const gomilp_ctx *ctx);
  * semantics of the same pipelines at 8192 rows.  A shape whose buffers (A^T, the two B^-1 copies, the final solve's matrices, the
  * tableau) do not fit the free device memory returns GOMILP_ERR_UNSUPPORTED before anything is allocated; the context stays usable.
  * Warm starts on a context (gomilp_lp_solve_warm) work there too: the dual loop runs on the same chunked revised-simplex kernels.
- * Still GOMILP_ERR_UNSUPPORTED beyond 8192 rows: non-slack starts (equality rows, a supplied initial_basic, m >= n), frontier pools
- * (gomilp_pool_set_root, their waves and their warm starts), and exact_degenerate = 3 (the blocked tableau does not run there).  The final
+ * Frontier pools take such roots with the pool knob "large_rows" = 1 (gomilp_pool_set: wide waves on the batched revised simplex in its
+ * chunked kernels, warm starts included; everything else on the workers).
+ * Still GOMILP_ERR_UNSUPPORTED beyond 8192 rows: non-slack starts (equality rows, a supplied initial_basic, m >= n), on a context and in
+ * a pool alike; frontier pools with "large_rows" = 0, the default (gomilp_pool_set_root, their waves and their warm starts); and
+ * exact_degenerate = 3 (the blocked tableau does not run there).  The final
  * solve of the bases beyond 4096 rows takes the one-launch-per-column LU (k_lu_step): seconds, not milliseconds — unless "lu_large" is
  * set, which gives the bases of 4097 .. 16384 rows the compressed rounds (beyond 16384 rows the knob changes nothing). */
 int gomilp_ctx_set(gomilp_ctx *ctx, const char *key, int64_t value);
@@ -277,7 +280,17 @@ void gomilp_pool_destroy(gomilp_pool *pool);
  * with 1e-13 < |x_art| < 1e-11: that verdict needs a fresh gonum-order solve), "warm_revised" (default 0, opt-in: a gomilp_frontier_solve_warm call whose wave passes the routing
  * test of "batch_revised" runs on that schedule too — relaxations whose parent was kept by it start from the parent's B^-1 with a batched
  * dual simplex, the others cold in the same run, final states are kept as B^-1 + basis list; 0: such a call runs on the workers, cold, and
- * keeps nothing.  Cold calls never look at it.  DESIGN.md section 2.6b); any gomilp_ctx_set key is forwarded to the worker contexts. */
+ * keeps nothing.  Cold calls never look at it.  DESIGN.md section 2.6b), "large_rows" (default 0, opt-in: the pool takes roots and
+ * children beyond 8192 rows.  The workers accept there what a context accepts — slack-basis roots that fit the device memory; a root
+ * without a slack basis stays GOMILP_ERR_UNSUPPORTED — and a wide wave of such relaxations passes the routing test of "batch_revised": that
+ * schedule's kernels then stream their m-long vectors through LDS in chunks of 4096 doubles, bit-identical to the worker path, and its warm
+ * starts ("warm_revised") are no longer limited to 4096 rows.  A relaxation there costs its own A^T and two copies of B^-1 (8200 x 24648:
+ * 1.6 GB + 2 x 0.54 GB); a wave whose buffers do not fit the free device memory runs on the workers, whole — correct, one relaxation per
+ * stream on the chunked three-kernel loop — and a final state that does not fit is not kept (warm_kept), which is no error.  With the
+ * knob at 1 the pool also stages in chunks of the worker knob "row_chunk" where that is set, at any row count (tests).  0: pools keep the
+ * 8192-row limit and never look at "row_chunk"; clearing the knob while the pool holds a root beyond 8192 rows returns
+ * GOMILP_ERR_BAD_SHAPE.  DESIGN.md section 2.5e); any gomilp_ctx_set key is forwarded to the worker contexts ("row_chunk" is remembered
+ * by the pool as well). */
 int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value);
 /* Upload the root standard form (row-major A0, stride lda) to every worker context of the pool. */
 int gomilp_pool_set_root(gomilp_pool *pool, const double *c0, const double *A0, int64_t lda, const double *b0, int64_t m0,
@@ -338,7 +351,8 @@ int gomilp_pool_solve_root(gomilp_pool *pool, double tol, double *opt_f, double 
  * whose parent was kept here: neither is an error.  A warm start that spends dual_budget is re-initialised in place and solved cold by
  * the same call, bit for bit what the cold call returns (warm_fallbacks).  Relaxations handed to a worker (host_fallbacks: the |x_art| band; with "rev_exchange" = 0 the zero-level artificial
  * exchange too) keep nothing, one that exchanged its artificial on the device is kept like any other; waves with more
- * than 4096 rows run on this schedule cold, with keeping.  With the knob at 0 (default) a wide warm call runs on the workers, cold,
+ * than 4096 rows run on this schedule cold, with keeping, unless the pool knob "large_rows" is 1: then they start warm like any other wave
+ * (the dual pricing kernel streams its two vectors through LDS in chunks), beyond 8192 rows too.  With the knob at 0 (default) a wide warm call runs on the workers, cold,
  * warm_started = 0.  Same parity contract. */
 int gomilp_frontier_solve_warm(gomilp_pool *pool, int64_t count, const int64_t *koff, const int32_t *var, const double *sign,
                                const double *rhs, const int64_t *parent, const int64_t *tag, const int32_t *keep, int32_t dual_budget,
