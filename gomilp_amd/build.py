@@ -21,7 +21,7 @@ OBJ = os.path.join(HERE, "build_debug" if DEBUG else "build")
 LIB = os.path.join(HERE, "libgomilp_hip_debug.so" if DEBUG else "libgomilp_hip.so")
 SOURCES = ["simplex_kernels.hip", "fused_kernels.hip", "lu_kernels.hip", "lu_compressed.hip", "lu_cross.hip", "tableau_kernels.hip", "bt_kernels.hip", "btg_kernels.hip", "btr_kernels.hip",
            "batch_kernels.hip", "batch_revised.hip", "res_kernels.hip", "dual_kernels.hip", "general_kernels.hip", "general_block.hip", "engine.cpp", "engine_final.cpp", "lu_host.cpp", "engine_batch.cpp", "engine_batch_revised.cpp", "engine_tableau.cpp", "engine_general.cpp", "engine_warm.cpp", "gonum_cond.cpp", "frontier_pool.cpp", "c_api.cpp", "comm.cpp"]
-HEADERS = ["device_types.h", "kernels_common.h", "bt_loop.h", "luc_role.h", "batch_dev.h", "simplex_helpers.h", "batch_revised.h", "engine.hpp", "engine_work.hpp", "lu_host.h", "engine_batch.hpp", "engine_batch_revised.hpp", "frontier_pool.hpp", os.path.join(ROOT, "include", "gomilp_lp.h")]
+HEADERS = ["device_types.h", "kernels_common.h", "bt_loop.h", "luc_role.h", "batch_dev.h", "simplex_helpers.h", "batch_revised.h", "rev_child_col.h", "engine.hpp", "engine_work.hpp", "lu_host.h", "engine_batch.hpp", "engine_batch_revised.hpp", "frontier_pool.hpp", os.path.join(ROOT, "include", "gomilp_lp.h")]
 # -ffp-contract=off: the final basis solve must round every multiply and add separately, like the
 # reference's SSE2 kernels (DESIGN.md "bit-exact final solve"); the streaming kernels are HBM-bound
 # and do not miss the FMAs.

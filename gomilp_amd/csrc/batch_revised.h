@@ -33,7 +33,8 @@ enum : int32_t { RR_NONE = 0, RR_LOOP = 1, RR_FORCED = 2, RR_DUAL = 3, RR_EXCH =
 
 struct RevLP {
     // ---- fixed for the wave (written by the host) ----
-    double *At;              // (n + 1) x ld: row j = column j of the child's A (k_rv_assemble), row n = the Phase-I artificial
+    double *At;              // (n + 1) x ld: row j = column j of the child's A (k_rv_assemble), row n = the Phase-I artificial; null where the
+                             // wave reads its roots in place (`inplace` at the tail)
     const double *c2;        // Phase-II cost [c0, 0, ...] (at least n + 1 entries)
     double *c1;              // Phase-I cost: e_n (n + 1 entries, written by k_rv_init)
     double *b;               // ld, zero padded
@@ -87,6 +88,11 @@ struct RevLP {
     const double *asign;
     const int32_t *avar;
     int32_t ld0, pad3;
+    // ---- the root in place (pool knob rev_inplace; written by the host, at the tail, for the same reason): inplace != 0: At is null, the
+    // kernels read column j of the child through ChildCol (rev_child_col.h) from At0 / asign / avar, and the Phase-I artificial column
+    // is the relaxation's own row `art` (ld doubles of the zeroed work arena, written by k_rv_init<true>)
+    int32_t inplace, pad4;
+    double *art;
 };
 
 // what the host reads of every active relaxation after a superstep
@@ -102,22 +108,25 @@ struct RevOut {
 // the whole wave's At in one launch, in front of launch_rv_init: grid (n_max + 1 child columns, count relaxations); writes what
 // k_child_assemble (simplex_kernels.hip) writes per child
 void launch_rv_assemble(const RevLP *lps, int count, int n_max, hipStream_t s);
-void launch_rv_init(RevLP *lps, int count, hipStream_t s);
+// inplace (launch_rv_init / _setup / _pivot / _exchange / _dual_pivot): 0: today's kernels on the assembled At, launch for launch; 1: the wave
+// was not assembled (pool knob rev_inplace) — the IP = true instantiations of the kernels that read a child's column, which take it from the
+// relaxation's root through ChildCol; the other kernels of a list are the same either way
+void launch_rv_init(RevLP *lps, int count, int inplace, hipStream_t s);
 // ck2 (launch_rv_setup / _pivot / _exchange / _dual_pivot): 0: the one-pass kernels with `lds` bytes, exactly the launches of a wave within
 // the LDS window; > 0: the chunked forms (*_ck), the staged vector streamed through LDS ck2 double2 at a time (a multiple of 256, at most
 // 4096: ck2 * sizeof(double2) bytes of dynamic LDS, never more than 64 KB) — the same values, whatever the chunk
-void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, int ck2, hipStream_t s);   // forced pivot, lists, refresh, check: 7 launches
-void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int ck2, hipStream_t s);       // Bland step?, K1, K2, K3: 4 launches
+void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, int ck2, int inplace, hipStream_t s);   // forced pivot, lists, refresh, check: 7 launches
+void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int ck2, int inplace, hipStream_t s);       // Bland step?, K1, K2, K3: 4 launches
 void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s);
 // the candidate scan of the relaxations with run == RR_EXCH, in front of launch_rv_setup: one workgroup per nonbasic position (nn_max: the
 // wave's largest n + 1 - m), then the verdict and the orders of the forced pivot (2 launches)
-void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, int ck2, hipStream_t s);
+void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, int ck2, int inplace, hipStream_t s);
 // warm starts: B^-1, basis list, b and the orders of every relaxation with warm != 0 (one launch for the wave, grid rows x count);
 // a dual pivot of the relaxations in the dual loop: leaving row, dual pricing, K2 / K3 in their kDualPick form (4 launches;
 // lds2: bytes of the TWO staged vectors of the one-pass pricing kernel, ld_max <= kRevDualLd; ck2d > 0: the chunked pricing kernel
 // instead, each of its two vectors ck2d <= kRevDualLd / 2 double2 at a time — 64 KB of LDS at most)
 constexpr int kRevDualLd = 4096;
 void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s);
-void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, int ck2, int ck2d, hipStream_t s);
+void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, int ck2, int ck2d, int inplace, hipStream_t s);
 
 }  // namespace gomilp

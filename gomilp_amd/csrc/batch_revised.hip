@@ -14,6 +14,10 @@
 // stage_chunk; pool knob large_rows, or wherever the pool's row_chunk forces it).  The two forms of a pair differ in their staging and
 // row loops only, so a relaxation's values do not depend on the chunk size either.  The chunked loops run to workgroup-uniform bounds
 // (the relaxation's own m, nn and ld): every thread of a workgroup reaches every barrier.
+//
+// Every kernel that reads a child's column is a template on IP (pool knob rev_inplace): IP = false reads the At that k_rv_assemble wrote,
+// IP = true reads the column from the relaxation's root in place through ChildCol and the loader-templated helpers of rev_child_col.h —
+// the same arithmetic on synthesised values, so a relaxation's values do not depend on the mode either.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -21,6 +25,7 @@
 #include "device_types.h"
 #include "gomilp_lp.h"
 #include "kernels_common.h"
+#include "rev_child_col.h"
 #include "simplex_helpers.h"
 
 namespace gomilp {
@@ -90,7 +95,10 @@ __global__ __launch_bounds__(kBlock) void k_rv_assemble(const RevLP *__restrict_
 // permutation, and either the orders of the Phase-II start or the Phase-I set-up (simplex.go:529-546): the artificial column
 // a_{n+1} = b - sum_{i != minidx} e_{rho_i} (one exact "- 1" per row) into row n of At and the forced no-swap pivot that brings it
 // into position minidx.  (The buffers arrive zeroed.)  One workgroup per relaxation.
+// IP (here and below): the form of a wave that reads its roots in place (pool knob rev_inplace, rev_child_col.h) — the artificial column
+// goes into the relaxation's own row RevLP::art, a child's column comes through ChildCol; IP = false is the kernel on the assembled At.
 // ------------------------------------------------------------------------------------------------
+template <bool IP>
 __global__ __launch_bounds__(kBlock) void k_rv_init(RevLP *lps) {
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
@@ -125,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_init(RevLP *lps) {
     block_argmin(bk, bi, sk, si);
     const int minidx = (int)bi;   // floats.MinIdx(xb), simplex.go:531
     const int rmin = child_rho(minidx, K, m0, rho0);
-    double *art = d->At + (size_t)n * ld;
+    double *art = IP ? d->art : d->At + (size_t)n * ld;
     int nonzero = 0;
     for (int r = threadIdx.x; r < ld; r += kBlock) {
         double v = 0.0;
@@ -220,6 +228,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_bland(RevLP *__restrict__ lps, co
     }
 }
 
+template <bool IP>
 __global__ __launch_bounds__(kBlock) void k_rv_price(RevLP *__restrict__ lps, const int *__restrict__ act) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
@@ -244,12 +253,35 @@ __global__ __launch_bounds__(kBlock) void k_rv_price(RevLP *__restrict__ lps, co
     unsigned int bi = 0xFFFFFFFFu;
     for (int pos = wave; pos < nn; pos += nwaves) {
         const int j = nonbasic[pos];
-        price_elem<false>(cost, rvec, pos, j, wave_dot_row(At + (size_t)j * ld, svec, ld2, lane), lane, bk, bi, b2);
+        if constexpr (IP) price_elem<false>(cost, rvec, pos, j, wave_dot_row_t(ChildCol(d, j), svec, ld2, lane), lane, bk, bi, b2);
+        else price_elem<false>(cost, rvec, pos, j, wave_dot_row(At + (size_t)j * ld, svec, ld2, lane), lane, bk, bi, b2);
     }
     publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
 }
 
+// the rows of a chunked group as ChildCols: row r = column rowmap[wave + (k0 + r) * nwaves] of the child, where that position is < rows
+__device__ __forceinline__ void child_rows(const RevLP *d, const int32_t *__restrict__ rowmap, int rows, int k0, int wave, int nwaves,
+                                           ChildCol (&col)[kCkRows], bool (&has)[kCkRows]) {
+#pragma unroll
+    for (int r = 0; r < kCkRows; r++) {
+        const int pos = wave + (k0 + r) * nwaves;
+        has[r] = pos < rows;
+        if (has[r]) col[r] = ChildCol(d, rowmap[pos]);
+    }
+}
+// the rows of a chunked group where they lie in memory: row r = row wave + (k0 + r) * nwaves of M
+__device__ __forceinline__ void plain_rows(const double *__restrict__ M, int ld, int rows, int k0, int wave, int nwaves, PlainCol (&row)[kCkRows],
+                                           bool (&has)[kCkRows]) {
+#pragma unroll
+    for (int r = 0; r < kCkRows; r++) {
+        const int pos = wave + (k0 + r) * nwaves;
+        has[r] = pos < rows;
+        row[r].p = reinterpret_cast<const double2 *>(M + (size_t)(has[r] ? pos : 0) * ld);
+    }
+}
+
 // the chunked form of k_rv_price (k_price_ck)
+template <bool IP>
 __global__ __launch_bounds__(kBlock) void k_rv_price_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
@@ -273,7 +305,15 @@ __global__ __launch_bounds__(kBlock) void k_rv_price_ck(RevLP *__restrict__ lps,
     unsigned int bi = 0xFFFFFFFFu;
     for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
         double dot[kCkRows][1];
-        dot_group<1>(At, ld, nonbasic, nn, k0, wave, nwaves, {y}, svec, ck2, lane, dot);
+        if constexpr (IP) {
+            ChildCol col[kCkRows];
+            bool has[kCkRows];
+            child_rows(d, nonbasic, nn, k0, wave, nwaves, col, has);
+            const PlainCol vy[1] = {{reinterpret_cast<const double2 *>(y)}};
+            dot_group_t<1>(col, has, ld, vy, svec, ck2, lane, dot);
+        } else {
+            dot_group<1>(At, ld, nonbasic, nn, k0, wave, nwaves, {y}, svec, ck2, lane, dot);
+        }
 #pragma unroll
         for (int r = 0; r < kCkRows; r++) {
             const int pos = wave + (k0 + r) * nwaves;
@@ -283,7 +323,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_price_ck(RevLP *__restrict__ lps,
     publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
 }
 
-template <int MODE>
+template <int MODE, bool IP>
 __global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_price) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
@@ -308,7 +348,8 @@ __global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, co
     if (!pick_entering<false>(st, pkp, pip, nparts_price, rvec, nonbasic, tol, 0.0, forced_pos, forced_var, sk, si, ss, var)) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) d->flips_k2 = flips;   // K3 of this pivot reads the parity K2 worked on
     const int ld2 = ld >> 1;
-    stage_vec(svec, At + (size_t)var * ld, ld2);
+    if constexpr (IP) stage_vec_t(svec, ChildCol(d, var), ld2);
+    else stage_vec(svec, At + (size_t)var * ld, ld2);
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
@@ -319,7 +360,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, co
 }
 
 // the chunked form of k_rv_ftran (k_ftran_ck)
-template <int MODE>
+template <int MODE, bool IP>
 __global__ __launch_bounds__(kBlock) void k_rv_ftran_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_price, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
@@ -343,7 +384,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_ftran_ck(RevLP *__restrict__ lps,
     int var;
     if (!pick_entering<false>(st, pkp, pip, nparts_price, rvec, nonbasic, tol, 0.0, forced_pos, forced_var, sk, si, ss, var)) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) d->flips_k2 = flips;   // K3 of this pivot reads the parity K2 worked on
-    const double *col = At + (size_t)var * ld;
+    const double *col = IP ? nullptr : At + (size_t)var * ld;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
@@ -352,7 +393,15 @@ __global__ __launch_bounds__(kBlock) void k_rv_ftran_ck(RevLP *__restrict__ lps,
     unsigned int bi = 0xFFFFFFFFu;
     for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
         double dot[kCkRows][1];
-        dot_group<1>(binv_cur, ld, nullptr, m, k0, wave, nwaves, {col}, svec, ck2, lane, dot);
+        if constexpr (IP) {
+            PlainCol row[kCkRows];
+            bool has[kCkRows];
+            plain_rows(binv_cur, ld, m, k0, wave, nwaves, row, has);
+            const ChildCol vcol[1] = {ChildCol(d, var)};
+            dot_group_t<1>(row, has, ld, vcol, svec, ck2, lane, dot);
+        } else {
+            dot_group<1>(binv_cur, ld, nullptr, m, k0, wave, nwaves, {col}, svec, ck2, lane, dot);
+        }
 #pragma unroll
         for (int r = 0; r < kCkRows; r++) {
             const int i = wave + (k0 + r) * nwaves;
@@ -508,6 +557,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_dual_leave(RevLP *__restrict__ lp
 // dual pricing: per nonbasic column a_j.y and a_j.rho (rho = row p of B^-1), the row of At read once for both; r_pos = cost[j] - a_j.y
 // into rvec, the ratio r_j / -alpha_pj over alpha_pj < -1e-13 as a first-index argmin (k_dual_price's rule).  y and rho staged whole:
 // 2 * ld doubles of LDS, ld <= kRevDualLd.
+template <bool IP>
 __global__ __launch_bounds__(kBlock) void k_rv_dual_price(RevLP *__restrict__ lps, const int *__restrict__ act) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
@@ -536,7 +586,8 @@ __global__ __launch_bounds__(kBlock) void k_rv_dual_price(RevLP *__restrict__ lp
     for (int pos = wave; pos < nn; pos += nwaves) {
         const int j = nonbasic[pos];
         DotAcc acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-        wave_dot_chunk<2>(At + (size_t)j * ld, svec, ld2, 0, ld2, ld2, lane, acc);
+        if constexpr (IP) wave_dot_chunk_t<2>(ChildCol(d, j), svec, ld2, 0, ld2, ld2, lane, acc);
+        else wave_dot_chunk<2>(At + (size_t)j * ld, svec, ld2, 0, ld2, ld2, lane, acc);
         const double dy = wave_dot_finish(acc[0]), da = wave_dot_finish(acc[1]);
         const double r = cost[j] - dy;
         if (lane == 0) rvec[pos] = r;
@@ -547,6 +598,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_dual_price(RevLP *__restrict__ lp
 
 // the chunked form of k_rv_dual_price (k_dual_price_ck): y and rho streamed through LDS ck2 double2 each at a time, ck2 <= kRevDualLd / 2
 // (2 * ck2 double2 of LDS: 64 KB at most)
+template <bool IP>
 __global__ __launch_bounds__(kBlock) void k_rv_dual_price_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
@@ -570,7 +622,15 @@ __global__ __launch_bounds__(kBlock) void k_rv_dual_price_ck(RevLP *__restrict__
     unsigned int bi = 0xFFFFFFFFu;
     for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
         double dot[kCkRows][2];
-        dot_group<2>(At, ld, nonbasic, nn, k0, wave, nwaves, {y, rho}, svec, ck2, lane, dot);
+        if constexpr (IP) {
+            ChildCol col[kCkRows];
+            bool has[kCkRows];
+            child_rows(d, nonbasic, nn, k0, wave, nwaves, col, has);
+            const PlainCol vyr[2] = {{reinterpret_cast<const double2 *>(y)}, {reinterpret_cast<const double2 *>(rho)}};
+            dot_group_t<2>(col, has, ld, vyr, svec, ck2, lane, dot);
+        } else {
+            dot_group<2>(At, ld, nonbasic, nn, k0, wave, nwaves, {y, rho}, svec, ck2, lane, dot);
+        }
 #pragma unroll
         for (int r = 0; r < kCkRows; r++) {
             const int pos = wave + (k0 + r) * nwaves;
@@ -823,6 +883,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_ctrl(RevLP *__restrict__ lps, con
 // happens to see ends early.  That changes the work done, never the minimum.
 // Dynamic LDS: ld doubles, as K2.  grid: (nonbasic positions of the widest relaxation, list positions).
 // ------------------------------------------------------------------------------------------------
+template <bool IP>
 __global__ __launch_bounds__(kBlock) void k_rv_exch(RevLP *__restrict__ lps, const int *__restrict__ act) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ double smax[kWavesPerBlock];
@@ -838,7 +899,8 @@ __global__ __launch_bounds__(kBlock) void k_rv_exch(RevLP *__restrict__ lps, con
     if (seen < (unsigned int)j) return;   // (workgroup-uniform)
     const double *binv_cur = d->binv[d->flips & 1], *xb = d->xb;
     const int ld2 = ld >> 1;
-    stage_vec(svec, d->At + (size_t)j * ld, ld2);
+    if constexpr (IP) stage_vec_t(svec, ChildCol(d, j), ld2);
+    else stage_vec(svec, d->At + (size_t)j * ld, ld2);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const double dpv = wave_dot_row(binv_cur + (size_t)added * ld, svec, ld2, lane);   // (every wave: the same bits, workgroup-uniform)
     if (!(fabs(dpv) > 1e-9)) return;
@@ -864,6 +926,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_exch(RevLP *__restrict__ lps, con
 // the chunked form of k_rv_exch: a_j streamed through LDS ck2 double2 at a time.  d_added first, as one row's chunked dot by every wave
 // (the same bits in each); a candidate that fails there costs one row.  The other rows kCkRows per wave at a time (dot_group with the
 // workgroup's own kWavesPerBlock waves: row i = w, w + 4, ... as the one-pass loop takes them).
+template <bool IP>
 __global__ __launch_bounds__(kBlock) void k_rv_exch_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ double smax[kWavesPerBlock];
@@ -878,13 +941,15 @@ __global__ __launch_bounds__(kBlock) void k_rv_exch_ck(RevLP *__restrict__ lps, 
     __syncthreads();
     if (seen < (unsigned int)j) return;   // (workgroup-uniform)
     const double *binv_cur = d->binv[d->flips & 1], *xb = d->xb;
-    const double *col = d->At + (size_t)j * ld;
+    const double *col = IP ? nullptr : d->At + (size_t)j * ld;
+    const ChildCol vcol[1] = {IP ? ChildCol(d, j) : ChildCol()};
     const int ld2 = ld >> 1;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     DotAcc acc[1] = {{0, 0, 0, 0}};
     for (int c0 = 0; c0 < ld2; c0 += ck2) {
         const int c1 = min(c0 + ck2, ld2);
-        stage_chunk<1>(svec, ck2, {col}, c0, c1);
+        if constexpr (IP) stage_chunk_t<1>(svec, ck2, vcol, c0, c1);
+        else stage_chunk<1>(svec, ck2, {col}, c0, c1);
         wave_dot_chunk<1>(binv_cur + (size_t)added * ld, svec, ck2, c0, c1, ld2, lane, acc);
     }
     const double dpv = wave_dot_finish(acc[0]);   // (every wave: the same bits, workgroup-uniform)
@@ -895,7 +960,14 @@ __global__ __launch_bounds__(kBlock) void k_rv_exch_ck(RevLP *__restrict__ lps, 
     const int kmax = (m + kWavesPerBlock - 1) / kWavesPerBlock;
     for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
         double dot[kCkRows][1];
-        dot_group<1>(binv_cur, ld, nullptr, m, k0, w, kWavesPerBlock, {col}, svec, ck2, lane, dot);
+        if constexpr (IP) {
+            PlainCol row[kCkRows];
+            bool has[kCkRows];
+            plain_rows(binv_cur, ld, m, k0, w, kWavesPerBlock, row, has);
+            dot_group_t<1>(row, has, ld, vcol, svec, ck2, lane, dot);
+        } else {
+            dot_group<1>(binv_cur, ld, nullptr, m, k0, w, kWavesPerBlock, {col}, svec, ck2, lane, dot);
+        }
 #pragma unroll
         for (int r = 0; r < kCkRows; r++) {
             const int i = w + (k0 + r) * kWavesPerBlock;
@@ -941,17 +1013,18 @@ __global__ void k_rv_exch_pick(RevLP *__restrict__ lps, const int *__restrict__ 
 void launch_rv_assemble(const RevLP *lps, int count, int n_max, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_assemble, dim3(n_max + 1, count), dim3(kBlock), 0, s, lps);
 }
-void launch_rv_init(RevLP *lps, int count, hipStream_t s) {
-    hipLaunchKernelGGL(k_rv_init, dim3(count), dim3(kBlock), 0, s, lps);
+// (inplace: the IP = true instantiation of every kernel that reads a child's column; 0: the IP = false ones, the kernels as they were)
+void launch_rv_init(RevLP *lps, int count, int inplace, hipStream_t s) {
+    hipLaunchKernelGGL(inplace ? k_rv_init<true> : k_rv_init<false>, dim3(count), dim3(kBlock), 0, s, lps);
 }
 // (ck2 > 0: the chunked forms, ck2 double2 of dynamic LDS; 0: the one-pass forms with `lds` bytes)
-void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, int ck2, hipStream_t s) {
+void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, int ck2, int inplace, hipStream_t s) {
     const size_t ldc = (size_t)ck2 * sizeof(double2);
     if (ck2 > 0) {
-        hipLaunchKernelGGL(k_rv_ftran_ck<RR_FORCED>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, 0, ck2);
+        hipLaunchKernelGGL((inplace ? k_rv_ftran_ck<RR_FORCED, true> : k_rv_ftran_ck<RR_FORCED, false>), dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, 0, ck2);
         hipLaunchKernelGGL(k_rv_update_ck<RR_FORCED>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gr, ck2);
     } else {
-        hipLaunchKernelGGL(k_rv_ftran<RR_FORCED>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, 0);
+        hipLaunchKernelGGL((inplace ? k_rv_ftran<RR_FORCED, true> : k_rv_ftran<RR_FORCED, false>), dim3(gr, nact), dim3(kBlock), lds, s, lps, act, 0);
         hipLaunchKernelGGL(k_rv_update<RR_FORCED>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
     }
     hipLaunchKernelGGL(k_rv_lists, dim3(nact), dim3(kBlock), 0, s, lps, act);
@@ -961,42 +1034,42 @@ void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, s
     hipLaunchKernelGGL(k_rv_y_reduce, dim3((ld_max + kBlock - 1) / kBlock, nact), dim3(kBlock), 0, s, lps, act);
     hipLaunchKernelGGL(k_rv_check, dim3(nact), dim3(kBlock), 0, s, lps, act);
 }
-void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int ck2, hipStream_t s) {
+void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int ck2, int inplace, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_bland, dim3(nact), dim3(kBlock), 0, s, lps, act);
     if (ck2 > 0) {
         const size_t ldc = (size_t)ck2 * sizeof(double2);
-        hipLaunchKernelGGL(k_rv_price_ck, dim3(gp, nact), dim3(kBlock), ldc, s, lps, act, ck2);
-        hipLaunchKernelGGL(k_rv_ftran_ck<RR_LOOP>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gp, ck2);
+        hipLaunchKernelGGL(inplace ? k_rv_price_ck<true> : k_rv_price_ck<false>, dim3(gp, nact), dim3(kBlock), ldc, s, lps, act, ck2);
+        hipLaunchKernelGGL((inplace ? k_rv_ftran_ck<RR_LOOP, true> : k_rv_ftran_ck<RR_LOOP, false>), dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gp, ck2);
         hipLaunchKernelGGL(k_rv_update_ck<RR_LOOP>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gr, ck2);
         return;
     }
-    hipLaunchKernelGGL(k_rv_price, dim3(gp, nact), dim3(kBlock), lds, s, lps, act);
-    hipLaunchKernelGGL(k_rv_ftran<RR_LOOP>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp);
+    hipLaunchKernelGGL(inplace ? k_rv_price<true> : k_rv_price<false>, dim3(gp, nact), dim3(kBlock), lds, s, lps, act);
+    hipLaunchKernelGGL((inplace ? k_rv_ftran<RR_LOOP, true> : k_rv_ftran<RR_LOOP, false>), dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp);
     hipLaunchKernelGGL(k_rv_update<RR_LOOP>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
 }
 void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_ctrl, dim3(nact), dim3(kBlock), 0, s, lps, act, out);
 }
-void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, int ck2, hipStream_t s) {
-    if (ck2 > 0) hipLaunchKernelGGL(k_rv_exch_ck, dim3(nn_max, nact), dim3(kBlock), (size_t)ck2 * sizeof(double2), s, lps, act, ck2);
-    else hipLaunchKernelGGL(k_rv_exch, dim3(nn_max, nact), dim3(kBlock), lds, s, lps, act);
+void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, int ck2, int inplace, hipStream_t s) {
+    if (ck2 > 0) hipLaunchKernelGGL(inplace ? k_rv_exch_ck<true> : k_rv_exch_ck<false>, dim3(nn_max, nact), dim3(kBlock), (size_t)ck2 * sizeof(double2), s, lps, act, ck2);
+    else hipLaunchKernelGGL(inplace ? k_rv_exch<true> : k_rv_exch<false>, dim3(nn_max, nact), dim3(kBlock), lds, s, lps, act);
     hipLaunchKernelGGL(k_rv_exch_pick, dim3(nact), dim3(64), 0, s, lps, act);
 }
 void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_warm_binv, dim3(m_max, count), dim3(kBlock), 0, s, lps);
 }
 // (ck2d > 0: the chunked pricing kernel, its TWO vectors ck2d double2 each; ck2: K2 / K3 as in launch_rv_pivot)
-void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, int ck2, int ck2d, hipStream_t s) {
+void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, int ck2, int ck2d, int inplace, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_dual_leave, dim3(nact), dim3(kBlock), 0, s, lps, act);
-    if (ck2d > 0) hipLaunchKernelGGL(k_rv_dual_price_ck, dim3(gp, nact), dim3(kBlock), (size_t)2 * ck2d * sizeof(double2), s, lps, act, ck2d);
-    else hipLaunchKernelGGL(k_rv_dual_price, dim3(gp, nact), dim3(kBlock), lds2, s, lps, act);
+    if (ck2d > 0) hipLaunchKernelGGL(inplace ? k_rv_dual_price_ck<true> : k_rv_dual_price_ck<false>, dim3(gp, nact), dim3(kBlock), (size_t)2 * ck2d * sizeof(double2), s, lps, act, ck2d);
+    else hipLaunchKernelGGL(inplace ? k_rv_dual_price<true> : k_rv_dual_price<false>, dim3(gp, nact), dim3(kBlock), lds2, s, lps, act);
     if (ck2 > 0) {
         const size_t ldc = (size_t)ck2 * sizeof(double2);
-        hipLaunchKernelGGL(k_rv_ftran_ck<RR_DUAL>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gp, ck2);
+        hipLaunchKernelGGL((inplace ? k_rv_ftran_ck<RR_DUAL, true> : k_rv_ftran_ck<RR_DUAL, false>), dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gp, ck2);
         hipLaunchKernelGGL(k_rv_update_ck<RR_DUAL>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gr, ck2);
         return;
     }
-    hipLaunchKernelGGL(k_rv_ftran<RR_DUAL>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp);
+    hipLaunchKernelGGL((inplace ? k_rv_ftran<RR_DUAL, true> : k_rv_ftran<RR_DUAL, false>), dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp);
     hipLaunchKernelGGL(k_rv_update<RR_DUAL>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
 }
 

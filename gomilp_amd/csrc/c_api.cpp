@@ -121,7 +121,7 @@ int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value) {
         for (auto &e : pool->eng) e->limit_rows_to_lds_window(value == 0);
     }
     if (sc == Scope::Pool || sc == Scope::PoolAndWorkers) {
-        pool->knobs.set(key, value);
+        if (!pool->knobs.set(key, value)) return GOMILP_ERR_BAD_SHAPE;   // (a value the knob refuses: a negative rev_mem_limit)
         pool->apply_knobs(*pool->batch);
         if (pool->batch2) pool->apply_knobs(*pool->batch2);
         if (sc == Scope::Pool) return GOMILP_OK;
@@ -356,6 +356,21 @@ int gomilp_debug_wave_plan(int64_t nroots, const int64_t *root_m, const int64_t 
     for (size_t t = 0; t < c.phase1.size(); t++) { group[c.phase1[t]] = GOMILP_WP_GROUP_PHASE1; pos[c.phase1[t]] = (int32_t)t; }
     if (c.cut == gomilp::WavePlan::HALVES)
         for (int64_t i = 0; i < count; i++) { group[i] = i < c.half ? GOMILP_WP_GROUP_HALF0 : GOMILP_WP_GROUP_HALF1; pos[i] = (int32_t)(i < c.half ? i : i - c.half); }
+    return GOMILP_OK;
+}
+
+// diagnostic (host only, no device): the two arenas of a wave of the batched revised simplex, in doubles — RevBatchEngine::layout, the
+// function RevBatchEngine::run sizes its buffers from
+int gomilp_debug_rev_footprint(int64_t nroots, const int64_t *root_m, const int64_t *root_n, int64_t count, const int32_t *root_of, const int64_t *koff,
+                               int32_t inplace, int64_t *out) {
+    if (nroots < 1 || nroots > 64 || !root_m || !root_n || count < 0 || count > (1 << 20) || !koff || !out || koff[0] < 0) return -GOMILP_ERR_BAD_SHAPE;
+    for (int64_t r = 0; r < nroots; r++)
+        if (root_m[r] < 1 || root_n[r] < 1 || root_m[r] > (1 << 20) || root_n[r] > (1 << 20)) return -GOMILP_ERR_BAD_SHAPE;
+    for (int64_t i = 0; i < count; i++)
+        if (koff[i + 1] < koff[i] || koff[i + 1] - koff[i] > (1 << 20) || (root_of && (root_of[i] < 0 || root_of[i] >= nroots))) return -GOMILP_ERR_BAD_SHAPE;
+    size_t at_tot = 0, wk_tot = 0;
+    gomilp::RevBatchEngine::layout(root_m, root_n, count, root_of, koff, inplace != 0, nullptr, &at_tot, &wk_tot);
+    out[0] = (int64_t)at_tot; out[1] = (int64_t)wk_tot;
     return GOMILP_OK;
 }
 

@@ -72,6 +72,30 @@ bool RevBatchEngine::eligible(const Engine::RootView &R, int K_min, int K_max, i
     return true;
 }
 
+void RevBatchEngine::layout(const int64_t *root_m, const int64_t *root_n, int64_t count, const int32_t *root_of, const int64_t *koff, bool inplace,
+                            Lay *lay, size_t *at_tot_out, size_t *wk_tot_out) {
+    size_t at_tot = 0, wk_tot = 0;
+    for (int64_t i = 0; i < count; i++) {
+        const int r = root_of ? root_of[i] : 0;
+        const int K = (int)(koff[i + 1] - koff[i]), m = (int)root_m[r] + K, n = (int)root_n[r] + K, ld = (m + 1) & ~1;
+        Lay L;
+        L.at = inplace ? 0 : at_tot;
+        if (!inplace) at_tot += (size_t)(n + 1) * ld;
+        auto take = [&](size_t doubles) { const size_t o = wk_tot; wk_tot += even(doubles); return o; };
+        L.wk0 = wk_tot;
+        L.binv0 = take((size_t)m * ld); L.binv1 = take((size_t)m * ld);
+        L.xb = take(ld); L.y = take(ld); L.dvec = take(ld); L.move = take(ld); L.bb = take(ld);
+        L.rvec = take((size_t)n + 1 - m); L.c1 = take((size_t)n + 1); L.ysc = take((size_t)64 * ld);
+        L.basic = take(((size_t)ld + 1) / 2); L.nonbasic = take(((size_t)n + 2 - m + 1) / 2); L.inb = take(((size_t)n + 2 + 1) / 2);
+        L.pkp = take(kMaxPartials); L.pkr = take(kMaxPartials); L.pip = take(kMaxPartials / 2); L.pir = take(kMaxPartials / 2);
+        L.st = take((sizeof(DevState) + 7) / 8);
+        L.art = inplace ? take(ld) : 0;   // (behind everything else: the other offsets of a relaxation are those of the assembled layout)
+        L.wk1 = wk_tot;
+        if (lay) lay[i] = L;
+    }
+    *at_tot_out = at_tot; *wk_tot_out = wk_tot;
+}
+
 int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const int32_t *root_of, int64_t count, const int64_t *koff,
                         const int32_t *var, const double *sign, const double *rhs, double tol, int64_t max_pivots,
                         const BatchEngine::DoneFn &on_done, Stats *stats, bool *fits, const WarmSpec *warm) {
@@ -126,22 +150,14 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
     }
 
     // ---- layout: per relaxation, offsets into the two arenas (doubles; every buffer 16-byte aligned) ----
-    struct Lay { size_t wk0, wk1; size_t at, binv0, binv1, xb, y, dvec, move, bb, rvec, c1, ysc, basic, nonbasic, inb, pkp, pkr, pip, pir, st; };
+    // (RevBatchEngine::layout; the knob is read once: the whole run is of one mode)
+    const bool inplace = inplace_;
     std::vector<Lay> lay((size_t)count);
     size_t at_tot = 0, wk_tot = 0;
-    for (int64_t i = 0; i < count; i++) {
-        const int K = (int)(koff[i + 1] - koff[i]), m = root_at(i).m + K, n = root_at(i).n + K, ld = (m + 1) & ~1;
-        Lay &L = lay[(size_t)i];
-        L.at = at_tot; at_tot += (size_t)(n + 1) * ld;
-        auto take = [&](size_t doubles) { const size_t o = wk_tot; wk_tot += even(doubles); return o; };
-        L.wk0 = wk_tot;
-        L.binv0 = take((size_t)m * ld); L.binv1 = take((size_t)m * ld);
-        L.xb = take(ld); L.y = take(ld); L.dvec = take(ld); L.move = take(ld); L.bb = take(ld);
-        L.rvec = take((size_t)n + 1 - m); L.c1 = take((size_t)n + 1); L.ysc = take((size_t)64 * ld);
-        L.basic = take(((size_t)ld + 1) / 2); L.nonbasic = take(((size_t)n + 2 - m + 1) / 2); L.inb = take(((size_t)n + 2 + 1) / 2);
-        L.pkp = take(kMaxPartials); L.pkr = take(kMaxPartials); L.pip = take(kMaxPartials / 2); L.pir = take(kMaxPartials / 2);
-        L.st = take((sizeof(DevState) + 7) / 8);
-        L.wk1 = wk_tot;
+    {
+        std::vector<int64_t> root_m((size_t)nroots), root_n((size_t)nroots);
+        for (int r = 0; r < nroots; r++) if (root_used[(size_t)r]) { root_m[(size_t)r] = roots[r]->m; root_n[(size_t)r] = roots[r]->n; }
+        layout(root_m.data(), root_n.data(), count, root_of, koff, inplace, lay.data(), &at_tot, &wk_tot);
     }
     // one block per used root in the shared arena: b0 (m_r) | c2 = [c, 0...] (n_r + K_max + 2) among the doubles, rho0 (m_r + 1) among the ints
     struct RootBlk { size_t b0 = 0, c2 = 0, rho = 0; };
@@ -166,6 +182,8 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
         if (grow) {
             size_t avail = 0, total = 0;
             RV_TRY(hipMemGetInfo(&avail, &total));
+            // (pool knob rev_mem_limit: a cap below the free memory takes its place)
+            if (mem_limit_mib_ > 0 && (uint64_t)mem_limit_mib_ < ((uint64_t)avail >> 20)) avail = (size_t)mem_limit_mib_ << 20;
             // (buffers that the re-allocation releases are not counted as free: conservative)
             if (grow + grow / 16 + ((size_t)256 << 20) > avail) { *fits = false; return GOMILP_OK; }
         }
@@ -242,7 +260,7 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
         RevLP &d = lps[(size_t)i];
         memset(&d, 0, sizeof(d));
         double *w = b.d_work;
-        d.At = b.d_at + L.at; d.c2 = d_c2; d.c1 = w + L.c1; d.b = w + L.bb;
+        d.At = inplace ? nullptr : b.d_at + L.at; d.c2 = d_c2; d.c1 = w + L.c1; d.b = w + L.bb;
         d.binv[0] = w + L.binv0; d.binv[1] = w + L.binv1;
         d.xb = w + L.xb; d.y = w + L.y; d.dvec = w + L.dvec; d.move = w + L.move; d.rvec = w + L.rvec; d.yscratch = w + L.ysc;
         d.basic = reinterpret_cast<int32_t *>(w + L.basic); d.nonbasic = reinterpret_cast<int32_t *>(w + L.nonbasic);
@@ -256,6 +274,7 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
         d.stage = RS_RUN; d.run = RR_NONE; d.cost = d_c2; d.f_var = d.f_pos = d.f_p = -1;
         d.exch_on = exchange_ ? 1 : 0; d.x_added = -1; d.x_best = 0xFFFFFFFFu;
         d.At0 = R.dAt; d.ld0 = R.ld; d.avar = d_var + (koff[i] - k_base); d.asign = d_sign + (koff[i] - k_base);
+        d.inplace = inplace ? 1 : 0; d.art = inplace ? w + L.art : nullptr;
         const Plan &P = plan[(size_t)i];
         if (P.e) {
             d.warm = 1; d.wJ = P.J; d.wmp = P.e->m; d.wldp = P.e->ld;
@@ -268,9 +287,11 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
     int64_t launches = 0;
     // (the roots' At0 are read where they lie: a root's upload, Engine::upload on its owner's stream, ends with a synchronisation of that
     // stream, so every root the pool holds is complete on the device before this stream reads it)
-    launch_rv_assemble(b.d_lps, (int)count, n_max, stream_);
-    launch_rv_init(b.d_lps, (int)count, stream_);
-    launches += 2;
+    // (rev_inplace: nothing is assembled — the kernels read those At0 through ChildCol for the whole run)
+    const int ip = inplace ? 1 : 0;
+    if (!inplace) { launch_rv_assemble(b.d_lps, (int)count, n_max, stream_); launches++; }
+    launch_rv_init(b.d_lps, (int)count, ip, stream_);
+    launches++;
     if (nwarm) { launch_rv_warm_binv(b.d_lps, (int)count, m_max, stream_); launches++; }
     RV_TRY(hipStreamSynchronize(stream_));   // (the pageable staging vectors go out of use here)
     RV_TRY(hipGetLastError());
@@ -305,12 +326,12 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
         bool any_dual = false, any_primal = false, any_scan = false;
         for (int id : act) { (in_dual[(size_t)id] ? any_dual : any_primal) = true; if (in_scan[(size_t)id]) any_scan = true; }
         // (the scan's verdict orders the forced pivot that the set-up launches behind it run: an exchange costs no superstep of its own)
-        if (any_scan) { launch_rv_exchange(b.d_lps, b.d_act, nact, nn_max, lds, ck2, stream_); launches += 2; }
-        launch_rv_setup(b.d_lps, b.d_act, nact, gr, ld_max, lds, ck2, stream_);
+        if (any_scan) { launch_rv_exchange(b.d_lps, b.d_act, nact, nn_max, lds, ck2, ip, stream_); launches += 2; }
+        launch_rv_setup(b.d_lps, b.d_act, nact, gr, ld_max, lds, ck2, ip, stream_);
         const int chunk = steps < 2 ? kFirstChunk : kChunk;
         for (int t = 0; t < chunk; t++) {
-            if (any_dual) launch_rv_dual_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, 2 * lds, ck2, ck2d, stream_);
-            if (any_primal) launch_rv_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, ck2, stream_);
+            if (any_dual) launch_rv_dual_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, 2 * lds, ck2, ck2d, ip, stream_);
+            if (any_primal) launch_rv_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, ck2, ip, stream_);
         }
         launch_rv_ctrl(b.d_lps, b.d_act, nact, b.d_out, stream_);
         launches += 7 + 4 * chunk * ((any_dual ? 1 : 0) + (any_primal ? 1 : 0)) + 1;
@@ -339,7 +360,7 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
                 is_warm[(size_t)id] = 0; in_dual[(size_t)id] = 0; in_scan[(size_t)id] = 0;
                 RV_TRY(hipMemsetAsync(b.d_work + L.wk0, 0, (L.wk1 - L.wk0) * sizeof(double), stream_));
                 RV_TRY(hipMemcpyAsync(b.d_lps + id, &d, sizeof(RevLP), hipMemcpyHostToDevice, stream_));
-                launch_rv_init(b.d_lps + id, 1, stream_);
+                launch_rv_init(b.d_lps + id, 1, ip, stream_);
                 launches++;
                 next.push_back(id);
                 continue;

@@ -51,6 +51,23 @@ class RevBatchEngine {
     // and warm starts are not limited to kRevDualLd.  Bit-identical to the one-pass forms.  Off (default): row_chunk is not looked at.
     void set_large_rows(bool on, int64_t row_chunk) { large_rows_ = on; row_chunk_ = row_chunk; }
 
+    // pool knob rev_inplace: the run assembles no At — no At arena, no k_rv_assemble launch; every kernel that reads a child's column takes
+    // it from the relaxation's root where it lies (ChildCol, rev_child_col.h), and the Phase-I artificial column is one ld-long row per
+    // relaxation in the work arena.  Bit-identical to the assembled run.  Off (default): today's launches.
+    void set_inplace(bool on) { inplace_ = on; }
+    // pool knob rev_mem_limit (MiB; 0: none): where it is below the free device memory it takes its place in the test behind *fits
+    void set_mem_limit(int64_t mib) { mem_limit_mib_ = mib > 0 ? mib : 0; }
+
+    // The layout of a wave's two arenas, in doubles, per relaxation: offsets into the work arena (cleared per wave; [wk0, wk1) is the
+    // relaxation's own part) and `at` into the At arena.  inplace: no At (at = 0 everywhere, *at_tot = 0) and `art`, the ld-long row of
+    // the artificial column, in the work arena (unused otherwise).
+    struct Lay { size_t wk0, wk1; size_t at, binv0, binv1, xb, y, dvec, move, bb, rvec, c1, ysc, basic, nonbasic, inb, pkp, pkr, pip, pir, st, art; };
+    // A pure function of the shapes (no HIP call): relaxation i is a child of root root_of[i] (null: of root 0; the caller has checked the
+    // range) with koff[i + 1] - koff[i] branch rows.  lay: null, or room for count entries.  run sizes its buffers from it, and
+    // gomilp_debug_rev_footprint reports it.
+    static void layout(const int64_t *root_m, const int64_t *root_n, int64_t count, const int32_t *root_of, const int64_t *koff, bool inplace,
+                       Lay *lay, size_t *at_tot, size_t *wk_tot);
+
     // gives the wave buffers back (they grow with the largest wave seen: 5 MB per 300 x 1500 relaxation); the pool calls it when the
     // root changes
     void release();
@@ -61,6 +78,8 @@ class RevBatchEngine {
     bool exchange_ = true;
     bool large_rows_ = false;
     int64_t row_chunk_ = 0;
+    bool inplace_ = false;
+    int64_t mem_limit_mib_ = 0;
     hipStream_t stream_ = nullptr;
     Buf *b_;
 };

@@ -20,7 +20,7 @@ namespace gomilp {
 PoolKnobs::Scope PoolKnobs::scope(const char *key) {
     const std::string k(key);
     for (const char *p : {"batched", "batch_revised", "warm_revised", "rev_exchange", "rev_roots", "split_large", "split_phase", "large_loop",
-                          "batch_virt", "batch_res", "batch_loop", "sample_batch", "lu_large", "large_rows"})
+                          "batch_virt", "batch_res", "batch_loop", "sample_batch", "lu_large", "large_rows", "rev_inplace", "rev_mem_limit"})
         if (k == p) return Scope::Pool;
 #ifdef GOMILP_DEBUG
     if (k == "bt_fault") return Scope::PoolAndWorkers;
@@ -36,9 +36,14 @@ bool PoolKnobs::set(const char *key, int64_t value) {
         {"batched", &batched}, {"batch_revised", &batch_revised}, {"warm_revised", &warm_revised}, {"rev_exchange", &rev_exchange},
         {"rev_roots", &rev_roots}, {"split_large", &split_large}, {"split_phase", &split_phase}, {"large_loop", &large_loop},
         {"batch_virt", &batch_virt}, {"batch_res", &batch_res}, {"batch_loop", &batch_loop}, {"sample_batch", &sample_batch},
-        {"large_rows", &large_rows}};
+        {"large_rows", &large_rows}, {"rev_inplace", &rev_inplace}};
     for (auto &f : flags) if (k == f.name) { *f.at = value ? 1 : 0; return true; }
     if (k == "lu_large") return true;
+    if (k == "rev_mem_limit") {   // MiB; 0: none
+        if (value < 0) return false;
+        rev_mem_limit = value;
+        return true;
+    }
     if (k == "cond_guard") { cond_guard = (int)value; return true; }
     if (k == "exact_degenerate") { exact_degenerate = (int)value; return true; }
 #ifdef GOMILP_DEBUG
@@ -341,6 +346,8 @@ struct Wave {
         RevBatchEngine::Stats rs;
         pool->rev->set_exchange(pool->knobs.rev_exchange != 0);
         pool->rev->set_large_rows(pool->knobs.large_rows != 0, pool->knobs.row_chunk);
+        pool->rev->set_inplace(pool->knobs.rev_inplace != 0);
+        pool->rev->set_mem_limit(pool->knobs.rev_mem_limit);
         gomilp::WarmSpec wspec;
         if (wa) {
             wspec.store = &pool->warm; wspec.parent = wa->parent; wspec.tag = wa->tag; wspec.keep = wa->keep; wspec.dual_budget = wa->budget;

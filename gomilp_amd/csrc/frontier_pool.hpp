@@ -48,6 +48,12 @@ struct PoolKnobs {
     int rev_exchange = 1;       // on the batched revised simplex a relaxation whose Phase I ends with the artificial basic at level zero
                                 // exchanges it on the device (batch_revised.hip: k_rv_exch) instead of going to a worker's whole solve — the same
                                 // column, bit-identical results; 0: the hand-over (host_fallbacks)
+    int rev_inplace = 0;        // (opt-in) a run of the batched revised simplex assembles no per-child A^T: its kernels read the root's resident
+                                // A^T in place and synthesise the K branch entries and unit columns (rev_child_col.h) — no At arena ((n + 1) x ld
+                                // doubles per relaxation), no k_rv_assemble launch, bit-identical results; 0: today's launches.  Routing does not
+                                // depend on it
+    int64_t rev_mem_limit = 0;  // MiB, 0: none.  Where it is below the free device memory it takes its place in RevBatchEngine::run's test of
+                                // whether a wave's buffers fit (a wave that does not fit runs on the workers, whole): a cap for a shared card
     int64_t max_pivots = 0;     // the workers' knob of this name, as the batched revised simplex needs it (negative: 0)
     int64_t row_chunk = 0;      // the workers' knob of this name (doubles per LDS chunk, a multiple of 512 up to 8192; 0: automatic): with
                                 // large_rows = 1 the batched revised simplex stages in chunks of it too, at any row count; with large_rows = 0 that

@@ -72,7 +72,7 @@ class FrontierStats(C.Structure):
 
 EXPORTS = [
     "gomilp_lp_solve_warm", "gomilp_frontier_solve_warm", "gomilp_pool_release_warm",
-    "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond", "gomilp_debug_lu_host_solve", "gomilp_debug_bt_plan", "gomilp_debug_wave_plan",
+    "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond", "gomilp_debug_lu_host_solve", "gomilp_debug_bt_plan", "gomilp_debug_wave_plan", "gomilp_debug_rev_footprint",
     "gomilp_lp_simplex", "gomilp_ctx_create", "gomilp_ctx_destroy", "gomilp_ctx_device", "gomilp_ctx_set",
     "gomilp_lp_upload", "gomilp_lp_free", "gomilp_lp_solve_resident", "gomilp_lp_last_trace", "gomilp_version",
     "gomilp_device_count", "gomilp_compiled_arch", "gomilp_comm_unique_id", "gomilp_comm_create", "gomilp_comm_destroy",
@@ -137,6 +137,8 @@ def lib():
     L.gomilp_debug_wave_plan.restype = C.c_int
     L.gomilp_debug_wave_plan.argtypes = [C.c_int64, ip, ip, i32p, dp, C.c_int64, i32p, ip, i32p, dp, C.c_int32, i32p, C.c_int64, ip, C.c_int64,
                                          C.POINTER(C.c_char_p), ip, i32p, i32p, i32p, i32p]
+    L.gomilp_debug_rev_footprint.restype = C.c_int
+    L.gomilp_debug_rev_footprint.argtypes = [C.c_int64, ip, ip, C.c_int64, i32p, ip, C.c_int32, ip]
     L.gomilp_debug_find_independent.restype = C.c_int64
     L.gomilp_debug_find_independent_device.restype = C.c_int64
     L.gomilp_debug_find_independent_device.argtypes = [C.c_void_p, C.c_int64, ip, C.c_int64]
@@ -361,7 +363,10 @@ class FrontierPool:
         waves runs on the batched revised simplex with warm starts; default 0), "rev_exchange" (1: that schedule exchanges a zero-level
         artificial on the device, stats art_exchanges; 0: the relaxation goes to a worker, host_fallbacks), "rev_roots" (1, default: a
         wide wave of several roots — solve(children, roots=...) — runs on the batched revised simplex as one schedule; 0: on the workers),
-        "large_rows" (1: roots and children beyond 8192 rows, wide waves on that schedule's chunked kernels; default 0: refused), the other pool knobs of include/gomilp_lp.h, or any Context knob."""
+        "large_rows" (1: roots and children beyond 8192 rows, wide waves on that schedule's chunked kernels; default 0: refused),
+        "rev_inplace" (1: that schedule reads the root's A^T in place instead of a copy per child — bit-identical, most of a wave's memory
+        saved, see debug_rev_footprint; default 0), "rev_mem_limit" (MiB, 0: none: a cap on the free memory that schedule's wave buffers
+        must fit; a wave that does not fit runs on the workers), the other pool knobs of include/gomilp_lp.h, or any Context knob."""
         rc = lib().gomilp_pool_set(self._h, key.encode(), int(value))
         if rc != OK:
             raise ValueError("bad knob %s=%s" % (key, value))
@@ -638,6 +643,24 @@ def debug_wave_plan(roots, children, root_of=None, warm=None, spent=(), **knobs)
         raise ValueError("bad shape, list or key: %r" % (knobs,))
     return {"route": WP_ROUTES[route.value], "cut": WP_CUTS[cut.value], "groups": [WP_GROUPS[g] for g in group[: pk.count]],
             "pos": [int(v) for v in pos[: pk.count]]}
+
+
+def debug_rev_footprint(roots, children, root_of=None, inplace: bool = False) -> tuple:
+    """(doubles of the At arena, doubles of the work arena) of the wave `children` — constraint lists, or their counts of branch rows —
+    of `roots`, (m, n) each, on the batched revised simplex with pool knob rev_inplace = `inplace`: the schedule's own layout
+    (RevBatchEngine::layout), host only (no device).  ValueError for a bad shape or list."""
+    rm = np.array([r[0] for r in roots], dtype=np.int64)
+    rn = np.array([r[1] for r in roots], dtype=np.int64)
+    ks = [int(ch) if np.isscalar(ch) else len(ch) for ch in children]
+    koff = np.zeros(len(ks) + 1, dtype=np.int64)
+    koff[1:] = np.cumsum(ks)
+    rof = None if root_of is None else np.ascontiguousarray(root_of, dtype=np.int32)
+    out = np.zeros(2, dtype=np.int64)
+    rc = lib().gomilp_debug_rev_footprint(len(roots), _ip(rm), _ip(rn), len(ks), None if rof is None else rof.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          _ip(koff), 1 if inplace else 0, _ip(out))
+    if rc != OK:
+        raise ValueError("bad shape or list")
+    return int(out[0]), int(out[1])
 
 
 def debug_cond_estimate(B, inf: bool = False) -> float:

@@ -289,7 +289,14 @@ void gomilp_pool_destroy(gomilp_pool *pool);
  * stream on the chunked three-kernel loop — and a final state that does not fit is not kept (warm_kept), which is no error.  With the
  * knob at 1 the pool also stages in chunks of the worker knob "row_chunk" where that is set, at any row count (tests).  0: pools keep the
  * 8192-row limit and never look at "row_chunk"; clearing the knob while the pool holds a root beyond 8192 rows returns
- * GOMILP_ERR_BAD_SHAPE.  DESIGN.md section 2.5e); any gomilp_ctx_set key is forwarded to the worker contexts ("row_chunk" is remembered
+ * GOMILP_ERR_BAD_SHAPE.  DESIGN.md section 2.5e), "rev_inplace" (default 0, opt-in: a run of that schedule assembles no per-child copy of
+ * A^T — (n + 1) x ld doubles per relaxation, most of a wave's memory: 3.6 MB of 5 MB at 300 x 1500 — but reads the root's resident A^T in
+ * place and synthesises the K branch entries and unit columns while it reads, with one ld-long row per relaxation for the Phase-I
+ * artificial column: the same arithmetic in the same order, bit-identical results, one launch less per wave, and wider waves fit the
+ * device.  Routing does not depend on it; 0: the launches as they were.  gomilp_debug_rev_footprint gives both footprints),
+ * "rev_mem_limit" (MiB, default 0: none; a negative value is GOMILP_ERR_BAD_SHAPE: where it is below the free device memory it takes its
+ * place in that schedule's test of whether a wave's buffers fit — a cap on the wave buffers for a caller on a shared card; a wave that does
+ * not fit runs on the workers, whole); any gomilp_ctx_set key is forwarded to the worker contexts ("row_chunk" is remembered
  * by the pool as well). */
 int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value);
 /* Upload the root standard form (row-major A0, stride lda) to every worker context of the pool. */
@@ -422,6 +429,16 @@ int gomilp_debug_wave_plan(int64_t nroots, const int64_t *root_m, const int64_t 
                            int64_t count, const int32_t *root_of, const int64_t *koff, const int32_t *var, const double *rhs, int32_t warm_call,
                            const int32_t *warm, int64_t nspent, const int64_t *spent, int64_t nknobs, const char *const *keys, const int64_t *values,
                            int32_t *route, int32_t *cut, int32_t *group, int32_t *pos);
+
+/* Diagnostic (host only, no device): the device memory a wave takes on the batched revised simplex of pool knob "batch_revised", as that
+ * schedule itself lays it out (the function its run sizes its buffers from).  Roots by shape, the wave as count / root_of (NULL: all of
+ * root 0) / koff of gomilp_frontier_solve_roots; inplace: the value of pool knob "rev_inplace".  With m_i, n_i the child's rows and
+ * columns and ld_i = m_i rounded up to even: out[0], doubles of the arena of assembled A^T copies, is the sum of (n_i + 1) * ld_i, or 0
+ * with inplace; out[1], doubles of the work arena (both B^-1, the vectors, the lists), is larger by the sum of ld_i with inplace — the
+ * rows of the artificial columns.  The schedule takes the wave when (out[0] + out[1]) * 8 bytes, plus a sixteenth, plus 256 MiB fit the
+ * free device memory (or pool knob "rev_mem_limit").  Returns GOMILP_OK, or -GOMILP_ERR_BAD_SHAPE for a bad shape or list. */
+int gomilp_debug_rev_footprint(int64_t nroots, const int64_t *root_m, const int64_t *root_n, int64_t count, const int32_t *root_of,
+                               const int64_t *koff, int32_t inplace, int64_t *out /* [2] */);
 
 /* Library / device probes (no compute): used by the loader checks and by __graft_entry__. */
 const char *gomilp_version(void);
