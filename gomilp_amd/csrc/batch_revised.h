@@ -113,7 +113,7 @@ void launch_rv_assemble(const RevLP *lps, int count, int n_max, hipStream_t s);
 // relaxation's root through ChildCol; the other kernels of a list are the same either way
 void launch_rv_init(RevLP *lps, int count, int inplace, hipStream_t s);
 // ck2 (launch_rv_setup / _pivot / _exchange / _dual_pivot): 0: the one-pass kernels with `lds` bytes, exactly the launches of a wave within
-// the LDS window; > 0: the chunked forms (*_ck), the staged vector streamed through LDS ck2 double2 at a time (a multiple of 256, at most
+// the LDS window; > 0: the chunked forms (CK = true), the staged vector streamed through LDS ck2 double2 at a time (a multiple of 256, at most
 // 4096: ck2 * sizeof(double2) bytes of dynamic LDS, never more than 64 KB) — the same values, whatever the chunk
 void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, int ck2, int inplace, hipStream_t s);   // forced pivot, lists, refresh, check: 7 launches
 void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int ck2, int inplace, hipStream_t s);       // Bland step?, K1, K2, K3: 4 launches

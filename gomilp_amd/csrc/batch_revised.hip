@@ -3,21 +3,22 @@
 // refreshes, the Bland rule, the zero-level artificial exchange, the verdicts) so that a wave costs a constant number of host round trips per superstep.
 //
 // The pivot rules, the per-element work and the commit are the helpers of simplex_helpers.h, the code the single-relaxation
-// kernels run: every dot product is one wave over one row (wave_dot_row), the argmins are first-index over per-workgroup
+// kernels run: every dot product is one wave over one row (wave_dot_chunk), the argmins are first-index over per-workgroup
 // partials, so a relaxation's values do not depend on the grid it gets or on the relaxations beside it.  Nothing is reduced
 // across relaxations and no kernel waits for another workgroup: kernels communicate across launch boundaries only.
 // Every field of a RevLP that a kernel reads was written by an earlier launch of the stream (RevLP::flips / flips_k2); the one
 // exception, RevLP::x_best in k_rv_exch, only saves work.
 //
-// Every kernel that stages an m-long vector in LDS comes in two forms, as in simplex_kernels.hip: one pass (the vector staged whole: rows
-// up to the 64 KB window) and the chunked form *_ck (the vector streamed through LDS ck2 double2 at a time: kernels_common.h dot_group /
-// stage_chunk; pool knob large_rows, or wherever the pool's row_chunk forces it).  The two forms of a pair differ in their staging and
-// row loops only, so a relaxation's values do not depend on the chunk size either.  The chunked loops run to workgroup-uniform bounds
-// (the relaxation's own m, nn and ld): every thread of a workgroup reaches every barrier.
+// Every kernel that stages an m-long vector in LDS is a template on CK, as in simplex_kernels.hip: CK = false is one pass (the vector
+// staged whole: rows up to the 64 KB window), CK = true the chunked form (the vector streamed through LDS ck2 double2 at a time; pool knob
+// large_rows, or wherever the pool's row_chunk forces it).  The two forms differ in their staging and row loops only, and those are
+// sweep_rows of kernels_common.h (update_rows of simplex_helpers.h for K3), so a relaxation's values do not depend on the chunk size
+// either.  The chunked loops run to workgroup-uniform bounds (the relaxation's own m, nn and ld): every thread of a workgroup reaches
+// every barrier.
 //
-// Every kernel that reads a child's column is a template on IP (pool knob rev_inplace): IP = false reads the At that k_rv_assemble wrote,
-// IP = true reads the column from the relaxation's root in place through ChildCol and the loader-templated helpers of rev_child_col.h —
-// the same arithmetic on synthesised values, so a relaxation's values do not depend on the mode either.
+// Every kernel that reads a child's column is a template on IP (pool knob rev_inplace), and IP only picks the loader (child_col):
+// IP = false reads the At that k_rv_assemble wrote (PlainCol), IP = true reads the column from the relaxation's root in place (ChildCol,
+// rev_child_col.h) — the same arithmetic on synthesised values, so a relaxation's values do not depend on the mode either.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -228,61 +229,15 @@ __global__ __launch_bounds__(kBlock) void k_rv_bland(RevLP *__restrict__ lps, co
     }
 }
 
+// column j of a relaxation's matrix as a loader: from its root in place (IP), or row j of the assembled At
 template <bool IP>
-__global__ __launch_bounds__(kBlock) void k_rv_price(RevLP *__restrict__ lps, const int *__restrict__ act) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ unsigned long long sk[kWavesPerBlock];
-    __shared__ unsigned int si[kWavesPerBlock];
-    __shared__ unsigned long long ss[1];
-    const RevLP *d = lps + act[blockIdx.y];
-    if (d->run != RR_LOOP || d->bl) return;
-    DevState *st = d->st;
-    if (!price_gate(st)) return;
-    const int ld = d->ld, nn = d->nn;
-    const double *At = d->At, *cost = d->cost, *y = d->y;
-    double *rvec = d->rvec;
-    const int32_t *nonbasic = d->nonbasic;
-    unsigned long long *pk = d->pk_price;
-    unsigned int *pi = d->pi_price;
-    const int ld2 = ld >> 1;
-    stage_vec(svec, y, ld2);
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    unsigned long long bk = ~0ull, b2 = ~0ull;
-    unsigned int bi = 0xFFFFFFFFu;
-    for (int pos = wave; pos < nn; pos += nwaves) {
-        const int j = nonbasic[pos];
-        if constexpr (IP) price_elem<false>(cost, rvec, pos, j, wave_dot_row_t(ChildCol(d, j), svec, ld2, lane), lane, bk, bi, b2);
-        else price_elem<false>(cost, rvec, pos, j, wave_dot_row(At + (size_t)j * ld, svec, ld2, lane), lane, bk, bi, b2);
-    }
-    publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
+__device__ __forceinline__ auto child_col(const RevLP *d, const double *At, int ld, int j) {
+    if constexpr (IP) return ChildCol(d, j);
+    else return PlainCol(At + (size_t)j * ld);
 }
 
-// the rows of a chunked group as ChildCols: row r = column rowmap[wave + (k0 + r) * nwaves] of the child, where that position is < rows
-__device__ __forceinline__ void child_rows(const RevLP *d, const int32_t *__restrict__ rowmap, int rows, int k0, int wave, int nwaves,
-                                           ChildCol (&col)[kCkRows], bool (&has)[kCkRows]) {
-#pragma unroll
-    for (int r = 0; r < kCkRows; r++) {
-        const int pos = wave + (k0 + r) * nwaves;
-        has[r] = pos < rows;
-        if (has[r]) col[r] = ChildCol(d, rowmap[pos]);
-    }
-}
-// the rows of a chunked group where they lie in memory: row r = row wave + (k0 + r) * nwaves of M
-__device__ __forceinline__ void plain_rows(const double *__restrict__ M, int ld, int rows, int k0, int wave, int nwaves, PlainCol (&row)[kCkRows],
-                                           bool (&has)[kCkRows]) {
-#pragma unroll
-    for (int r = 0; r < kCkRows; r++) {
-        const int pos = wave + (k0 + r) * nwaves;
-        has[r] = pos < rows;
-        row[r].p = reinterpret_cast<const double2 *>(M + (size_t)(has[r] ? pos : 0) * ld);
-    }
-}
-
-// the chunked form of k_rv_price (k_price_ck)
-template <bool IP>
-__global__ __launch_bounds__(kBlock) void k_rv_price_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
+template <bool IP, bool CK>
+__global__ __launch_bounds__(kBlock) void k_rv_price(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
@@ -300,31 +255,15 @@ __global__ __launch_bounds__(kBlock) void k_rv_price_ck(RevLP *__restrict__ lps,
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
-    const int kmax = (nn + nwaves - 1) / nwaves;
     unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows][1];
-        if constexpr (IP) {
-            ChildCol col[kCkRows];
-            bool has[kCkRows];
-            child_rows(d, nonbasic, nn, k0, wave, nwaves, col, has);
-            const PlainCol vy[1] = {{reinterpret_cast<const double2 *>(y)}};
-            dot_group_t<1>(col, has, ld, vy, svec, ck2, lane, dot);
-        } else {
-            dot_group<1>(At, ld, nonbasic, nn, k0, wave, nwaves, {y}, svec, ck2, lane, dot);
-        }
-#pragma unroll
-        for (int r = 0; r < kCkRows; r++) {
-            const int pos = wave + (k0 + r) * nwaves;
-            if (pos < nn) price_elem<false>(cost, rvec, pos, nonbasic[pos], dot[r][0], lane, bk, bi, b2);
-        }
-    }
+    sweep_rows<CK, 1>([&](int pos) { return child_col<IP>(d, At, ld, nonbasic[pos]); }, {PlainCol(y)}, nn, wave, nwaves, ld, svec, ck2, lane,
+                      [&](int pos, const double (&dot)[1]) { price_elem<false>(cost, rvec, pos, nonbasic[pos], dot[0], lane, bk, bi, b2); });
     publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
 }
 
-template <int MODE, bool IP>
-__global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_price) {
+template <int MODE, bool IP, bool CK>
+__global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_price, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
@@ -347,67 +286,13 @@ __global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, co
     int var;
     if (!pick_entering<false>(st, pkp, pip, nparts_price, rvec, nonbasic, tol, 0.0, forced_pos, forced_var, sk, si, ss, var)) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) d->flips_k2 = flips;   // K3 of this pivot reads the parity K2 worked on
-    const int ld2 = ld >> 1;
-    if constexpr (IP) stage_vec_t(svec, ChildCol(d, var), ld2);
-    else stage_vec(svec, At + (size_t)var * ld, ld2);
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
     unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
-    for (int i = wave; i < m; i += nwaves) ratio_elem<false>(xb, dvec, move, i, wave_dot_row(binv_cur + (size_t)i * ld, svec, ld2, lane), lane, bk, bi, b2);
-    publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
-}
-
-// the chunked form of k_rv_ftran (k_ftran_ck)
-template <int MODE, bool IP>
-__global__ __launch_bounds__(kBlock) void k_rv_ftran_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_price, int ck2) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ unsigned long long sk[kWavesPerBlock];
-    __shared__ unsigned int si[kWavesPerBlock];
-    __shared__ unsigned long long ss[1];
-    RevLP *d = lps + act[blockIdx.y];
-    if (d->run != MODE) return;
-    DevState *st = d->st;
-    const int m = d->m, ld = d->ld, flips = d->flips;
-    int forced_pos, forced_var;
-    if constexpr (MODE == RR_DUAL) { forced_pos = kDualPick; forced_var = -1; }
-    else { forced_pos = MODE == RR_FORCED ? d->f_pos : (d->bl ? d->bl_pos : -1); forced_var = MODE == RR_FORCED ? d->f_var : -1; }
-    const double tol = d->tol;
-    const double *At = d->At, *binv_cur = d->binv[flips & 1], *xb = d->xb;
-    double *rvec = d->rvec, *dvec = d->dvec, *move = d->move;
-    const int32_t *nonbasic = d->nonbasic;
-    const unsigned long long *pkp = d->pk_price;
-    const unsigned int *pip = d->pi_price;
-    unsigned long long *pk = d->pk_ratio;
-    unsigned int *pi = d->pi_ratio;
-    int var;
-    if (!pick_entering<false>(st, pkp, pip, nparts_price, rvec, nonbasic, tol, 0.0, forced_pos, forced_var, sk, si, ss, var)) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) d->flips_k2 = flips;   // K3 of this pivot reads the parity K2 worked on
-    const double *col = IP ? nullptr : At + (size_t)var * ld;
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    const int kmax = (m + nwaves - 1) / nwaves;
-    unsigned long long bk = ~0ull, b2 = ~0ull;
-    unsigned int bi = 0xFFFFFFFFu;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows][1];
-        if constexpr (IP) {
-            PlainCol row[kCkRows];
-            bool has[kCkRows];
-            plain_rows(binv_cur, ld, m, k0, wave, nwaves, row, has);
-            const ChildCol vcol[1] = {ChildCol(d, var)};
-            dot_group_t<1>(row, has, ld, vcol, svec, ck2, lane, dot);
-        } else {
-            dot_group<1>(binv_cur, ld, nullptr, m, k0, wave, nwaves, {col}, svec, ck2, lane, dot);
-        }
-#pragma unroll
-        for (int r = 0; r < kCkRows; r++) {
-            const int i = wave + (k0 + r) * nwaves;
-            if (i < m) ratio_elem<false>(xb, dvec, move, i, dot[r][0], lane, bk, bi, b2);
-        }
-    }
+    sweep_rows<CK, 1>([&](int i) { return PlainCol(binv_cur + (size_t)i * ld); }, {child_col<IP>(d, At, ld, var)}, m, wave, nwaves, ld, svec, ck2, lane,
+                      [&](int i, const double (&dot)[1]) { ratio_elem<false>(xb, dvec, move, i, dot[0], lane, bk, bi, b2); });
     publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
 }
 
@@ -432,8 +317,8 @@ __device__ __forceinline__ bool bland_leaving(DevState *st, const unsigned long 
     return true;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(kBlock) void k_rv_update(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_ratio) {
+template <int MODE, bool CK>
+__global__ __launch_bounds__(kBlock) void k_rv_update(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_ratio, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
@@ -458,68 +343,11 @@ __global__ __launch_bounds__(kBlock) void k_rv_update(RevLP *__restrict__ lps, c
         return;
     }
     const double dpv = dvec[p];
-    const int ld2 = ld >> 1;
-    stage_vec(svec, binv_cur + (size_t)p * ld, ld2);  // old row p
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    for (int i = wave; i < m; i += nwaves) update_row(binv_cur, binv_next, ld, dvec, i, p, dpv, svec, 0, ld2, lane);
-    if (blockIdx.x == 0) {
-        commit_pivot(st, xb, y, dvec, move, basic, nonbasic, nullptr, 0, phase, m, ld, p, dpv, reinterpret_cast<const double *>(svec), no_swap, bland);
-        if (threadIdx.x == 0) {
-            d->flips = flips + 1;
-            if (bland) d->bland += 1;
-        }
-    }
-}
-
-// the chunked form of k_rv_update (k_update_ck): elementwise, its chunks are only bounds; old row p is read where it lies for the commit
-// (binv_cur is only read here)
-template <int MODE>
-__global__ __launch_bounds__(kBlock) void k_rv_update_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_ratio, int ck2) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ unsigned long long sk[kWavesPerBlock];
-    __shared__ unsigned int si[kWavesPerBlock];
-    __shared__ unsigned long long ss[1];
-    RevLP *d = lps + act[blockIdx.y];
-    if (d->run != MODE) return;
-    DevState *st = d->st;
-    const int m = d->m, ld = d->ld, flips = d->flips_k2, phase = d->phase;
-    int forced_p, no_swap, bland;
-    if constexpr (MODE == RR_DUAL) { forced_p = kDualPick; no_swap = 0; bland = 0; }
-    else { forced_p = MODE == RR_FORCED ? d->f_p : -1; no_swap = MODE == RR_FORCED ? d->f_noswap : 0; bland = MODE == RR_FORCED ? 0 : d->bl; }
-    const double *binv_cur = d->binv[flips & 1];
-    double *binv_next = d->binv[(flips + 1) & 1];
-    double *xb = d->xb, *y = d->y, *dvec = d->dvec, *move = d->move;
-    int32_t *basic = d->basic, *nonbasic = d->nonbasic;
-    const unsigned long long *pk = d->pk_ratio;
-    const unsigned int *pi = d->pi_ratio;
-    int p;
-    if (bland) {
-        if (!bland_leaving(st, pk, pi, nparts_ratio, move, m, sk, si, p)) return;
-    } else if (!pick_leaving<false>(st, pk, pi, nparts_ratio, move, dvec, 0.0, forced_p, sk, si, ss, p)) {
-        return;
-    }
-    const double dpv = dvec[p];
-    const int ld2 = ld >> 1;
     const double *rowp_g = binv_cur + (size_t)p * ld;   // old row p
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    const int kmax = (m + nwaves - 1) / nwaves;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        for (int c0 = 0; c0 < ld2; c0 += ck2) {
-            const int c1 = min(c0 + ck2, ld2);
-            stage_chunk<1>(svec, ck2, {rowp_g}, c0, c1);
-#pragma unroll
-            for (int r = 0; r < kCkRows; r++) {
-                const int i = wave + (k0 + r) * nwaves;
-                if (i < m) update_row(binv_cur, binv_next, ld, dvec, i, p, dpv, svec, c0, c1, lane);
-            }
-        }
-    }
+    update_rows<CK>(binv_cur, binv_next, ld, dvec, m, p, dpv, rowp_g, svec, ck2);
     if (blockIdx.x == 0) {
-        commit_pivot(st, xb, y, dvec, move, basic, nonbasic, nullptr, 0, phase, m, ld, p, dpv, rowp_g, no_swap, bland);
+        commit_pivot(st, xb, y, dvec, move, basic, nonbasic, nullptr, 0, phase, m, ld, p, dpv, CK ? rowp_g : reinterpret_cast<const double *>(svec), no_swap,
+                     bland);
         if (threadIdx.x == 0) {
             d->flips = flips + 1;
             if (bland) d->bland += 1;
@@ -555,51 +383,11 @@ __global__ __launch_bounds__(kBlock) void k_rv_dual_leave(RevLP *__restrict__ lp
 }
 
 // dual pricing: per nonbasic column a_j.y and a_j.rho (rho = row p of B^-1), the row of At read once for both; r_pos = cost[j] - a_j.y
-// into rvec, the ratio r_j / -alpha_pj over alpha_pj < -1e-13 as a first-index argmin (k_dual_price's rule).  y and rho staged whole:
-// 2 * ld doubles of LDS, ld <= kRevDualLd.
-template <bool IP>
-__global__ __launch_bounds__(kBlock) void k_rv_dual_price(RevLP *__restrict__ lps, const int *__restrict__ act) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ unsigned long long sk[kWavesPerBlock];
-    __shared__ unsigned int si[kWavesPerBlock];
-    const RevLP *d = lps + act[blockIdx.y];
-    if (d->run != RR_DUAL) return;
-    const DevState *st = d->st;
-    if (st->done) return;
-    const int ld = d->ld, nn = d->nn;
-    const double *At = d->At, *cost = d->cost;
-    double *rvec = d->rvec;
-    const int32_t *nonbasic = d->nonbasic;
-    unsigned long long *pk = d->pk_price;
-    unsigned int *pi = d->pi_price;
-    const int ld2 = ld >> 1;
-    double2 *sy = svec, *sr = svec + ld2;
-    const double2 *y2 = reinterpret_cast<const double2 *>(d->y);
-    const double2 *rho2 = reinterpret_cast<const double2 *>(d->binv[d->flips & 1] + (size_t)st->p * ld);
-    for (int c = threadIdx.x; c < ld2; c += kBlock) { sy[c] = y2[c]; sr[c] = rho2[c]; }
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    unsigned long long bk = ~0ull;
-    unsigned int bi = 0xFFFFFFFFu;
-    for (int pos = wave; pos < nn; pos += nwaves) {
-        const int j = nonbasic[pos];
-        DotAcc acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-        if constexpr (IP) wave_dot_chunk_t<2>(ChildCol(d, j), svec, ld2, 0, ld2, ld2, lane, acc);
-        else wave_dot_chunk<2>(At + (size_t)j * ld, svec, ld2, 0, ld2, ld2, lane, acc);
-        const double dy = wave_dot_finish(acc[0]), da = wave_dot_finish(acc[1]);
-        const double r = cost[j] - dy;
-        if (lane == 0) rvec[pos] = r;
-        amin_take(bk, bi, ordkey(da < -1e-13 ? r / (-da) : __builtin_inf()), (unsigned int)pos);
-    }
-    publish_partials(bk, bi, sk, si, pk, pi);
-}
-
-// the chunked form of k_rv_dual_price (k_dual_price_ck): y and rho streamed through LDS ck2 double2 each at a time, ck2 <= kRevDualLd / 2
-// (2 * ck2 double2 of LDS: 64 KB at most)
-template <bool IP>
-__global__ __launch_bounds__(kBlock) void k_rv_dual_price_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
+// into rvec, the ratio r_j / -alpha_pj over alpha_pj < -1e-13 as a first-index argmin (k_dual_price's rule).  CK = false: y and rho staged
+// whole, 2 * ld doubles of LDS, ld <= kRevDualLd; CK = true: streamed ck2 double2 each at a time, ck2 <= kRevDualLd / 2 (2 * ck2 double2 of
+// LDS: 64 KB at most).
+template <bool IP, bool CK>
+__global__ __launch_bounds__(kBlock) void k_rv_dual_price(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
@@ -617,30 +405,14 @@ __global__ __launch_bounds__(kBlock) void k_rv_dual_price_ck(RevLP *__restrict__
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
-    const int kmax = (nn + nwaves - 1) / nwaves;
     unsigned long long bk = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows][2];
-        if constexpr (IP) {
-            ChildCol col[kCkRows];
-            bool has[kCkRows];
-            child_rows(d, nonbasic, nn, k0, wave, nwaves, col, has);
-            const PlainCol vyr[2] = {{reinterpret_cast<const double2 *>(y)}, {reinterpret_cast<const double2 *>(rho)}};
-            dot_group_t<2>(col, has, ld, vyr, svec, ck2, lane, dot);
-        } else {
-            dot_group<2>(At, ld, nonbasic, nn, k0, wave, nwaves, {y, rho}, svec, ck2, lane, dot);
-        }
-#pragma unroll
-        for (int r = 0; r < kCkRows; r++) {
-            const int pos = wave + (k0 + r) * nwaves;
-            if (pos < nn) {
-                const double rr = cost[nonbasic[pos]] - dot[r][0], da = dot[r][1];
-                if (lane == 0) rvec[pos] = rr;
-                amin_take(bk, bi, ordkey(da < -1e-13 ? rr / (-da) : __builtin_inf()), (unsigned int)pos);
-            }
-        }
-    }
+    sweep_rows<CK, 2>([&](int pos) { return child_col<IP>(d, At, ld, nonbasic[pos]); }, {PlainCol(y), PlainCol(rho)}, nn, wave, nwaves, ld, svec, ck2, lane,
+                      [&](int pos, const double (&dot)[2]) {
+                          const double r = cost[nonbasic[pos]] - dot[0], da = dot[1];
+                          if (lane == 0) rvec[pos] = r;
+                          amin_take(bk, bi, ordkey(da < -1e-13 ? r / (-da) : __builtin_inf()), (unsigned int)pos);
+                      });
     publish_partials(bk, bi, sk, si, pk, pi);
 }
 
@@ -680,26 +452,8 @@ __global__ __launch_bounds__(kBlock) void k_rv_lists(RevLP *__restrict__ lps, co
 }
 
 // x_B = B^-1 b (k_matvec_rows)
-__global__ __launch_bounds__(kBlock) void k_rv_matvec(RevLP *__restrict__ lps, const int *__restrict__ act) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    const RevLP *d = lps + act[blockIdx.y];
-    if (d->do_refresh != 1 || d->stage != RS_RUN) return;
-    const int m = d->m, ld = d->ld;
-    const double *M = d->binv[d->flips & 1], *vec = d->b;
-    double *out = d->xb;
-    const int ld2 = ld >> 1;
-    stage_vec(svec, vec, ld2);
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    for (int i = wave; i < m; i += nwaves) {
-        const double v = wave_dot_row(M + (size_t)i * ld, svec, ld2, lane);
-        if (lane == 0) out[i] = v;
-    }
-}
-
-// the chunked form of k_rv_matvec (k_matvec_rows_ck)
-__global__ __launch_bounds__(kBlock) void k_rv_matvec_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
+template <bool CK>
+__global__ __launch_bounds__(kBlock) void k_rv_matvec(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     const RevLP *d = lps + act[blockIdx.y];
     if (d->do_refresh != 1 || d->stage != RS_RUN) return;
@@ -709,16 +463,8 @@ __global__ __launch_bounds__(kBlock) void k_rv_matvec_ck(RevLP *__restrict__ lps
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
-    const int kmax = (m + nwaves - 1) / nwaves;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows][1];
-        dot_group<1>(M, ld, nullptr, m, k0, wave, nwaves, {vec}, svec, ck2, lane, dot);
-#pragma unroll
-        for (int r = 0; r < kCkRows; r++) {
-            const int i = wave + (k0 + r) * nwaves;
-            if (i < m && lane == 0) out[i] = dot[r][0];
-        }
-    }
+    sweep_rows<CK, 1>([&](int i) { return PlainCol(M + (size_t)i * ld); }, {PlainCol(vec)}, m, wave, nwaves, ld, svec, ck2, lane,
+                      [&](int i, const double (&dot)[1]) { if (lane == 0) out[i] = dot[0]; });
 }
 
 // y = B^-T c_B in the arithmetic of k_y_partial / k_y_reduce (the chunking of launch_y_from_binv for this relaxation's m);
@@ -883,8 +629,8 @@ __global__ __launch_bounds__(kBlock) void k_rv_ctrl(RevLP *__restrict__ lps, con
 // happens to see ends early.  That changes the work done, never the minimum.
 // Dynamic LDS: ld doubles, as K2.  grid: (nonbasic positions of the widest relaxation, list positions).
 // ------------------------------------------------------------------------------------------------
-template <bool IP>
-__global__ __launch_bounds__(kBlock) void k_rv_exch(RevLP *__restrict__ lps, const int *__restrict__ act) {
+template <bool IP, bool CK>
+__global__ __launch_bounds__(kBlock) void k_rv_exch(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ double smax[kWavesPerBlock];
     RevLP *d = lps + act[blockIdx.y];
@@ -898,88 +644,31 @@ __global__ __launch_bounds__(kBlock) void k_rv_exch(RevLP *__restrict__ lps, con
     __syncthreads();
     if (seen < (unsigned int)j) return;   // (workgroup-uniform)
     const double *binv_cur = d->binv[d->flips & 1], *xb = d->xb;
-    const int ld2 = ld >> 1;
-    if constexpr (IP) stage_vec_t(svec, ChildCol(d, j), ld2);
-    else stage_vec(svec, d->At + (size_t)j * ld, ld2);
+    const auto col = child_col<IP>(d, d->At, ld, j);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const double dpv = wave_dot_row(binv_cur + (size_t)added * ld, svec, ld2, lane);   // (every wave: the same bits, workgroup-uniform)
-    if (!(fabs(dpv) > 1e-9)) return;
-    const double theta = xb[added] / dpv;
-    double dmax = 0;
-    int bad = 0;
-    for (int i = w; i < m; i += kWavesPerBlock) {
-        const double di = wave_dot_row(binv_cur + (size_t)i * ld, svec, ld2, lane);
-        const double a = fabs(di);
-        if (dmax < a) dmax = a;
-        const double v = (i == added) ? theta : xb[i] - theta * di;
-        if (v < -1e-13) bad = 1;
-    }
-    if (lane == 0) smax[w] = dmax;
-    bad = __syncthreads_or(bad);
-    if (threadIdx.x != 0 || bad) return;
-#pragma unroll
-    for (int t = 0; t < kWavesPerBlock; t++) if (dmax < smax[t]) dmax = smax[t];
-    if (!(fabs(dpv) > 1e-9 * (1.0 < dmax ? dmax : 1.0))) return;
-    atomicMin(&d->x_best, (unsigned int)j);
-}
-
-// the chunked form of k_rv_exch: a_j streamed through LDS ck2 double2 at a time.  d_added first, as one row's chunked dot by every wave
-// (the same bits in each); a candidate that fails there costs one row.  The other rows kCkRows per wave at a time (dot_group with the
-// workgroup's own kWavesPerBlock waves: row i = w, w + 4, ... as the one-pass loop takes them).
-template <bool IP>
-__global__ __launch_bounds__(kBlock) void k_rv_exch_ck(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ double smax[kWavesPerBlock];
-    RevLP *d = lps + act[blockIdx.y];
-    if (d->run != RR_EXCH) return;
-    const int m = d->m, n = d->n, ld = d->ld, added = d->x_added, pos = blockIdx.x;
-    if (pos >= d->nn) return;
-    const int j = d->nonbasic[pos];
-    if (j < 0 || j >= n) return;   // (row n of At is the artificial: never a candidate)
-    __shared__ unsigned int seen;
-    if (threadIdx.x == 0) seen = __atomic_load_n(&d->x_best, __ATOMIC_RELAXED);
-    __syncthreads();
-    if (seen < (unsigned int)j) return;   // (workgroup-uniform)
-    const double *binv_cur = d->binv[d->flips & 1], *xb = d->xb;
-    const double *col = IP ? nullptr : d->At + (size_t)j * ld;
-    const ChildCol vcol[1] = {IP ? ChildCol(d, j) : ChildCol()};
-    const int ld2 = ld >> 1;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // d_added first, as one row's chunked dot by every wave (the same bits in each, workgroup-uniform; CK = false: the one chunk [0, ld2))
+    const int ld2 = ld >> 1, cb = CK ? ck2 : ld2;
     DotAcc acc[1] = {{0, 0, 0, 0}};
-    for (int c0 = 0; c0 < ld2; c0 += ck2) {
-        const int c1 = min(c0 + ck2, ld2);
-        if constexpr (IP) stage_chunk_t<1>(svec, ck2, vcol, c0, c1);
-        else stage_chunk<1>(svec, ck2, {col}, c0, c1);
-        wave_dot_chunk<1>(binv_cur + (size_t)added * ld, svec, ck2, c0, c1, ld2, lane, acc);
+    for (int c0 = 0; c0 < ld2; c0 += cb) {
+        const int c1 = min(c0 + cb, ld2);
+        stage_chunk<1>(svec, cb, {col}, c0, c1);
+        wave_dot_chunk<1>(PlainCol(binv_cur + (size_t)added * ld), svec, cb, c0, c1, ld2, lane, acc);
     }
-    const double dpv = wave_dot_finish(acc[0]);   // (every wave: the same bits, workgroup-uniform)
+    const double dpv = wave_dot_finish(acc[0]);
     if (!(fabs(dpv) > 1e-9)) return;
     const double theta = xb[added] / dpv;
     double dmax = 0;
     int bad = 0;
-    const int kmax = (m + kWavesPerBlock - 1) / kWavesPerBlock;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows][1];
-        if constexpr (IP) {
-            PlainCol row[kCkRows];
-            bool has[kCkRows];
-            plain_rows(binv_cur, ld, m, k0, w, kWavesPerBlock, row, has);
-            dot_group_t<1>(row, has, ld, vcol, svec, ck2, lane, dot);
-        } else {
-            dot_group<1>(binv_cur, ld, nullptr, m, k0, w, kWavesPerBlock, {col}, svec, ck2, lane, dot);
-        }
-#pragma unroll
-        for (int r = 0; r < kCkRows; r++) {
-            const int i = w + (k0 + r) * kWavesPerBlock;
-            if (i < m) {
-                const double di = dot[r][0];
-                const double a = fabs(di);
-                if (dmax < a) dmax = a;
-                const double v = (i == added) ? theta : xb[i] - theta * di;
-                if (v < -1e-13) bad = 1;
-            }
-        }
-    }
+    if constexpr (!CK) __syncthreads();   // (the sweep stages a_j again: no wave reads svec any more)
+    // the rows by the workgroup's own kWavesPerBlock waves: row i = w, w + 4, ...
+    sweep_rows<CK, 1>([&](int i) { return PlainCol(binv_cur + (size_t)i * ld); }, {col}, m, w, kWavesPerBlock, ld, svec, ck2, lane,
+                      [&](int i, const double (&dot)[1]) {
+                          const double di = dot[0];
+                          const double a = fabs(di);
+                          if (dmax < a) dmax = a;
+                          const double v = (i == added) ? theta : xb[i] - theta * di;
+                          if (v < -1e-13) bad = 1;
+                      });
     if (lane == 0) smax[w] = dmax;
     bad = __syncthreads_or(bad);
     if (threadIdx.x != 0 || bad) return;
@@ -1017,60 +706,50 @@ void launch_rv_assemble(const RevLP *lps, int count, int n_max, hipStream_t s) {
 void launch_rv_init(RevLP *lps, int count, int inplace, hipStream_t s) {
     hipLaunchKernelGGL(inplace ? k_rv_init<true> : k_rv_init<false>, dim3(count), dim3(kBlock), 0, s, lps);
 }
-// (ck2 > 0: the chunked forms, ck2 double2 of dynamic LDS; 0: the one-pass forms with `lds` bytes)
+// (ck2 > 0: the CK = true instances, ck2 double2 of dynamic LDS; 0: the one-pass instances with `lds` bytes)
+static size_t rv_lds(size_t lds, int ck2) { return ck2 > 0 ? (size_t)ck2 * sizeof(double2) : lds; }
+
+// K2 and K3 of one pivot of MODE (nparts_price: the workgroups of the pricing launch in front, 0: none)
+template <int MODE>
+static void launch_rv_k23(RevLP *lps, const int *act, int nact, int gr, int nparts_price, size_t lds, int ck2, int inplace, hipStream_t s) {
+    const auto k2 = ck2 > 0 ? (inplace ? k_rv_ftran<MODE, true, true> : k_rv_ftran<MODE, false, true>)
+                            : (inplace ? k_rv_ftran<MODE, true, false> : k_rv_ftran<MODE, false, false>);
+    hipLaunchKernelGGL(k2, dim3(gr, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, nparts_price, ck2);
+    hipLaunchKernelGGL((ck2 > 0 ? k_rv_update<MODE, true> : k_rv_update<MODE, false>), dim3(gr, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, gr, ck2);
+}
 void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, int ck2, int inplace, hipStream_t s) {
-    const size_t ldc = (size_t)ck2 * sizeof(double2);
-    if (ck2 > 0) {
-        hipLaunchKernelGGL((inplace ? k_rv_ftran_ck<RR_FORCED, true> : k_rv_ftran_ck<RR_FORCED, false>), dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, 0, ck2);
-        hipLaunchKernelGGL(k_rv_update_ck<RR_FORCED>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gr, ck2);
-    } else {
-        hipLaunchKernelGGL((inplace ? k_rv_ftran<RR_FORCED, true> : k_rv_ftran<RR_FORCED, false>), dim3(gr, nact), dim3(kBlock), lds, s, lps, act, 0);
-        hipLaunchKernelGGL(k_rv_update<RR_FORCED>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
-    }
+    launch_rv_k23<RR_FORCED>(lps, act, nact, gr, 0, lds, ck2, inplace, s);
     hipLaunchKernelGGL(k_rv_lists, dim3(nact), dim3(kBlock), 0, s, lps, act);
-    if (ck2 > 0) hipLaunchKernelGGL(k_rv_matvec_ck, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, ck2);
-    else hipLaunchKernelGGL(k_rv_matvec, dim3(gr, nact), dim3(kBlock), lds, s, lps, act);
+    hipLaunchKernelGGL((ck2 > 0 ? k_rv_matvec<true> : k_rv_matvec<false>), dim3(gr, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, ck2);
     hipLaunchKernelGGL(k_rv_y_partial, dim3((ld_max + kBlock - 1) / kBlock, 64, nact), dim3(kBlock), 0, s, lps, act);
     hipLaunchKernelGGL(k_rv_y_reduce, dim3((ld_max + kBlock - 1) / kBlock, nact), dim3(kBlock), 0, s, lps, act);
     hipLaunchKernelGGL(k_rv_check, dim3(nact), dim3(kBlock), 0, s, lps, act);
 }
 void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int ck2, int inplace, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_bland, dim3(nact), dim3(kBlock), 0, s, lps, act);
-    if (ck2 > 0) {
-        const size_t ldc = (size_t)ck2 * sizeof(double2);
-        hipLaunchKernelGGL(inplace ? k_rv_price_ck<true> : k_rv_price_ck<false>, dim3(gp, nact), dim3(kBlock), ldc, s, lps, act, ck2);
-        hipLaunchKernelGGL((inplace ? k_rv_ftran_ck<RR_LOOP, true> : k_rv_ftran_ck<RR_LOOP, false>), dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gp, ck2);
-        hipLaunchKernelGGL(k_rv_update_ck<RR_LOOP>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gr, ck2);
-        return;
-    }
-    hipLaunchKernelGGL(inplace ? k_rv_price<true> : k_rv_price<false>, dim3(gp, nact), dim3(kBlock), lds, s, lps, act);
-    hipLaunchKernelGGL((inplace ? k_rv_ftran<RR_LOOP, true> : k_rv_ftran<RR_LOOP, false>), dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp);
-    hipLaunchKernelGGL(k_rv_update<RR_LOOP>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
+    const auto k1 = ck2 > 0 ? (inplace ? k_rv_price<true, true> : k_rv_price<false, true>) : (inplace ? k_rv_price<true, false> : k_rv_price<false, false>);
+    hipLaunchKernelGGL(k1, dim3(gp, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, ck2);
+    launch_rv_k23<RR_LOOP>(lps, act, nact, gr, gp, lds, ck2, inplace, s);
 }
 void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_ctrl, dim3(nact), dim3(kBlock), 0, s, lps, act, out);
 }
 void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, int ck2, int inplace, hipStream_t s) {
-    if (ck2 > 0) hipLaunchKernelGGL(inplace ? k_rv_exch_ck<true> : k_rv_exch_ck<false>, dim3(nn_max, nact), dim3(kBlock), (size_t)ck2 * sizeof(double2), s, lps, act, ck2);
-    else hipLaunchKernelGGL(inplace ? k_rv_exch<true> : k_rv_exch<false>, dim3(nn_max, nact), dim3(kBlock), lds, s, lps, act);
+    const auto kx = ck2 > 0 ? (inplace ? k_rv_exch<true, true> : k_rv_exch<false, true>) : (inplace ? k_rv_exch<true, false> : k_rv_exch<false, false>);
+    hipLaunchKernelGGL(kx, dim3(nn_max, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, ck2);
     hipLaunchKernelGGL(k_rv_exch_pick, dim3(nact), dim3(64), 0, s, lps, act);
 }
 void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_warm_binv, dim3(m_max, count), dim3(kBlock), 0, s, lps);
 }
-// (ck2d > 0: the chunked pricing kernel, its TWO vectors ck2d double2 each; ck2: K2 / K3 as in launch_rv_pivot)
+// (ck2d > 0: the CK = true pricing kernel, its TWO vectors ck2d double2 each, else the one-pass one with lds2 bytes; ck2: K2 / K3 as in
+// launch_rv_pivot)
 void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, int ck2, int ck2d, int inplace, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_dual_leave, dim3(nact), dim3(kBlock), 0, s, lps, act);
-    if (ck2d > 0) hipLaunchKernelGGL(inplace ? k_rv_dual_price_ck<true> : k_rv_dual_price_ck<false>, dim3(gp, nact), dim3(kBlock), (size_t)2 * ck2d * sizeof(double2), s, lps, act, ck2d);
-    else hipLaunchKernelGGL(inplace ? k_rv_dual_price<true> : k_rv_dual_price<false>, dim3(gp, nact), dim3(kBlock), lds2, s, lps, act);
-    if (ck2 > 0) {
-        const size_t ldc = (size_t)ck2 * sizeof(double2);
-        hipLaunchKernelGGL((inplace ? k_rv_ftran_ck<RR_DUAL, true> : k_rv_ftran_ck<RR_DUAL, false>), dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gp, ck2);
-        hipLaunchKernelGGL(k_rv_update_ck<RR_DUAL>, dim3(gr, nact), dim3(kBlock), ldc, s, lps, act, gr, ck2);
-        return;
-    }
-    hipLaunchKernelGGL((inplace ? k_rv_ftran<RR_DUAL, true> : k_rv_ftran<RR_DUAL, false>), dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp);
-    hipLaunchKernelGGL(k_rv_update<RR_DUAL>, dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr);
+    const auto k1 = ck2d > 0 ? (inplace ? k_rv_dual_price<true, true> : k_rv_dual_price<false, true>)
+                             : (inplace ? k_rv_dual_price<true, false> : k_rv_dual_price<false, false>);
+    hipLaunchKernelGGL(k1, dim3(gp, nact), dim3(kBlock), rv_lds(lds2, 2 * ck2d), s, lps, act, ck2d);
+    launch_rv_k23<RR_DUAL>(lps, act, nact, gr, gp, lds, ck2, inplace, s);
 }
 
 }  // namespace gomilp

@@ -38,8 +38,9 @@ __global__ __launch_bounds__(kBlock) void k_dual_leave(const double *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
-// dual pricing: per nonbasic column a_j.y and a_j.rho, the row of At read once for both (kernels_common.h: wave_dot_chunk<2>),
-// so the one-pass form (one chunk [0, ld2)) and the chunked form (dot_group<2>) agree bit for bit.
+// dual pricing: per nonbasic column a_j.y and a_j.rho, the row of At read once for both (kernels_common.h: sweep_rows with two
+// vectors).  CK = false: y and rho staged whole (2 * ld doubles of LDS: ld <= 4096); CK = true: streamed through LDS ck2 double2
+// each at a time.  The two forms agree bit for bit.
 // ------------------------------------------------------------------------------------------------
 
 // r_pos = cost[j] - a_j.y (kept in rvec for k_ftran / k_update), the ratio key of column pos
@@ -49,34 +50,8 @@ __device__ __forceinline__ unsigned long long dual_key(const LPArgs &a, int pos,
     return ordkey(da < -1e-13 ? r / (-da) : __builtin_inf());
 }
 
-// one-pass form: y and rho staged whole (2 * ld doubles of LDS: ld <= 4096)
-__global__ __launch_bounds__(kBlock) void k_dual_price(LPArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ unsigned long long sk[kWavesPerBlock];
-    __shared__ unsigned int si[kWavesPerBlock];
-    DevState *st = a.st;
-    if (st->done) return;
-    const int ld2 = a.ld >> 1;
-    double2 *sy = svec, *sr = svec + ld2;
-    const double2 *y2 = reinterpret_cast<const double2 *>(a.y);
-    const double2 *rho2 = reinterpret_cast<const double2 *>(a.binv_cur + (size_t)st->p * a.ld);
-    for (int c = threadIdx.x; c < ld2; c += kBlock) { sy[c] = y2[c]; sr[c] = rho2[c]; }
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    unsigned long long bk = ~0ull;
-    unsigned int bi = 0xFFFFFFFFu;
-    for (int pos = wave; pos < a.nn; pos += nwaves) {
-        DotAcc acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-        wave_dot_chunk<2>(a.At + (size_t)a.nonbasic[pos] * a.ld, svec, ld2, 0, ld2, ld2, lane, acc);
-        amin_take(bk, bi, dual_key(a, pos, wave_dot_finish(acc[0]), wave_dot_finish(acc[1]), lane), (unsigned int)pos);
-    }
-    publish_partials(bk, bi, sk, si, a.pk_price, a.pi_price);
-}
-
-// chunked form: y and rho streamed through LDS ck2 double2 each at a time
-__global__ __launch_bounds__(kBlock) void k_dual_price_ck(LPArgs a, int ck2) {
+template <bool CK>
+__global__ __launch_bounds__(kBlock) void k_dual_price(LPArgs a, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
@@ -86,18 +61,10 @@ __global__ __launch_bounds__(kBlock) void k_dual_price_ck(LPArgs a, int ck2) {
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
-    const int kmax = (a.nn + nwaves - 1) / nwaves;
     unsigned long long bk = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows][2];
-        dot_group<2>(a.At, a.ld, a.nonbasic, a.nn, k0, wave, nwaves, {a.y, rho}, svec, ck2, lane, dot);
-#pragma unroll
-        for (int r = 0; r < kCkRows; r++) {
-            const int pos = wave + (k0 + r) * nwaves;
-            if (pos < a.nn) amin_take(bk, bi, dual_key(a, pos, dot[r][0], dot[r][1], lane), (unsigned int)pos);
-        }
-    }
+    sweep_rows<CK, 2>([&](int pos) { return PlainCol(a.At + (size_t)a.nonbasic[pos] * a.ld); }, {PlainCol(a.y), PlainCol(rho)}, a.nn, wave, nwaves, a.ld, svec,
+                      ck2, lane, [&](int pos, const double (&dot)[2]) { amin_take(bk, bi, dual_key(a, pos, dot[0], dot[1], lane), (unsigned int)pos); });
     publish_partials(bk, bi, sk, si, a.pk_price, a.pi_price);
 }
 
@@ -151,10 +118,10 @@ int launch_dual_price(const LPArgs &a, hipStream_t s) {
     const int g = grid_for_rows(a.nn);
     // one pass while both vectors fit the 64 KB window; else (and whenever the row_chunk knob forces it) the chunked form
     if (a.row_chunk2 == 0 && a.ld <= kDualOnePassLd) {
-        hipLaunchKernelGGL(k_dual_price, dim3(g), dim3(kBlock), (size_t)2 * a.ld * sizeof(double), s, a);
+        hipLaunchKernelGGL(k_dual_price<false>, dim3(g), dim3(kBlock), (size_t)2 * a.ld * sizeof(double), s, a, 0);
     } else {
         const int ck2 = (a.row_chunk2 > 0 && a.row_chunk2 < kDualOnePassLd / 2) ? a.row_chunk2 : kDualOnePassLd / 2;
-        hipLaunchKernelGGL(k_dual_price_ck, dim3(g), dim3(kBlock), (size_t)2 * ck2 * sizeof(double2), s, a, ck2);
+        hipLaunchKernelGGL(k_dual_price<true>, dim3(g), dim3(kBlock), (size_t)2 * ck2 * sizeof(double2), s, a, ck2);
     }
     return g;
 }

@@ -124,7 +124,7 @@ int Engine::set(const std::string &key, int64_t v) {
     else if (key == "exact_degenerate") { if (v < 0 || v > 3) return GOMILP_ERR_BAD_SHAPE; exact_degenerate_ = v; }   // 3: strict — EVERY pivot decided on fresh gonum-order solves (engine_tableau.cpp exact_step)
     else if (key == "cond_guard") cond_guard_ = v ? 1 : 0;
     else if (key == "poll_delay") { if (v < 0 || v > 64) return GOMILP_ERR_BAD_SHAPE; poll_delay_ = v; }
-    else if (key == "row_chunk") { if (v < 0 || v % 512 != 0 || v > kLdsWindowLd) return GOMILP_ERR_BAD_SHAPE; row_chunk_ = v; }   // (whole 256-double2 steps of wave_dot_row)
+    else if (key == "row_chunk") { if (v < 0 || v % 512 != 0 || v > kLdsWindowLd) return GOMILP_ERR_BAD_SHAPE; row_chunk_ = v; }   // (whole 256-double2 steps of wave_dot_chunk)
     else return GOMILP_ERR_BAD_SHAPE;
     return GOMILP_OK;
 }

@@ -46,7 +46,7 @@ class RevBatchEngine {
     // (1e-13 < |x_art| < 1e-11) is BS_HOST either way: its verdict needs a fresh gonum-order solve.
     void set_exchange(bool on) { exchange_ = on; }
 
-    // pool knobs large_rows / row_chunk: with large_rows the kernels that stage an m-long vector run in their chunked forms (*_ck of
+    // pool knobs large_rows / row_chunk: with large_rows the kernels that stage an m-long vector run in their chunked forms (CK = true of
     // batch_revised.hip) — row_chunk doubles at a time where the pool set it (any row count), else kAutoRowChunk beyond the LDS window —
     // and warm starts are not limited to kRevDualLd.  Bit-identical to the one-pass forms.  Off (default): row_chunk is not looked at.
     void set_large_rows(bool on, int64_t row_chunk) { large_rows_ = on; row_chunk_ = row_chunk; }

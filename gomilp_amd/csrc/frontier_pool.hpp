@@ -42,7 +42,7 @@ struct PoolKnobs {
     int64_t refresh = 0;        // the workers' knob of this name: a periodic refresh stays on the workers
     int large_rows = 0;         // (opt-in) roots and children beyond the 64 KB LDS window (ld > 8192): the workers accept what a context accepts
                                 // there (slack-basis roots that fit the device memory), and wide waves of such relaxations run on the batched
-                                // revised simplex in its chunked kernels (batch_revised.hip: *_ck); warm starts of that schedule are no longer
+                                // revised simplex in its chunked kernels (batch_revised.hip: the CK = true instances); warm starts of that schedule are no longer
                                 // limited to 4096 rows.  0: pools keep the row limit of one-pass LDS staging
     // ---- kept and handed on (BatchEngine: gomilp_pool::apply_knobs; RevBatchEngine: per run)
     int rev_exchange = 1;       // on the batched revised simplex a relaxation whose Phase I ends with the artificial basic at level zero

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void k_price_fused(LPArgs a, const double *
         }
         __syncthreads();
     } else {
-        stage_vec(svec, y_in, ld2);
+        stage_vec<1>(svec, {PlainCol(y_in)}, ld2);
     }
     unsigned long long bk = ~0ull;
     unsigned int bi = 0xFFFFFFFFu, bv = 0;

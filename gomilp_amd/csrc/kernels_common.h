@@ -311,32 +311,35 @@ __device__ __forceinline__ size_t tab_idx(int i, int j, int ldt, int tiled) {
                  : (size_t)i * ldt + j;
 }
 
-__device__ __forceinline__ void stage_vec(double2 *__restrict__ svec, const double *__restrict__ src, int ld2) {
-    const double2 *s2 = reinterpret_cast<const double2 *>(src);
-    for (int c = threadIdx.x; c < ld2; c += kBlock) svec[c] = s2[c];
-    __syncthreads();
-}
+// ------------------------------------------------------------------------------------------------
+// Row dot products against LDS-staged vectors.  Rows and vectors come through loaders: load2(c) gives double2 c of a padded row
+// (ld2 double2, 16-byte aligned) — PlainCol where the row lies in memory, ChildCol (rev_child_col.h) where it is synthesised.
+// One pass stages the whole vector; the chunked form (vectors longer than the LDS window) stages it in chunks of
+// ck2 double2 (a multiple of 256) and carries the four accumulators of wave_dot_chunk from chunk to chunk.  A chunk [c0, c1)
+// that is not the last one holds whole 256-wide steps of the main loop, so every lane adds the same terms into the same
+// accumulator in the same order as one pass over [0, ld2): the result is bit-identical.
+// ------------------------------------------------------------------------------------------------
 
-// ------------------------------------------------------------------------------------------------
-// Row dot products against LDS-staged vectors.  One pass stages the whole vector; the chunked form (vectors longer than the
-// LDS window) stages it in chunks of ck2 double2 (a multiple of 256) and carries the four accumulators of
-// wave_dot_chunk from chunk to chunk.  A chunk [c0, c1) that is not the last one holds whole 256-wide steps of the main
-// loop, so every lane adds the same terms into the same accumulator in the same order as one pass over [0, ld2): the
-// result is bit-identical.
-// ------------------------------------------------------------------------------------------------
+// a padded row that lies in memory (rows of At and B^-1, the vectors y / rho / b)
+struct PlainCol {
+    const double2 *p;
+    __host__ __device__ __forceinline__ PlainCol() : p(nullptr) {}   // (the slot of a row a group does not have)
+    __host__ __device__ __forceinline__ explicit PlainCol(const double *row) : p(reinterpret_cast<const double2 *>(row)) {}
+    __host__ __device__ __forceinline__ double2 load2(int c) const { return p[c]; }
+};
+
 struct DotAcc {
     double a0, a1, a2, a3;
 };
 
-// the part of the dots of one padded row (ld2 double2, 16-byte aligned) with NV staged vectors that falls into the chunk
-// [c0, c1): vector v at svec + v * sstride, element c0 at offset 0.  The row is read once for all NV vectors.
-template <int NV>
-__device__ __forceinline__ void wave_dot_chunk(const double *__restrict__ row, const double2 *__restrict__ svec, int sstride, int c0,
-                                               int c1, int ld2, int lane, DotAcc (&acc)[NV]) {
-    const double2 *r2 = reinterpret_cast<const double2 *>(row);
+// the part of the dots of one row with NV staged vectors that falls into the chunk [c0, c1): vector v at svec + v * sstride,
+// element c0 at offset 0.  The row is read once for all NV vectors.
+template <int NV, class Row>
+__device__ __forceinline__ void wave_dot_chunk(const Row &row, const double2 *__restrict__ svec, int sstride, int c0, int c1, int ld2, int lane,
+                                               DotAcc (&acc)[NV]) {
     int c = c0 + lane;
     for (; c + 192 < c1; c += 256) {
-        const double2 v0 = r2[c], v1 = r2[c + 64], v2 = r2[c + 128], v3 = r2[c + 192];
+        const double2 v0 = row.load2(c), v1 = row.load2(c + 64), v2 = row.load2(c + 128), v3 = row.load2(c + 192);
 #pragma unroll
         for (int v = 0; v < NV; v++) {
             const double2 *s = svec + v * sstride + (c - c0);
@@ -349,7 +352,7 @@ __device__ __forceinline__ void wave_dot_chunk(const double *__restrict__ row, c
     }
     if (c1 == ld2) {   // the last chunk: the tail
         for (; c < ld2; c += 64) {
-            const double2 v0 = r2[c];
+            const double2 v0 = row.load2(c);
 #pragma unroll
             for (int v = 0; v < NV; v++) {
                 const double2 s0 = svec[v * sstride + (c - c0)];
@@ -361,60 +364,95 @@ __device__ __forceinline__ void wave_dot_chunk(const double *__restrict__ row, c
 
 __device__ __forceinline__ double wave_dot_finish(const DotAcc &acc) { return wave_sum((acc.a0 + acc.a1) + (acc.a2 + acc.a3)); }
 
-// dot of one padded row (ld doubles, 16-byte aligned) with the whole LDS-staged vector; result in all lanes
-__device__ __forceinline__ double wave_dot_row(const double *__restrict__ row, const double2 *__restrict__ svec, int ld2, int lane) {
-    DotAcc acc[1] = {{0, 0, 0, 0}};
-    wave_dot_chunk<1>(row, svec, 0, 0, ld2, ld2, lane, acc);
-    return wave_dot_finish(acc[0]);
+// NV vectors whole into LDS, ld2 double2 apart; one barrier behind
+template <int NV, class Vec>
+__device__ __forceinline__ void stage_vec(double2 *__restrict__ svec, const Vec (&src)[NV], int ld2) {
+    for (int c = threadIdx.x; c < ld2; c += kBlock) {
+#pragma unroll
+        for (int v = 0; v < NV; v++) svec[v * ld2 + c] = src[v].load2(c);
+    }
+    __syncthreads();
 }
 
 // chunk [c0, c1) of NV vectors into LDS (vector v at svec + v * sstride).  Every thread of the workgroup: a barrier in front, so
 // that the previous chunk is no longer read, and one behind.
-template <int NV>
-__device__ __forceinline__ void stage_chunk(double2 *__restrict__ svec, int sstride, const double *const (&src)[NV], int c0, int c1) {
-    const double2 *s2[NV];
-#pragma unroll
-    for (int v = 0; v < NV; v++) s2[v] = reinterpret_cast<const double2 *>(src[v]) + c0;
+template <int NV, class Vec>
+__device__ __forceinline__ void stage_chunk(double2 *__restrict__ svec, int sstride, const Vec (&src)[NV], int c0, int c1) {
     __syncthreads();
     for (int c = threadIdx.x; c < c1 - c0; c += kBlock) {
 #pragma unroll
-        for (int v = 0; v < NV; v++) svec[v * sstride + c] = s2[v][c];
+        for (int v = 0; v < NV; v++) svec[v * sstride + c] = src[v].load2(c0 + c);
     }
     __syncthreads();
 }
 
-// The chunked kernels take a wave's rows (wave, wave + nwaves, ... as the one-pass kernels do) kCkRows at a time, and the
-// workgroup streams the vectors through LDS once per such group; the loops run to a workgroup-uniform bound, so every thread
-// reaches every barrier.
+// The chunked kernels take a wave's rows kCkRows at a time, and the workgroup streams the vectors through LDS once per such group.
 constexpr int kCkRows = 4;
 
-// one group of up to kCkRows rows of a wave: dot[r][v] = M[row(r), :] . vec[v], valid where row(r) < rows (row(r) = rowmap[pos],
-// or pos without a rowmap); the NV vectors are staged ck2 double2 apart
-template <int NV>
-__device__ __forceinline__ void dot_group(const double *__restrict__ M, int ld, const int32_t *__restrict__ rowmap, int rows, int k0,
-                                          int wave, int nwaves, const double *const (&vec)[NV], double2 *svec, int ck2, int lane,
-                                          double (&dot)[kCkRows][NV]) {
+// one group of up to kCkRows rows: dot[r][v] = rows[r] . vec[v], valid where has[r]; the NV vectors are staged ck2 double2 apart.
+// Every thread of the workgroup (stage_chunk's barriers).
+template <int NV, class Row, class Vec>
+__device__ __forceinline__ void dot_group(const Row (&rows)[kCkRows], const bool (&has)[kCkRows], int ld, const Vec (&vec)[NV], double2 *svec,
+                                          int ck2, int lane, double (&dot)[kCkRows][NV]) {
     const int ld2 = ld >> 1;
-    const double *rowp[kCkRows];
     DotAcc acc[kCkRows][NV];
 #pragma unroll
-    for (int r = 0; r < kCkRows; r++) {
-        const int pos = wave + (k0 + r) * nwaves;
-        rowp[r] = pos < rows ? M + (size_t)(rowmap ? rowmap[pos] : pos) * ld : nullptr;
+    for (int r = 0; r < kCkRows; r++)
 #pragma unroll
         for (int v = 0; v < NV; v++) acc[r][v].a0 = acc[r][v].a1 = acc[r][v].a2 = acc[r][v].a3 = 0;
-    }
     for (int c0 = 0; c0 < ld2; c0 += ck2) {
         const int c1 = min(c0 + ck2, ld2);
         stage_chunk<NV>(svec, ck2, vec, c0, c1);
 #pragma unroll
         for (int r = 0; r < kCkRows; r++)
-            if (rowp[r]) wave_dot_chunk<NV>(rowp[r], svec, ck2, c0, c1, ld2, lane, acc[r]);
+            if (has[r]) wave_dot_chunk<NV>(rows[r], svec, ck2, c0, c1, ld2, lane, acc[r]);
     }
 #pragma unroll
     for (int r = 0; r < kCkRows; r++)
 #pragma unroll
-        for (int v = 0; v < NV; v++) dot[r][v] = rowp[r] ? wave_dot_finish(acc[r][v]) : 0.0;
+        for (int v = 0; v < NV; v++) dot[r][v] = has[r] ? wave_dot_finish(acc[r][v]) : 0.0;
+}
+
+// The row loop of every kernel that dots rows with staged vectors: the rows at positions first, first + step, ... < rows, row_of(pos)
+// the loader of the row at a position, each dotted with the NV vectors vec[]; per_row(pos, dot) gets a row's NV dots (in all lanes).
+//   CK = false: the vectors staged whole, ld2 apart, then one row at a time.
+//   CK = true:  the rows kCkRows at a time (dot_group), the vectors streamed ck2 double2 at a time per group.  The loop runs to the
+//               bound (rows + step - 1) / step, which is uniform wherever step is: every thread of the workgroup reaches every barrier.
+// Every thread of the workgroup calls it (first = the wave's own position).  The two forms give a row the same bits.
+template <bool CK, int NV, class RowOf, class Vec, class PerRow>
+__device__ __forceinline__ void sweep_rows(RowOf row_of, const Vec (&vec)[NV], int rows, int first, int step, int ld, double2 *svec, int ck2,
+                                           int lane, PerRow per_row) {
+    if constexpr (CK) {
+        const int kmax = (rows + step - 1) / step;
+        for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+            decltype(row_of(0)) row[kCkRows];
+            bool has[kCkRows];
+#pragma unroll
+            for (int r = 0; r < kCkRows; r++) {
+                const int pos = first + (k0 + r) * step;
+                has[r] = pos < rows;
+                if (has[r]) row[r] = row_of(pos);
+            }
+            double dot[kCkRows][NV];
+            dot_group<NV>(row, has, ld, vec, svec, ck2, lane, dot);
+#pragma unroll
+            for (int r = 0; r < kCkRows; r++)
+                if (has[r]) per_row(first + (k0 + r) * step, dot[r]);
+        }
+    } else {
+        const int ld2 = ld >> 1;
+        stage_vec<NV>(svec, vec, ld2);
+        for (int pos = first; pos < rows; pos += step) {
+            DotAcc acc[NV];
+#pragma unroll
+            for (int v = 0; v < NV; v++) acc[v].a0 = acc[v].a1 = acc[v].a2 = acc[v].a3 = 0;
+            wave_dot_chunk<NV>(row_of(pos), svec, ld2, 0, ld2, ld2, lane, acc);
+            double dot[NV];
+#pragma unroll
+            for (int v = 0; v < NV; v++) dot[v] = wave_dot_finish(acc[v]);
+            per_row(pos, dot);
+        }
+    }
 }
 
 // the workgroup's first-index argmin into the per-workgroup partials that the next kernel reduces (reduce_partials)

@@ -11,10 +11,11 @@
 namespace gomilp {
 
 // ------------------------------------------------------------------------------------------------
-// K1-K3 come in two forms each: one pass (the m-long vector staged whole in LDS) and the chunked form *_ck (the vector streamed
-// through LDS in chunks, kernels_common.h: dot_group; for vectors longer than the LDS window, ld > 8192, or wherever the context
-// knob row_chunk forces it).  The two kernels of a pair differ only in their staging and row loops: the pivot rules, the
-// per-element work and the commit are the helpers below, so both forms take the same decisions from bit-identical values.
+// K1-K3 come in two forms each, one kernel template on CK: one pass (the m-long vector staged whole in LDS) and the chunked form
+// (the vector streamed through LDS in chunks; for vectors longer than the LDS window, ld > 8192, or wherever the context knob
+// row_chunk forces it).  The two forms differ only in their staging and row loops (kernels_common.h: sweep_rows; update_rows
+// below): the pivot rules, the per-element work and the commit are the helpers below, so both forms take the same decisions from
+// bit-identical values.
 // The helpers take the pointers they use, not the LPArgs: a reference to the kernel's argument hides from the compiler that those
 // pointers are kernel arguments that nothing in the kernel overwrites, and the kernel loses its scalar loads (rvec[q], nonbasic[q]).
 // Template parameter G (every K1-K3 kernel and helper): the exact-step guard (LPArgs::guard > 0).  G = false is the code of every
@@ -165,9 +166,38 @@ __device__ __forceinline__ void update_row(const double *binv_cur, double *binv_
     }
 }
 
+// K3's rows: every row of the next B^-1 by the waves of the grid, old row p (rowp_g, in B^-1) staged in LDS.  Elementwise, so the
+// chunks of CK are only bounds: CK = false stages row p whole and takes a row at a time, CK = true takes a wave's rows kCkRows at a
+// time and streams row p ck2 double2 at a time per group, to a workgroup-uniform bound (every thread reaches stage_chunk's barriers).
+template <bool CK>
+__device__ __forceinline__ void update_rows(const double *binv_cur, double *binv_next, int ld, const double *dvec, int m, int p, double dpv,
+                                            const double *rowp_g, double2 *svec, int ck2) {
+    const int ld2 = ld >> 1;
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * kWavesPerBlock;
+    if constexpr (CK) {
+        const int kmax = (m + nwaves - 1) / nwaves;
+        for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
+            for (int c0 = 0; c0 < ld2; c0 += ck2) {
+                const int c1 = min(c0 + ck2, ld2);
+                stage_chunk<1>(svec, ck2, {PlainCol(rowp_g)}, c0, c1);
+#pragma unroll
+                for (int r = 0; r < kCkRows; r++) {
+                    const int i = wave + (k0 + r) * nwaves;
+                    if (i < m) update_row(binv_cur, binv_next, ld, dvec, i, p, dpv, svec, c0, c1, lane);
+                }
+            }
+        }
+    } else {
+        stage_vec<1>(svec, {PlainCol(rowp_g)}, ld2);
+        for (int i = wave; i < m; i += nwaves) update_row(binv_cur, binv_next, ld, dvec, i, p, dpv, svec, 0, ld2, lane);
+    }
+}
+
 // the rest of K3, by workgroup 0 after its rows: x_B and y (O(m); nobody else touches them in this kernel), the index swap
-// (simplex.go:280), the trace record and the counters.  rowp: old row p of B^-1 (LDS in k_update, B^-1 itself in k_update_ck:
-// the same values).  (The other pointers and m, ld, trace_cap, phase as in LPArgs.)
+// (simplex.go:280), the trace record and the counters.  rowp: old row p of B^-1 (where update_rows left it whole: LDS for CK = false,
+// B^-1 itself for CK = true: the same values).  (The other pointers and m, ld, trace_cap, phase as in LPArgs.)
 __device__ __forceinline__ void commit_pivot(DevState *st, double *xb, double *y, const double *dvec, const double *move, int32_t *basic,
                                              int32_t *nonbasic, DevPivot *trace, int64_t trace_cap, int phase, int m, int ld, int p, double dpv,
                                              const double *rowp, int no_swap, int bland) {

@@ -20,33 +20,16 @@ namespace gomilp {
 
 // K1-K3: the pivot rules, the per-element work and the commit are the helpers of simplex_helpers.h (shared with batch_revised.hip).
 
+// Template parameter CK (every kernel that stages an m-long vector): false stages the vector whole (ld up to the 64 KB LDS window, the
+// kernel's ck2 unused), true streams it through LDS ck2 double2 at a time (ld > 8192, or wherever the context knob row_chunk forces it).
+// The staging and the row loop of either form are sweep_rows of kernels_common.h; everything around them is written once.
+
 // ------------------------------------------------------------------------------------------------
 // K1  pricing:  r[pos] = cost[j] - At[j,:].y   (simplex.go:242-243), fused first-index argmin (:247)
 //     algorithmic traffic: m*(n-m)*8 bytes read (A_N once)
 // ------------------------------------------------------------------------------------------------
-template <bool G>
-__global__ __launch_bounds__(kBlock) void k_price(LPArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ unsigned long long sk[kWavesPerBlock];
-    __shared__ unsigned int si[kWavesPerBlock];
-    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
-    if (!price_gate(a.st)) return;
-    const int ld2 = a.ld >> 1;
-    stage_vec(svec, a.y, ld2);
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    unsigned long long bk = ~0ull, b2 = ~0ull;
-    unsigned int bi = 0xFFFFFFFFu;
-    for (int pos = wave; pos < a.nn; pos += nwaves) {
-        const int j = a.nonbasic[pos];
-        price_elem<G>(a.cost, a.rvec, pos, j, wave_dot_row(a.At + (size_t)j * a.ld, svec, ld2, lane), lane, bk, bi, b2);
-    }
-    publish<G>(bk, bi, b2, sk, si, ss, a.pk_price, a.pi_price);
-}
-
-template <bool G>
-__global__ __launch_bounds__(kBlock) void k_price_ck(LPArgs a, int ck2) {
+template <bool G, bool CK>
+__global__ __launch_bounds__(kBlock) void k_price(LPArgs a, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
@@ -55,18 +38,10 @@ __global__ __launch_bounds__(kBlock) void k_price_ck(LPArgs a, int ck2) {
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
-    const int kmax = (a.nn + nwaves - 1) / nwaves;
     unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows][1];
-        dot_group<1>(a.At, a.ld, a.nonbasic, a.nn, k0, wave, nwaves, {a.y}, svec, ck2, lane, dot);
-#pragma unroll
-        for (int r = 0; r < kCkRows; r++) {
-            const int pos = wave + (k0 + r) * nwaves;
-            if (pos < a.nn) price_elem<G>(a.cost, a.rvec, pos, a.nonbasic[pos], dot[r][0], lane, bk, bi, b2);
-        }
-    }
+    sweep_rows<CK, 1>([&](int pos) { return PlainCol(a.At + (size_t)a.nonbasic[pos] * a.ld); }, {PlainCol(a.y)}, a.nn, wave, nwaves, a.ld, svec, ck2, lane,
+                      [&](int pos, const double (&dot)[1]) { price_elem<G>(a.cost, a.rvec, pos, a.nonbasic[pos], dot[0], lane, bk, bi, b2); });
     publish<G>(bk, bi, b2, sk, si, ss, a.pk_price, a.pi_price);
 }
 
@@ -75,27 +50,8 @@ __global__ __launch_bounds__(kBlock) void k_price_ck(LPArgs a, int ck2) {
 //     fused first-index argmin of move (:268).   traffic: m*m*8 bytes read (B^-1 once)
 //     entering variable: pick_entering
 // ------------------------------------------------------------------------------------------------
-template <bool G>
-__global__ __launch_bounds__(kBlock) void k_ftran(LPArgs a, int nparts_price, int forced_pos, int forced_var) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ unsigned long long sk[kWavesPerBlock];
-    __shared__ unsigned int si[kWavesPerBlock];
-    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
-    int var;
-    if (!pick_entering<G>(a.st, a.pk_price, a.pi_price, nparts_price, a.rvec, a.nonbasic, a.tol, a.guard, forced_pos, forced_var, sk, si, ss, var)) return;
-    const int ld2 = a.ld >> 1;
-    stage_vec(svec, a.At + (size_t)var * a.ld, ld2);
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    unsigned long long bk = ~0ull, b2 = ~0ull;
-    unsigned int bi = 0xFFFFFFFFu;
-    for (int i = wave; i < a.m; i += nwaves) ratio_elem<G>(a.xb, a.dvec, a.move, i, wave_dot_row(a.binv_cur + (size_t)i * a.ld, svec, ld2, lane), lane, bk, bi, b2);
-    publish<G>(bk, bi, b2, sk, si, ss, a.pk_ratio, a.pi_ratio);
-}
-
-template <bool G>
-__global__ __launch_bounds__(kBlock) void k_ftran_ck(LPArgs a, int nparts_price, int forced_pos, int forced_var, int ck2) {
+template <bool G, bool CK>
+__global__ __launch_bounds__(kBlock) void k_ftran(LPArgs a, int nparts_price, int forced_pos, int forced_var, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
@@ -105,18 +61,10 @@ __global__ __launch_bounds__(kBlock) void k_ftran_ck(LPArgs a, int nparts_price,
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
-    const int kmax = (a.m + nwaves - 1) / nwaves;
     unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows][1];
-        dot_group<1>(a.binv_cur, a.ld, nullptr, a.m, k0, wave, nwaves, {a.At + (size_t)var * a.ld}, svec, ck2, lane, dot);
-#pragma unroll
-        for (int r = 0; r < kCkRows; r++) {
-            const int i = wave + (k0 + r) * nwaves;
-            if (i < a.m) ratio_elem<G>(a.xb, a.dvec, a.move, i, dot[r][0], lane, bk, bi, b2);
-        }
-    }
+    sweep_rows<CK, 1>([&](int i) { return PlainCol(a.binv_cur + (size_t)i * a.ld); }, {PlainCol(a.At + (size_t)var * a.ld)}, a.m, wave, nwaves, a.ld, svec, ck2, lane,
+                      [&](int i, const double (&dot)[1]) { ratio_elem<G>(a.xb, a.dvec, a.move, i, dot[0], lane, bk, bi, b2); });
     publish<G>(bk, bi, b2, sk, si, ss, a.pk_ratio, a.pi_ratio);
 }
 
@@ -124,9 +72,11 @@ __global__ __launch_bounds__(kBlock) void k_ftran_ck(LPArgs a, int nparts_price,
 // K3  basis change: rank-1 update of B^-1 (ping-pong), x_B, y, index swap (simplex.go:280-292 without
 //     the three fresh LU factorizations).   traffic: m*m*8 read + m*m*8 written
 //     leaving row: pick_leaving.  no_swap: setup pivot (indices managed by the host).
+//     Elementwise: the chunks of CK are only bounds, and the commit reads old row p where CK left it (LDS, or B^-1 itself:
+//     binv_cur is only read here).
 // ------------------------------------------------------------------------------------------------
-template <bool G>
-__global__ __launch_bounds__(kBlock) void k_update(LPArgs a, int nparts_ratio, int forced_p, int no_swap, int bland) {
+template <bool G, bool CK>
+__global__ __launch_bounds__(kBlock) void k_update(LPArgs a, int nparts_ratio, int forced_p, int no_swap, int bland, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
@@ -134,47 +84,11 @@ __global__ __launch_bounds__(kBlock) void k_update(LPArgs a, int nparts_ratio, i
     int p;
     if (!pick_leaving<G>(a.st, a.pk_ratio, a.pi_ratio, nparts_ratio, a.move, a.dvec, a.guard, forced_p, sk, si, ss, p)) return;
     const double dpv = a.dvec[p];
-    const int ld2 = a.ld >> 1;
-    stage_vec(svec, a.binv_cur + (size_t)p * a.ld, ld2);  // old row p
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    for (int i = wave; i < a.m; i += nwaves) update_row(a.binv_cur, a.binv_next, a.ld, a.dvec, i, p, dpv, svec, 0, ld2, lane);
+    const double *rowp_g = a.binv_cur + (size_t)p * a.ld;   // old row p
+    update_rows<CK>(a.binv_cur, a.binv_next, a.ld, a.dvec, a.m, p, dpv, rowp_g, svec, ck2);
     if (blockIdx.x == 0)
         commit_pivot(a.st, a.xb, a.y, a.dvec, a.move, a.basic, a.nonbasic, a.trace, a.trace_cap, a.phase, a.m, a.ld, p, dpv,
-                     reinterpret_cast<const double *>(svec), no_swap, bland);
-}
-
-// elementwise: its chunks are only bounds
-template <bool G>
-__global__ __launch_bounds__(kBlock) void k_update_ck(LPArgs a, int nparts_ratio, int forced_p, int no_swap, int bland, int ck2) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    __shared__ unsigned long long sk[kWavesPerBlock];
-    __shared__ unsigned int si[kWavesPerBlock];
-    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
-    int p;
-    if (!pick_leaving<G>(a.st, a.pk_ratio, a.pi_ratio, nparts_ratio, a.move, a.dvec, a.guard, forced_p, sk, si, ss, p)) return;
-    const double dpv = a.dvec[p];
-    const int ld2 = a.ld >> 1;
-    const double *rowp_g = a.binv_cur + (size_t)p * a.ld;   // old row p (binv_cur is only read here)
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    const int kmax = (a.m + nwaves - 1) / nwaves;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        for (int c0 = 0; c0 < ld2; c0 += ck2) {
-            const int c1 = min(c0 + ck2, ld2);
-            stage_chunk<1>(svec, ck2, {rowp_g}, c0, c1);
-#pragma unroll
-            for (int r = 0; r < kCkRows; r++) {
-                const int i = wave + (k0 + r) * nwaves;
-                if (i < a.m) update_row(a.binv_cur, a.binv_next, a.ld, a.dvec, i, p, dpv, svec, c0, c1, lane);
-            }
-        }
-    }
-    if (blockIdx.x == 0)
-        commit_pivot(a.st, a.xb, a.y, a.dvec, a.move, a.basic, a.nonbasic, a.trace, a.trace_cap, a.phase, a.m, a.ld, p, dpv, rowp_g,
-                     no_swap, bland);
+                     CK ? rowp_g : reinterpret_cast<const double *>(svec), no_swap, bland);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -258,36 +172,15 @@ __global__ void k_set_binv_perm(double *binv, int ld, int m, const int32_t *rho)
 }
 
 // out[i] = M[i,:].vec   (x_B = Binv b refresh)
-__global__ __launch_bounds__(kBlock) void k_matvec_rows(const double *__restrict__ M, int ld, int m,
-                                                        const double *__restrict__ vec, double *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) double2 svec[];
-    const int ld2 = ld >> 1;
-    stage_vec(svec, vec, ld2);
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    for (int i = wave; i < m; i += nwaves) {
-        const double d = wave_dot_row(M + (size_t)i * ld, svec, ld2, lane);
-        if (lane == 0) out[i] = d;
-    }
-}
-// the chunked form of k_matvec_rows
-__global__ __launch_bounds__(kBlock) void k_matvec_rows_ck(const double *__restrict__ M, int ld, int m,
-                                                           const double *__restrict__ vec, double *__restrict__ out, int ck2) {
+template <bool CK>
+__global__ __launch_bounds__(kBlock) void k_matvec_rows(const double *__restrict__ M, int ld, int m, const double *__restrict__ vec,
+                                                        double *__restrict__ out, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * kWavesPerBlock;
-    const int kmax = (m + nwaves - 1) / nwaves;
-    for (int k0 = 0; k0 < kmax; k0 += kCkRows) {
-        double dot[kCkRows][1];
-        dot_group<1>(M, ld, nullptr, m, k0, wave, nwaves, {vec}, svec, ck2, lane, dot);
-#pragma unroll
-        for (int r = 0; r < kCkRows; r++) {
-            const int i = wave + (k0 + r) * nwaves;
-            if (i < m && lane == 0) out[i] = dot[r][0];
-        }
-    }
+    sweep_rows<CK, 1>([&](int i) { return PlainCol(M + (size_t)i * ld); }, {PlainCol(vec)}, m, wave, nwaves, ld, svec, ck2, lane,
+                      [&](int i, const double (&dot)[1]) { if (lane == 0) out[i] = dot[0]; });
 }
 
 // y[j] = sum_i cost[basic[i]] * Binv[i,j]   (y = B^-T c_B, simplex.go:236) — column-parallel, row-chunked;
@@ -430,11 +323,14 @@ __global__ __launch_bounds__(kBlock) void k_lu_step(LUArgs a, int k, int nparts)
 // host-callable launch wrappers (the engine is plain C++; only this file is device code)
 // ------------------------------------------------------------------------------------------------
 
+// dynamic LDS of a kernel that stages one m-long vector: the chunk (row_chunk2 > 0: the CK = true instance), else the whole vector
+static size_t staged_lds(int ld, int row_chunk2) { return row_chunk2 > 0 ? (size_t)row_chunk2 * sizeof(double2) : (size_t)ld * sizeof(double); }
+
 // (LPArgs::guard > 0: the guard instances)
 template <bool G>
 static void launch_price_t(const LPArgs &a, int g, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    if (a.row_chunk2 > 0) hipExtLaunchKernelGGL(k_price_ck<G>, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, a.row_chunk2);
-    else hipExtLaunchKernelGGL(k_price<G>, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a);
+    hipExtLaunchKernelGGL((a.row_chunk2 > 0 ? k_price<G, true> : k_price<G, false>), dim3(g), dim3(kBlock), staged_lds(a.ld, a.row_chunk2), s, e0, e1, 0, a,
+                          a.row_chunk2);
 }
 int launch_price(const LPArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const int g = grid_for_rows(a.nn);
@@ -445,12 +341,8 @@ int launch_price(const LPArgs &a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
 template <bool G>
 static void launch_ftran_t(const LPArgs &a, int g, int nparts_price, int forced_pos, int forced_var, hipStream_t s, hipEvent_t e0,
                            hipEvent_t e1) {
-    if (a.row_chunk2 > 0)
-        hipExtLaunchKernelGGL(k_ftran_ck<G>, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, nparts_price,
-                              forced_pos, forced_var, a.row_chunk2);
-    else
-        hipExtLaunchKernelGGL(k_ftran<G>, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a, nparts_price,
-                              forced_pos, forced_var);
+    hipExtLaunchKernelGGL((a.row_chunk2 > 0 ? k_ftran<G, true> : k_ftran<G, false>), dim3(g), dim3(kBlock), staged_lds(a.ld, a.row_chunk2), s, e0, e1, 0, a,
+                          nparts_price, forced_pos, forced_var, a.row_chunk2);
 }
 int launch_ftran(const LPArgs &a, int nparts_price, int forced_pos, int forced_var, hipStream_t s, hipEvent_t e0,
                  hipEvent_t e1) {
@@ -462,12 +354,8 @@ int launch_ftran(const LPArgs &a, int nparts_price, int forced_pos, int forced_v
 template <bool G>
 static void launch_update_t(const LPArgs &a, int g, int nparts_ratio, int forced_p, int no_swap, int bland, hipStream_t s, hipEvent_t e0,
                             hipEvent_t e1) {
-    if (a.row_chunk2 > 0)
-        hipExtLaunchKernelGGL(k_update_ck<G>, dim3(g), dim3(kBlock), (size_t)a.row_chunk2 * sizeof(double2), s, e0, e1, 0, a, nparts_ratio,
-                              forced_p, no_swap, bland, a.row_chunk2);
-    else
-        hipExtLaunchKernelGGL(k_update<G>, dim3(g), dim3(kBlock), (size_t)a.ld * sizeof(double), s, e0, e1, 0, a, nparts_ratio,
-                              forced_p, no_swap, bland);
+    hipExtLaunchKernelGGL((a.row_chunk2 > 0 ? k_update<G, true> : k_update<G, false>), dim3(g), dim3(kBlock), staged_lds(a.ld, a.row_chunk2), s, e0, e1, 0, a,
+                          nparts_ratio, forced_p, no_swap, bland, a.row_chunk2);
 }
 void launch_update(const LPArgs &a, int nparts_ratio, int forced_p, int no_swap, int bland, hipStream_t s, hipEvent_t e0,
                    hipEvent_t e1) {
@@ -491,11 +379,8 @@ void launch_set_binv_perm(double *binv, int ld, int m, const int32_t *rho, hipSt
     hipLaunchKernelGGL(k_set_binv_perm, dim3((m + 255) / 256), dim3(256), 0, s, binv, ld, m, rho);
 }
 void launch_matvec_rows(const double *M, int ld, int m, const double *vec, double *out, hipStream_t s, int row_chunk2) {
-    if (row_chunk2 > 0)
-        hipLaunchKernelGGL(k_matvec_rows_ck, dim3(grid_for_rows(m)), dim3(kBlock), (size_t)row_chunk2 * sizeof(double2), s, M, ld, m, vec, out,
-                           row_chunk2);
-    else
-        hipLaunchKernelGGL(k_matvec_rows, dim3(grid_for_rows(m)), dim3(kBlock), (size_t)ld * sizeof(double), s, M, ld, m, vec, out);
+    hipLaunchKernelGGL((row_chunk2 > 0 ? k_matvec_rows<true> : k_matvec_rows<false>), dim3(grid_for_rows(m)), dim3(kBlock), staged_lds(ld, row_chunk2), s, M,
+                       ld, m, vec, out, row_chunk2);
 }
 // scratch must hold y_chunks(m) * ld doubles
 int y_chunks(int m) { int c = (m + 63) / 64; return c > 64 ? 64 : c; }

@@ -1,5 +1,5 @@
 """Relaxations of more than 8192 rows: the three-kernel revised simplex runs them, its kernels staging their m-long vector through
-LDS in chunks (simplex_kernels.hip, *_ck kernels).  Slack-basis starts of 8193 to 12288 rows through the flat call, the resident
+LDS in chunks (simplex_kernels.hip, the CK = true kernel instances).  Slack-basis starts of 8193 to 12288 rows through the flat call, the resident
 upload and device-assembled children, checked by an optimality certificate computed here; the chunked form forced below 8192 rows
 (context knob row_chunk) bit-identical to the one-pass form; and the shapes that stay refused.
 

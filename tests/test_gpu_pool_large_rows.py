@@ -1,5 +1,5 @@
 """Frontier pools beyond the 64 KB LDS window (pool knob large_rows, DESIGN.md §2.5e "Chunked forms"): the batched revised simplex in its
-chunked kernels (batch_revised.hip: k_rv_*_ck), the staged m-long vectors streamed through LDS row_chunk doubles at a time.
+chunked kernels (batch_revised.hip: the CK = true instances of k_rv_*), the staged m-long vectors streamed through LDS row_chunk doubles at a time.
 
 The chunked kernels run the helpers of the one-pass kernels on dot products accumulated in the same order (kernels_common.h: dot_group), so
 every comparison between chunk sizes, and with the worker path, is by bits: status and has_x equal, z and x equal as uint64, the pivot,
@@ -109,7 +109,7 @@ def _run2(batch_revised, large_rows, row_chunk):
 @pytest.mark.parametrize("chunk", [512, 1536])
 def test_multi_chunk(chunk):
     """1101 rows, ld2 = 551: row_chunk 512 gives three chunks (256 + 256 + 39 double2), 1536 one; three of the six children start in
-    Phase I (the forced pivot and the refresh through k_rv_ftran_ck / k_rv_update_ck / k_rv_matvec_ck)"""
+    Phase I (the forced pivot and the refresh through the chunked k_rv_ftran / k_rv_update / k_rv_matvec)"""
     ref, workers, g = _run2(1, 1, 0), _run2(0, 0, 0), _run2(1, 1, chunk)
     assert len(g.status) == 6
     assert g.stats["phase1_runs"] == 3
@@ -124,7 +124,7 @@ def test_multi_chunk(chunk):
 
 def test_bland_steps():
     """synth.wide_degenerate_lp(1000, 0) under a budget of 400 pivots: the root itself and two one-row children; the Bland rule inside the
-    loop (k_rv_bland, the candidate's FTRAN in k_rv_ftran_ck, replaceBland's leaving row in k_rv_update_ck)"""
+    loop (k_rv_bland, the candidate's FTRAN in the chunked k_rv_ftran, replaceBland's leaving row in the chunked k_rv_update)"""
     root = synth.wide_degenerate_lp(1000, 0)
     wave = [[], [(0, 1, 1.0)], [(1, 1, 0.0)]]
     a = _show("degenerate 1000 rows, row_chunk 0", _pool("deg", root, large_rows=1, max_pivots=BUDGET).solve(wave))
@@ -139,7 +139,7 @@ def test_bland_steps():
 
 def test_artificial_exchange():
     """No construction of tests/test_gpu_wide_exchange.py has more than 512 rows, so its largest: wave P3 of the 300 x 1200 root (8
-    children of 303 rows, children 1 and 2 exchange) — the candidate scan in k_rv_exch_ck, one chunk with a tail"""
+    children of 303 rows, children 1 and 2 exchange) — the candidate scan in the chunked k_rv_exch, one chunk with a tail"""
     wave = _exch_wave(300, "P3")
     a = _show("exchange, row_chunk 0", _pool("x300", _exch_root(300), large_rows=1).solve(wave))
     b = _show("exchange, row_chunk 512", _pool("x300", large_rows=1, row_chunk=512).solve(wave))
@@ -164,8 +164,8 @@ def _warm2(row_chunk):
 
 
 def test_warm_start():
-    """the six children of test 2 from the kept root: k_rv_dual_price_ck (two vectors, 256 double2 each at a time) in front of
-    k_rv_ftran_ck<RR_DUAL> / k_rv_update_ck<RR_DUAL>; against the cold wave under the contract of the warm mode"""
+    """the six children of test 2 from the kept root: the chunked k_rv_dual_price (two vectors, 256 double2 each at a time) in front of
+    the chunked k_rv_ftran<RR_DUAL> / k_rv_update<RR_DUAL>; against the cold wave under the contract of the warm mode"""
     a, b = _warm2(0), _warm2(512)
     _assert_same_bits(a, b)
     for k in ("pivots_dual", "warm_started", "warm_fallbacks"):

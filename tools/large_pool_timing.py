@@ -3,7 +3,7 @@ pool with large_rows = 1 (the batched revised simplex in its chunked kernels), a
 single context, cold and warm.  Both paths run under the same pivot budget (the cold solves of these children take ~9500 pivots of
 ~0.6 ms each; the budget keeps the run short and the work equal: the two paths take the same pivots).
 
-usage: large_pool_timing.py [pivot budget, default 2000] [log file, default profiles/large_pool_timing.log]"""
+usage: large_pool_timing.py [pivot budget, default 2000] [log file, default profiles/large_pool_timing.log] [wave sizes, default 2,4,8]"""
 import math
 import os
 import sys
@@ -17,6 +17,7 @@ from gomilp_amd import lp  # noqa: E402
 
 BUDGET = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 LOG = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "large_pool_timing.log")
+COUNTS = [int(v) for v in sys.argv[3].split(",")] if len(sys.argv) > 3 else [2, 4, 8]
 M0, NV, NCOST, DUAL = 8200, 16448, 48, 256
 _log = open(LOG, "w")
 
@@ -64,7 +65,7 @@ g0 = root.solve(0.0, keep=True)
 say("context: root solved and kept in %.2f s: status %s, pivots %d" % (time.perf_counter() - t0, lp.STATUS_NAMES.get(g0.status), g0.stats["pivots_phase2"]))
 cx.set("max_pivots", BUDGET)
 
-for count in (2, 4, 8):
+for count in COUNTS:
     wave = pairs[:count]
     for mode in ("cold", "warm"):
         t0 = time.perf_counter()
