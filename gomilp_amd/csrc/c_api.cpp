@@ -303,6 +303,21 @@ int gomilp_debug_bt_plan(int64_t m, int64_t ldt, int64_t nknobs, const char *con
     return GOMILP_BT_PLAN_FIELDS;
 }
 
+int gomilp_debug_solve_plan(int64_t m, int64_t n, int32_t start, double scale_span, int64_t nknobs, const char *const *keys, const int64_t *values, double *out) {
+    if (m < 1 || n <= m || n > (1 << 24) || start < 0 || start > 2 || nknobs < 0 || (nknobs > 0 && (!keys || !values)) || !out) return -GOMILP_ERR_BAD_SHAPE;
+    gomilp::SolveKnobs knobs;
+    for (int64_t i = 0; i < nknobs; i++) {
+        const int rc = keys[i] ? knobs.set(keys[i], values[i]) : -1;
+        if (rc != GOMILP_OK) return -GOMILP_ERR_BAD_SHAPE;   // (a key that is none of the plan's knobs included)
+    }
+    const gomilp::SolvePlan p = gomilp::SolvePlan::make((int)m, (int)n, (int)((m + 1) & ~(int64_t)1), (gomilp::SolvePlan::StartKind)start, scale_span, knobs);
+    const double f[GOMILP_SOLVE_PLAN_FIELDS] = {(double)p.status, (double)p.pipeline, (double)p.use_tab, (double)p.blocked, (double)p.gen_start, (double)p.gen_revised,
+                                                (double)p.badly_scaled, p.guard, p.cguard, (double)p.replay_if_feasible, (double)p.search_on_device,
+                                                (double)p.art_on_device, (double)p.needs_host_A};
+    for (int i = 0; i < GOMILP_SOLVE_PLAN_FIELDS; i++) out[i] = f[i];
+    return GOMILP_SOLVE_PLAN_FIELDS;
+}
+
 // diagnostic (host only, no device): the routing of one frontier wave.  The root views are made here from the fields WavePlan reads; a
 // General made on the host holds null pointers, which its destructor leaves alone.
 int gomilp_debug_wave_plan(int64_t nroots, const int64_t *root_m, const int64_t *root_n, const int32_t *root_flags, const double *root_scale_span,

@@ -100,29 +100,84 @@ int BtKnobs::set(const std::string &key, int64_t v) {
     return GOMILP_OK;
 }
 
+int SolveKnobs::set(const std::string &key, int64_t v) {
+    if (key == "fused") fused = v ? 1 : 0;
+    else if (key == "tableau") tableau = v ? 1 : 0;
+    else if (key == "blocked") blocked = v ? 1 : 0;
+    else if (key == "general_device") general_device = v ? 1 : 0;
+    else if (key == "general_min_rows") general_min_rows = v < 2 ? 2 : v;
+    else if (key == "exact_degenerate") { if (v < 0 || v > 3) return GOMILP_ERR_BAD_SHAPE; exact_degenerate = v; }   // 3: strict — EVERY pivot decided on fresh gonum-order solves (engine_tableau.cpp exact_step)
+    else if (key == "cond_guard") cond_guard = v ? 1 : 0;
+    else return -1;
+    return GOMILP_OK;
+}
+
+// The one place that says where a single solve of m < n rows goes ("Where a solve goes"; tests/test_solve_plan.py).
+SolvePlan SolvePlan::make(int m, int n, int ld, StartKind start, double scale_span, const SolveKnobs &k) {
+    SolvePlan p;
+    const bool slack = start == Slack, strict = k.exact_degenerate == 3;
+    p.gen_start = p.needs_host_A = !slack;   // (the search, the set-up and the exact steps of a non-slack start read the host copy of A)
+    p.badly_scaled = scale_span > 1e9;
+    // beyond the LDS window (chunked staging) only the three-kernel revised simplex runs, from slack starts: the general
+    // start's search and set-up stage m-long rows, and the single-kernel tableau returned a wrong ErrUnbounded on a 12288 x 18432 slack
+    // start after a run of Bland steps
+    const bool windowed = ld <= kLdsWindowLd;
+    if (!windowed && !slack) { p.status = GOMILP_ERR_UNSUPPORTED; return p; }
+    // A non-slack starting basis (equality rows, supplied basis) takes the tableau pipelines wherever their row fits: their set-up accepts
+    // any B^-1; the n - m < 2m rule is only the bytes-per-pivot trade-off between the two formulations (the explicit tableau moves
+    // 16*m*(n-m) bytes per pivot in one launch, the revised form 8*[m(n-m) + 2m^2] in two).  So does a wide LP that wants exact steps when
+    // the BLOCKED tableau takes it: on slack starts only the block kernels stop in front of a degenerate pivot (ST_NEED_EXACT) for
+    // Engine::exact_step — the single-kernel tableau and the revised pipelines decide every pivot on their updated quantities.
+    // (tableau = 0 keeps the revised pipelines, blocked = 0 the n - m < 2m rule, both without the guard on slack starts: A/B knobs.)
+    const int nn_max = n + 1 - m;
+    const bool tab_fits = (size_t)tab_ld(nn_max) * sizeof(double) <= 64 * 1024;
+    const bool bt_ok = k.blocked && bt_supported(m, nn_max);
+    const bool exact = exact_wanted(k.exact_degenerate, m, slack, scale_span);
+    p.use_tab = k.tableau && ((n - m) < 2 * m || !slack || (exact && bt_ok)) && tab_fits && windowed;
+    p.blocked = p.use_tab && bt_ok;
+    // A non-slack start the tableau does not take (its row beyond the LDS window: n - m > 8191, or knob tableau = 0) runs the three-kernel
+    // revised loop with the exact-step guard (LPArgs::guard; the fused pipeline has none): the exact steps need the host copy of A, kept
+    // up to m * n = 2^25
+    p.gen_revised = !slack && !p.use_tab && (size_t)m * (size_t)n <= ((size_t)1 << 25);
+    // strict mode IS the exact steps: where neither the blocked tableau nor that loop runs, the solve refuses instead of deciding the
+    // default way; a non-slack start that neither the tableau nor that loop takes has nowhere to go
+    if ((strict && !p.blocked && !p.gen_revised) || (!slack && !p.use_tab && !p.gen_revised)) { p.status = GOMILP_ERR_UNSUPPORTED; return p; }
+    p.pipeline = p.use_tab ? (p.blocked ? 3 : 2) : ((k.fused && fused_supported(ld) && !p.gen_revised) ? 1 : 0);
+    // degenerate vertices decided on a fresh gonum-order x_B where the pipeline has exact steps; strict: an infinite guard —
+    // the kernels stop in front of EVERY decision, stop test included, and the host repeats the reference's iteration on fresh solves
+    if (p.blocked || p.gen_revised) p.guard = strict ? std::numeric_limits<double>::infinity() : exact ? 1e-9 : 0.0;
+    p.cguard = (k.cond_guard && slack && m > 64) ? 1e-9 : 0.0;   // (<= 64 rows: the per-pivot replay; non-slack starts: the guard above is on)
+    p.replay_if_feasible = k.cond_guard && m <= 64 && start != Supplied;
+    p.search_on_device = m >= k.general_min_rows && k.general_device;
+    p.art_on_device = !slack && m >= k.general_min_rows;
+    return p;
+}
+
+SolvePlan SolvePlan::warm(int ld, double scale_span, const SolveKnobs &k) {
+    SolvePlan p;
+    p.badly_scaled = scale_span > 1e9;
+    p.pipeline = (k.fused && fused_supported(ld)) ? 1 : 0;
+    return p;
+}
+
 int Engine::set(const std::string &key, int64_t v) {
     std::lock_guard<std::mutex> g(mu_);
     const int bt = bt_knobs_.set(key, v);
     if (bt >= 0) return bt;
+    const int sk = knobs_.set(key, v);
+    if (sk >= 0) return sk;
     if (key == "refresh") { if (v < 0) return GOMILP_ERR_BAD_SHAPE; refresh_ = v; }
     else if (key == "trace") trace_on_ = v ? 1 : 0;
     else if (key == "sample_events") sample_events_ = v < 0 ? 0 : v;
-    else if (key == "fused") fused_ = v ? 1 : 0;
     else if (key == "lu_look") lu_look_ = v ? 1 : 0;
     else if (key == "lu_large") lu_large_ = v ? 1 : 0;
     else if (key == "lu_blocked") lu_blocked_ = v < 0 ? 0 : (v > 2 ? 3 : v);  // 0 per column, 1 blocked panels, 2 compressed rounds (slot panel), 3 the same with the look-ahead schedule (default; lu_compressed.hip)
-    else if (key == "tableau") tableau_ = v ? 1 : 0;
-    else if (key == "blocked") blocked_ = v ? 1 : 0;
     else if (key == "bt_upd_valu") bt_upd_valu_ = v ? 1 : 0;
 #ifdef GOMILP_DEBUG
     else if (key == "bt_fault") bt_fault_ = v;   // fault injection, diagnostic flavour only: 1 a workgroup of the block / loop kernels, 2 the U-solve workgroup of the look-ahead LU
 #endif
-    else if (key == "general_device") general_device_ = v ? 1 : 0;
     else if (key == "lu_cross") lu_cross_ = v < 0 ? -1 : (v > 2 ? 2 : v);   // the panel's rows on the workgroups of one XCD (lu_cross.hip): 0 never, 1 sixteen slots in the plain schedule, 2 thirty-two slots in the schedule lu_blocked names, -1 (default) 2 for bases of 1281 .. 2048 rows
     else if (key == "general_block") general_block_ = v ? 1 : 0;
-    else if (key == "general_min_rows") general_min_rows_ = v < 2 ? 2 : v;
-    else if (key == "exact_degenerate") { if (v < 0 || v > 3) return GOMILP_ERR_BAD_SHAPE; exact_degenerate_ = v; }   // 3: strict — EVERY pivot decided on fresh gonum-order solves (engine_tableau.cpp exact_step)
-    else if (key == "cond_guard") cond_guard_ = v ? 1 : 0;
     else if (key == "poll_delay") { if (v < 0 || v > 64) return GOMILP_ERR_BAD_SHAPE; poll_delay_ = v; }
     else if (key == "row_chunk") { if (v < 0 || v % 512 != 0 || v > kLdsWindowLd) return GOMILP_ERR_BAD_SHAPE; row_chunk_ = v; }   // (whole 256-double2 steps of wave_dot_chunk)
     else return GOMILP_ERR_BAD_SHAPE;
@@ -460,7 +515,7 @@ LPArgs Engine::make_args(const Problem &P, int phase, double tol, int nn, const 
     a.trace = (trace_on_ || shadow_trace_) ? w.trace : nullptr;
     a.trace_cap = w.trace_cap;
     a.row_chunk2 = row_chunk2(P);
-    a.guard = lp_guard_;
+    a.guard = plan_.guard;
     return a;
 }
 
@@ -637,7 +692,7 @@ void Engine::account_samples(gomilp_lp_stats *st, const std::vector<int64_t> &sa
 }
 
 int Engine::run_loop(const Problem &P, int phase, double tol, int nn, const double *cost, gomilp_lp_stats *st) {
-    if (fused_ && fused_supported(P.ld) && !gen_revised_) return run_loop_fused(P, phase, tol, nn, cost, st);   // (no guard there: general starts stay here)
+    if (plan_.pipeline == 1) return run_loop_fused(P, phase, tol, nn, cost, st);   // (no guard there: general starts stay here)
     Work &w = *w_;
     DevState &hs = *w.st_host;
     hs.done = 0; hs.status = ST_RUNNING; hs.pivots = 0; hs.q = hs.p = -1; hs.rq = hs.dp = hs.mv = 0;
@@ -723,10 +778,8 @@ int Engine::run_loop(const Problem &P, int phase, double tol, int nn, const doub
                 if (ret == GOMILP_ERR_LINSOLVE && cond_fresh(P, nullptr, &k1, &kinf) == GOMILP_OK && !(k1 < 1e16)) ret = GOMILP_ERR_CONDITION;
                 // strict: the pivot into this basis was decided in the previous exact step, and a singular basis keeps that step's fresh
                 // x_B (the reference's receiver keeps its values when Det() == 0, simplex.go:289-292; the epilogue returns it)
-                if (ret == GOMILP_ERR_CONDITION && lp_guard_ == std::numeric_limits<double>::infinity() && exact_xb_.size() == (size_t)P.m) {
-                    std::vector<double> xpad(P.ld, 0.0);
-                    std::copy(exact_xb_.begin(), exact_xb_.end(), xpad.begin());
-                    const int rc = stage_upload(w.xb, xpad.data(), (size_t)P.ld * sizeof(double));
+                if (ret == GOMILP_ERR_CONDITION && plan_.guard == std::numeric_limits<double>::infinity() && exact_xb_.size() == (size_t)P.m) {
+                    const int rc = upload_padded(w.xb, exact_xb_, P.ld);
                     if (rc != GOMILP_OK) ret = rc;
                 }
                 break;
@@ -886,6 +939,23 @@ int Engine::solve_cold_locked(int64_t id, double tol, const int64_t *initial_bas
     return rc;
 }
 
+void Engine::open_stats() {
+    launches_ = 0;
+    fs_device_ = fs_host_ = 0; lu_look_fault_ = 0;
+    last_trace_.clear();
+    last_trace_total_ = 0;
+}
+
+int Engine::close_stats(gomilp_lp_stats *st, double t0, int code) {
+    st->seconds_total = now_s() - t0; st->kernel_launches = launches_;
+    st->seconds_final_device = fs_device_; st->seconds_final_host = fs_host_;
+    st->lu_dense_steps = lu_dense_; st->lu_rounds = lu_rounds_;
+    if (lu_look_fault_) st->device_retries = lu_look_fault_;   // (the final solve was repeated with the plain LU schedule)
+    return code;
+}
+
+// The stages of a solve: validate, the starting basis (scan_start), the plan, x_B of a searched basis (search_start), set-up
+// (upload_start), the phase loops of the plan's pipeline, solve_tail.
 int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, double *opt_f, double *opt_x, int32_t *has_x,
                          int64_t *basis_out, gomilp_lp_stats *stats) {
     const double t0 = now_s();
@@ -893,26 +963,15 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
     gomilp_lp_stats *st = stats ? stats : &local;
     memset(st, 0, sizeof(*st));
     st->device_id = device_;
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    const double inf = std::numeric_limits<double>::infinity();
     if (has_x) *has_x = 0;
-    if (opt_f) *opt_f = nan;
+    if (opt_f) *opt_f = std::numeric_limits<double>::quiet_NaN();
     if (id < 0 || (size_t)id >= problems_.size() || !problems_[id] || !opt_f || !opt_x || !has_x) return GOMILP_ERR_BAD_SHAPE;
     const Problem &P = *problems_[id];
     st->seconds_upload = P.seconds_upload;
-    auto finish = [&](int code) {
-        st->seconds_total = now_s() - t0; st->kernel_launches = launches_;
-        st->seconds_final_device = fs_device_; st->seconds_final_host = fs_host_;
-        st->lu_dense_steps = lu_dense_; st->lu_rounds = lu_rounds_;
-        if (lu_look_fault_) st->device_retries = lu_look_fault_;   // (the final solve was repeated with the plain LU schedule)
-        return code;
-    };
-    launches_ = 0;
-    fs_device_ = fs_host_ = 0; lu_look_fault_ = 0;
-    last_trace_.clear();
-    last_trace_total_ = 0;
+    auto finish = [&](int code) { return close_stats(st, t0, code); };
+    open_stats();
     if (P.verify_status != GOMILP_OK) {  // simplex.go:94-100
-        if (P.verify_status == GOMILP_ERR_UNBOUNDED) *opt_f = -inf;
+        if (P.verify_status == GOMILP_ERR_UNBOUNDED) *opt_f = -std::numeric_limits<double>::infinity();
         return finish(P.verify_status);
     }
     const int m = P.m, n = P.n;
@@ -920,129 +979,124 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
     if (P.ld > kLdsWindowLd && (initial_basic || m >= n || !large_solve_fits(P))) return finish(GOMILP_ERR_UNSUPPORTED);
     int rc = ensure_work(m, n + 1);
     if (rc != GOMILP_OK) return finish(rc);
-    Work &w = *w_;
-    w.st_host->trace_len = 0;
-    std::vector<double> xb_exact;
-    bool singular = false;
-
-    if (m == n) {  // simplex.go:103-119: exactly constrained, one linear solve
-        std::vector<int32_t> ident(n);
-        for (int j = 0; j < n; j++) ident[j] = j;
-        if ((rc = upload_index_lists(ident, {})) != GOMILP_OK) return finish(rc);
-        const double t1 = now_s();
-        if ((rc = final_solve(P, xb_exact, &singular)) != GOMILP_OK) return finish(rc);
-        st->seconds_final_solve = now_s() - t1;
-        if (singular) return finish(GOMILP_ERR_SINGULAR);
-        if (cond_guard_ && !P.hA.empty() && n <= 1024) {   // cond > 1e16 is a Condition too: lp.ErrSingular (simplex.go:109-112)
-            st->cond_fallbacks++;
-            const double kinf = general_cond_inf(P.hA, n);
-            if (kinf > 1e16 || kinf != kinf) return finish(GOMILP_ERR_SINGULAR);
-        }
-        for (int j = 0; j < n; j++)
-            if (xb_exact[j] < 0) return finish(GOMILP_ERR_INFEASIBLE);
-        *opt_f = dot_unitary(xb_exact.data(), P.hc.data(), n);
-        memcpy(opt_x, xb_exact.data(), sizeof(double) * (size_t)n);
-        *has_x = 1;
-        return finish(GOMILP_OK);
-    }
+    w_->st_host->trace_len = 0;
+    if (m == n) return finish(solve_square(P, opt_f, opt_x, has_x, st));
     if (m > n) return finish(GOMILP_ERR_SINGULAR);  // findLinearlyIndependent cannot reach m columns (:495-497)
 
-    // findLinearlyIndependent (simplex.go:611-637), unit-column fast path: the descending scan meets m distinct
-    // unit vectors (always true for GoMILP's [.. | I] standard forms, subproblem.go:81-139); cond == 1 there.
-    std::vector<int32_t> basic(m), rho(m);
-    bool unit_basis = true;
-    if (initial_basic) {
-        // supplied basis (simplex.go:147-160; GoMILP itself always passes nil): the caller hands over m entries; an index
-        // out of range panics in extractColumns, a singular or infeasible set panics in initializeFromBasic (:447-471)
-        unit_basis = false;
-        for (int pos = 0; pos < m; pos++) {
-            const int64_t j = initial_basic[pos];
-            if (j < 0 || j >= n) return finish(GOMILP_ERR_PANIC);
-            basic[pos] = (int32_t)j;
-        }
-    } else {
-        std::vector<char> used(m, 0);
-        for (int pos = 0; pos < m; pos++) {
-            const int j = n - 1 - pos;
-            if (!(P.nnz[j] == 1 && P.allone[j]) || used[P.lastrow[j]]) { unit_basis = false; break; }
-            rho[pos] = P.lastrow[j]; used[rho[pos]] = 1; basic[pos] = j;
-        }
-    }
-    if (!unit_basis && P.ld > kLdsWindowLd) return finish(GOMILP_ERR_UNSUPPORTED);   // (the general start's search and set-up stage m-long rows)
-    gen_start_ = !unit_basis;
+    Start s;
+    if ((rc = scan_start(P, initial_basic, s)) != GOMILP_OK) return finish(rc);
+    plan_ = SolvePlan::make(m, n, P.ld, s.slack ? SolvePlan::Slack : initial_basic ? SolvePlan::Supplied : SolvePlan::Searched, P.scale_span, knobs_);
+    if (plan_.status != GOMILP_OK || (plan_.needs_host_A && !ensure_host_A(P))) return finish(GOMILP_ERR_UNSUPPORTED);
     gen_binv_dev_ = false;
-    struct RouteReset { Engine *e; ~RouteReset() { e->gen_revised_ = false; e->lp_guard_ = 0.0; } } route_reset{this};   // (per solve)
     exact_xb_.clear();
-    badly_scaled_ = P.scale_span > 1e9;
-    const int nn_max = n + 1 - m;
-    // a non-slack starting basis (equality rows, supplied basis) takes the tableau pipelines wherever their row fits: their set-up
-    // accepts any B^-1; the n - m < 2m rule is only the bytes-per-pivot trade-off between the two formulations.  So does a wide LP whose
-    // exact_degenerate mode asks for exact steps on this problem (the predicate of make_bt_args' guard, engine_tableau.cpp) when the
-    // BLOCKED tableau takes it: on slack starts only the block kernels stop in front of a degenerate pivot (ST_NEED_EXACT) for
-    // Engine::exact_step — the single-kernel tableau and the revised pipelines decide every pivot on their updated quantities.
-    // (tableau = 0 keeps the revised pipelines, blocked = 0 the n - m < 2m rule, both without the guard on slack starts: A/B knobs.)
-    const bool tab_fits = (size_t)tab_ld(nn_max) * sizeof(double) <= 64 * 1024;
-    const bool bt_ok = blocked_ && bt_supported(m, nn_max);
-    const bool exact_wanted = exact_degenerate_ == 3 || exact_degenerate_ == 2 || (exact_degenerate_ == 1 && (m <= 256 || !unit_basis || badly_scaled_));
-    // (beyond the LDS window only the three-kernel revised simplex runs: the single-kernel tableau returned a wrong ErrUnbounded on a
-    // 12288 x 18432 slack start after a run of Bland steps — DESIGN.md §2.1, "Beyond 8192 rows")
-    const bool use_tab = tableau_ && ((n - m) < 2 * m || !unit_basis || (exact_wanted && bt_ok)) && tab_fits && P.ld <= kLdsWindowLd;
-    // A non-slack start the tableau does not take (its row beyond the LDS window: n - m > 8191, or knob tableau = 0) runs the
-    // three-kernel revised loop with the exact-step guard of make_bt_args for general starts (LPArgs::guard; the fused pipeline has
-    // none): the exact steps need the host copy of A, kept up to m * n = 2^25
-    const bool gen_rev = !unit_basis && !use_tab && (size_t)m * (size_t)n <= ((size_t)1 << 25) && ensure_host_A(P);
-    // strict mode IS the exact steps: where neither the blocked tableau nor that loop runs, the solve refuses instead of deciding the
-    // default way
-    if (exact_degenerate_ == 3 && !(use_tab && bt_ok) && !gen_rev) return finish(GOMILP_ERR_UNSUPPORTED);
-    if (gen_rev) {
-        gen_revised_ = true;
-        lp_guard_ = exact_degenerate_ == 3 ? inf : exact_degenerate_ == 0 ? 0.0 : 1e-9;
-    }
-    std::vector<double> xb(m, 0.0), binv_host;
-    bool feasible = true;
-    if (unit_basis) {
-        // ab = permutation, xb = ab^-1 b exactly (initializeFromBasic, simplex.go:447-471)
-        for (int pos = 0; pos < m; pos++) { xb[pos] = P.hb[rho[pos]]; if (xb[pos] < -1e-13) feasible = false; }
-    } else {
-        // general case (engine_general.cpp): host search over a kept copy of A; the tableau pipelines, or the guarded revised loop
-        if (!(use_tab || gen_rev) || !ensure_host_A(P)) return finish(GOMILP_ERR_UNSUPPORTED);
-        const double t_g0 = now_s();
-        if (!initial_basic) {
-            // 96 rows and more (knob general_min_rows): the scan runs on the device — whole solves with the host / the blocked device search,
-            // tools/general_small.py: 64 rows 0.96 / 1.08 ms, 96: 1.54 / 1.51, 128: 2.28 / 1.85, 180: 4.5 / 2.9, 224: 6.8 / 3.4, 300: 11.1 / 4.5
-            // (until round 5, five launches per candidate: 224 rows)
-            rc = (m >= general_min_rows_ && general_device_) ? find_independent_device(P, basic, &binv_host, &gen_binv_dev_) : general_find_linearly_independent(P.hA, m, n, basic, &binv_host);
-            if (rc != GOMILP_OK) return finish(rc);  // ErrSingular, simplex.go:495-497
-        }
-        const double t_g1 = now_s();
-        if (!gen_binv_dev_ && binv_host.size() != (size_t)m * m && !general_basis_inverse(P.hA, m, n, basic, n, std::vector<double>(), binv_host))
-            return finish(initial_basic ? GOMILP_ERR_PANIC : GOMILP_ERR_SINGULAR);
-        const double t_g2 = now_s();
-        // xb = ab^-1 b with the reference's own arithmetic (gonum-order LU on the device): the feasibility test of
-        // simplex.go:459-469 then sees the same bits
-        if ((rc = upload_index_lists(basic, {})) != GOMILP_OK) return finish(rc);
-        bool sing = false;
-        if ((rc = final_solve(P, xb_exact, &sing)) != GOMILP_OK) return finish(rc);
-        if (sing) { feasible = false; }  // "singular" also sends the reference to Phase I (simplex.go:504-507), xb stays zero
-        else { xb = xb_exact; for (int pos = 0; pos < m; pos++) if (xb[pos] < -1e-13) feasible = false; }
-        if (initial_basic && !feasible) return finish(GOMILP_ERR_PANIC);  // initializeFromBasic errors panic (:156-158)
-        if (GOMILP_DBG_ENV("GOMILP_DEBUG_GS")) fprintf(stderr, "general start: search %.2f ms, host inverse %.2f ms, x_B (gonum-order LU) %.2f ms\n", 1e3 * (t_g1 - t_g0), 1e3 * (t_g2 - t_g1), 1e3 * (now_s() - t_g2));
-    }
+    if (!s.slack && (rc = search_start(P, initial_basic != nullptr, s)) != GOMILP_OK) return finish(rc);
     // small bases starting feasible: record the pivots for the host replay of the reference's condition guards
     // (every pipeline: until round 5 the revised-simplex pipelines — shapes with n - m >= 2m, wide small LPs among them — went without the
     // replay, which is what the one status difference of the badly scaled family, seed 1079, a 2 x 6 LP, came from)
-    shadow_trace_ = cond_guard_ && feasible && m <= 64 && !initial_basic && ensure_host_A(P);
-    const std::vector<int32_t> basic_start = basic;
+    shadow_trace_ = plan_.replay_if_feasible && s.feasible && ensure_host_A(P);
+    const std::vector<int32_t> basic_start = s.basic;
+    if ((rc = upload_start(P, s)) != GOMILP_OK) return finish(rc);
+    st->pipeline = plan_.pipeline;
+    int loop_rc = GOMILP_OK;
+    rc = plan_.use_tab ? solve_tableau(P, tol, s, st, &loop_rc) : solve_revised(P, tol, s, st, &loop_rc);
+    if (rc != GOMILP_OK) return finish(rc);
+    return finish(solve_tail(P, id, loop_rc, s.basic, s.xb, basic_start, s.slack ? &s.rho : nullptr, opt_f, opt_x, has_x, basis_out, st));
+}
+
+int Engine::solve_square(const Problem &P, double *opt_f, double *opt_x, int32_t *has_x, gomilp_lp_stats *st) {  // simplex.go:103-119: exactly constrained, one linear solve
+    const int n = P.n;
+    std::vector<int32_t> ident(n);
+    for (int j = 0; j < n; j++) ident[j] = j;
+    int rc = upload_index_lists(ident, {});
+    if (rc != GOMILP_OK) return rc;
+    std::vector<double> xb_exact;
+    bool singular = false;
+    const double t1 = now_s();
+    if ((rc = final_solve(P, xb_exact, &singular)) != GOMILP_OK) return rc;
+    st->seconds_final_solve = now_s() - t1;
+    if (singular) return GOMILP_ERR_SINGULAR;
+    if (knobs_.cond_guard && !P.hA.empty() && n <= 1024) {   // cond > 1e16 is a Condition too: lp.ErrSingular (simplex.go:109-112)
+        st->cond_fallbacks++;
+        const double kinf = general_cond_inf(P.hA, n);
+        if (kinf > 1e16 || kinf != kinf) return GOMILP_ERR_SINGULAR;
+    }
+    for (int j = 0; j < n; j++)
+        if (xb_exact[j] < 0) return GOMILP_ERR_INFEASIBLE;
+    *opt_f = dot_unitary(xb_exact.data(), P.hc.data(), n);
+    memcpy(opt_x, xb_exact.data(), sizeof(double) * (size_t)n);
+    *has_x = 1;
+    return GOMILP_OK;
+}
+
+// findLinearlyIndependent (simplex.go:611-637), unit-column fast path: the descending scan meets m distinct unit vectors (always true
+// for GoMILP's [.. | I] standard forms, subproblem.go:81-139); cond == 1 there, ab = permutation, xb = ab^-1 b exactly
+// (initializeFromBasic, simplex.go:447-471).  A supplied basis (simplex.go:147-160; GoMILP itself always passes nil): the caller hands
+// over m entries; an index out of range panics in extractColumns, a singular or infeasible set in initializeFromBasic
+int Engine::scan_start(const Problem &P, const int64_t *initial_basic, Start &s) {
+    const int m = P.m, n = P.n;
+    s.basic.assign(m, 0); s.rho.assign(m, 0); s.xb.assign(m, 0.0);
+    if (initial_basic) {
+        s.slack = false;
+        for (int pos = 0; pos < m; pos++) {
+            const int64_t j = initial_basic[pos];
+            if (j < 0 || j >= n) return GOMILP_ERR_PANIC;
+            s.basic[pos] = (int32_t)j;
+        }
+        return GOMILP_OK;
+    }
+    std::vector<char> used(m, 0);
+    for (int pos = 0; pos < m; pos++) {
+        const int j = n - 1 - pos;
+        if (!(P.nnz[j] == 1 && P.allone[j]) || used[P.lastrow[j]]) { s.slack = false; return GOMILP_OK; }
+        s.rho[pos] = P.lastrow[j]; used[s.rho[pos]] = 1; s.basic[pos] = j;
+    }
+    for (int pos = 0; pos < m; pos++) { s.xb[pos] = P.hb[s.rho[pos]]; if (s.xb[pos] < -1e-13) s.feasible = false; }
+    return GOMILP_OK;
+}
+
+// general case (engine_general.cpp): search over a kept copy of A, for the tableau pipelines or the guarded revised loop
+int Engine::search_start(const Problem &P, bool supplied, Start &s) {
+    const int m = P.m, n = P.n;
+    int rc;
+    const double t_g0 = now_s();
+    if (!supplied) {
+        // 96 rows and more (knob general_min_rows): the scan runs on the device — whole solves with the host / the blocked device search,
+        // tools/general_small.py: 64 rows 0.96 / 1.08 ms, 96: 1.54 / 1.51, 128: 2.28 / 1.85, 180: 4.5 / 2.9, 224: 6.8 / 3.4, 300: 11.1 / 4.5
+        // (until round 5, five launches per candidate: 224 rows)
+        rc = plan_.search_on_device ? find_independent_device(P, s.basic, &s.binv_host, &gen_binv_dev_) : general_find_linearly_independent(P.hA, m, n, s.basic, &s.binv_host);
+        if (rc != GOMILP_OK) return rc;  // ErrSingular, simplex.go:495-497
+    }
+    const double t_g1 = now_s();
+    if (!gen_binv_dev_ && s.binv_host.size() != (size_t)m * m && !general_basis_inverse(P.hA, m, n, s.basic, n, std::vector<double>(), s.binv_host))
+        return supplied ? GOMILP_ERR_PANIC : GOMILP_ERR_SINGULAR;
+    const double t_g2 = now_s();
+    // xb = ab^-1 b with the reference's own arithmetic (gonum-order LU on the device): the feasibility test of
+    // simplex.go:459-469 then sees the same bits
+    if ((rc = upload_index_lists(s.basic, {})) != GOMILP_OK) return rc;
+    std::vector<double> xb_exact;
+    bool sing = false;
+    if ((rc = final_solve(P, xb_exact, &sing)) != GOMILP_OK) return rc;
+    if (sing) { s.feasible = false; }  // "singular" also sends the reference to Phase I (simplex.go:504-507), xb stays zero
+    else { s.xb = xb_exact; for (int pos = 0; pos < m; pos++) if (s.xb[pos] < -1e-13) s.feasible = false; }
+    if (supplied && !s.feasible) return GOMILP_ERR_PANIC;  // initializeFromBasic errors panic (:156-158)
+    if (GOMILP_DBG_ENV("GOMILP_DEBUG_GS")) fprintf(stderr, "general start: search %.2f ms, host inverse %.2f ms, x_B (gonum-order LU) %.2f ms\n", 1e3 * (t_g1 - t_g0), 1e3 * (t_g2 - t_g1), 1e3 * (now_s() - t_g2));
+    return GOMILP_OK;
+}
+
+int Engine::upload_start(const Problem &P, const Start &s) {
+    Work &w = *w_;
+    const int m = P.m;
+    int rc;
     cur_ = 0;
-    if (unit_basis && !use_tab) {
+    if (s.slack && !plan_.use_tab) {
         HIP_TRY(hipMemsetAsync(w.binv[0], 0, (size_t)m * P.ld * sizeof(double), stream_));
-        if ((rc = stage_upload(w.rho, rho.data(), (size_t)m * sizeof(int32_t))) != GOMILP_OK) return finish(rc);
+        if ((rc = stage_upload(w.rho, s.rho.data(), (size_t)m * sizeof(int32_t))) != GOMILP_OK) return rc;
         launch_set_binv_perm(w.binv[0], P.ld, m, w.rho, stream_);
     }
-    if (gen_rev) {   // the searched (or supplied) basis' B^-1: in place from the device search, else the host's (the tableau set-up's copy)
+    if (plan_.gen_revised) {   // the searched (or supplied) basis' B^-1: in place from the device search, else the host's (the tableau set-up's copy)
         if (!gen_binv_dev_) {
             HIP_TRY(hipMemsetAsync(w.binv[0], 0, (size_t)m * P.ld * sizeof(double), stream_));
-            HIP_TRY(hipMemcpy2DAsync(w.binv[0], (size_t)P.ld * sizeof(double), binv_host.data(), (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
+            HIP_TRY(hipMemcpy2DAsync(w.binv[0], (size_t)P.ld * sizeof(double), s.binv_host.data(), (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
                                      hipMemcpyHostToDevice, stream_));
             HIP_TRY(sync_stream());   // (pageable source)
         } else if (P.ld > m) {   // (the K1-K3 rows run over the padding column too)
@@ -1050,90 +1104,92 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
         }
     }
     ycur_ = 0;
-    if (!use_tab) {   // the duals only exist on the revised-simplex pipelines
+    if (!plan_.use_tab) {   // the duals only exist on the revised-simplex pipelines
         HIP_TRY(hipMemsetAsync(w.yb[0], 0, (size_t)P.ld * sizeof(double), stream_));
         HIP_TRY(hipMemsetAsync(w.yb[1], 0, (size_t)P.ld * sizeof(double), stream_));
     }
-    {   // x_B with its zero padding in one copy
-        std::vector<double> xpad(P.ld, 0.0);
-        std::copy(xb.begin(), xb.begin() + m, xpad.begin());
-        if ((rc = stage_upload(w.xb, xpad.data(), (size_t)P.ld * sizeof(double))) != GOMILP_OK) return finish(rc);
-    }
+    return upload_padded(w.xb, s.xb, P.ld);
+}
 
-    // pipeline choice: the explicit tableau moves 16*m*(n-m) bytes per pivot in one launch, the revised form
-    // 8*[m(n-m) + 2m^2] in two: the tableau wins while n - m < 2m
-    use_bt_ = use_tab && bt_ok;
-    st->pipeline = use_tab ? (use_bt_ ? 3 : 2) : ((fused_ && fused_supported(P.ld) && !gen_rev) ? 1 : 0);
-    int loop_rc = GOMILP_OK;
-    if (use_tab) {
-        const int ldt = tab_ld(nn_max);
-        if (w.cap_T < (size_t)(m + 3) * ldt || w.cap_ldt < ldt) {   // + 3 rows: the tiled layout pads m to a multiple of 4
-            for (double **pp : {&w.T[0], &w.T[1], &w.R[0], &w.R[1], &w.tscratch, &w.btV}) { if (*pp) hipFree(*pp); *pp = nullptr; }
-            if (w.srcpos) hipFree(w.srcpos); w.srcpos = nullptr;
-            const size_t cap = std::max(w.cap_T, (size_t)(m + 3 + 32 + m / 16) * ldt);   // head-room for deeper children
-            const int cl = std::max(w.cap_ldt, ldt);
-            HIP_TRY(dmalloc(&w.T[0], cap)); HIP_TRY(dmalloc(&w.T[1], cap));
-            HIP_TRY(dmalloc(&w.R[0], (size_t)cl)); HIP_TRY(dmalloc(&w.R[1], (size_t)cl));
-            HIP_TRY(dmalloc(&w.tscratch, (size_t)64 * cl)); HIP_TRY(dmalloc(&w.srcpos, (size_t)cl));
-            HIP_TRY(dmalloc(&w.btV, (size_t)bt_max_k() * cl));
-            w.cap_T = cap; w.cap_ldt = cl; w.cap_btU = 0;
-        }
-        // the rank-1 u terms are rows of P.ld doubles: sized by the ROW count, which can grow while the T buffers
-        // (sized by m * ldt) still fit — a wide problem followed by a taller, narrower one on the same context
-        if (w.cap_btU < (size_t)bt_max_k() * (size_t)P.ld) {
-            if (w.btU) hipFree(w.btU); w.btU = nullptr;
-            const size_t cap = (size_t)bt_max_k() * (size_t)std::max(w.cap_ld, P.ld);
-            HIP_TRY(dmalloc(&w.btU, cap));
-            w.cap_btU = cap;
-        }
-        if (use_bt_ && !w.xbuf) {   // exchange records of the multi-workgroup block kernel: zero = no exchange has happened
-            HIP_TRY(dmalloc(&w.xbuf, bt_xbuf_doubles()));
-            HIP_TRY(hipMemsetAsync(w.xbuf, 0, bt_xbuf_doubles() * sizeof(double), stream_));
-        }
-        if (!use_bt_) {   // the blocked kernels never read the padding of r
-            HIP_TRY(hipMemsetAsync(w.R[0], 0, (size_t)w.cap_ldt * sizeof(double), stream_));
-            HIP_TRY(hipMemsetAsync(w.R[1], 0, (size_t)w.cap_ldt * sizeof(double), stream_));
-        }
-        rc = solve_tableau(P, tol, basic, rho, xb, feasible, st, &loop_rc, unit_basis ? nullptr : &binv_host);
-        if (rc != GOMILP_OK) return finish(rc);
+int Engine::upload_padded(double *dst, const std::vector<double> &v, int ld) {   // v with its zero padding in one copy
+    std::vector<double> pad(ld, 0.0);
+    std::copy(v.begin(), v.end(), pad.begin());
+    return stage_upload(dst, pad.data(), (size_t)ld * sizeof(double));
+}
+
+void build_nonbasic(const std::vector<int32_t> &basic, int ncols, std::vector<int32_t> &nonbasic) {
+    std::vector<char> inb(ncols, 0);
+    for (int32_t j : basic) inb[j] = 1;
+    nonbasic.clear();
+    for (int j = 0; j < ncols; j++) if (!inb[j]) nonbasic.push_back(j);
+}
+
+// for unit columns one exact "- 1" per row (floats.Sub, :536-542); a searched basis subtracts its full columns, on the device from
+// general_min_rows on (k_gs_art: the same subtractions, element by element)
+int Engine::phase1_artificial(const Problem &P, const Start &s, int64_t minidx, std::vector<double> &art, gomilp_lp_stats *st) {
+    Work &w = *w_;
+    const int m = P.m, n = P.n;
+    double *row = P.dAt + (size_t)n * P.ld;
+    for (int k = 0; k < m; k++) art[k] = P.hb[k];
+    if (s.slack) {
+        for (int i = 0; i < m; i++) { if (i == minidx) continue; art[s.rho[i]] = -1 * 1.0 + art[s.rho[i]]; }
+    } else if (plan_.art_on_device) {
+        launch_gs_art(P.dAt, P.ld, m, w.basic, (int)minidx, P.db, row, stream_);
+        launches_++;
+        HIP_TRY(hipMemcpyAsync(art.data(), row, (size_t)P.ld * sizeof(double), hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(sync_stream());
     } else {
-    std::vector<int32_t> nonbasic;
-    auto build_nonbasic = [&](int ncols) {  // simplex.go:174-184: ascending ids not in the basis
-        std::vector<char> inb(ncols, 0);
-        for (int i = 0; i < m; i++) inb[basic[i]] = 1;
-        nonbasic.clear();
-        for (int j = 0; j < ncols; j++) if (!inb[j]) nonbasic.push_back(j);
-    };
+        for (int i = 0; i < m; i++) {
+            if (i == minidx) continue;
+            for (int k = 0; k < m; k++) art[k] = -1 * P.hA[(size_t)k * n + s.basic[i]] + art[k];
+        }
+    }
+    bool art_zero = true;
+    for (int k = 0; k < m; k++) if (art[k] != 0) { art_zero = false; break; }
+    if (art_zero) { st->wrapped_status = GOMILP_ERR_ZERO_COLUMN; return GOMILP_ERR_PHASE1_WRAPPED; }  // verifyInputs of the recursive call
+    return plan_.art_on_device ? GOMILP_OK : stage_upload(row, art.data(), (size_t)P.ld * sizeof(double));
+}
 
-    if (!feasible) {
+int Engine::phase1_art_level(const Problem &P, int added, const std::vector<double> &xb) {
+    double xart = added >= 0 ? xb[added] : 0.0;
+    if (added >= 0 && fabs(xart) > 1e-13 && fabs(xart) < 1e-11) {
+        // too close to phaseIZeroTol to trust the updated x_B: take the reference's own value (fresh gonum-order solve)
+        std::vector<double> xe;
+        bool sing = false;
+        const int rc = final_solve(P, xe, &sing);
+        if (rc != GOMILP_OK) return rc;
+        if (!sing) xart = xe[added];
+    }
+    return fabs(xart) > 1e-12 ? GOMILP_ERR_INFEASIBLE : GOMILP_OK;  // phaseIZeroTol, :563-565
+}
+
+// keeps the basis nonsingular — a guard on the pivot element instead of the LU condition estimate — and x_B feasible
+bool exchange_keeps_feasible(const double *dcol, const std::vector<double> &xb, int added, int m) {
+    double dmax = 0;
+    for (int i = 0; i < m; i++) dmax = std::max(dmax, fabs(dcol[i]));
+    const double dpv = dcol[added];
+    if (!(fabs(dpv) > 1e-9 * std::max(1.0, dmax))) return false;
+    const double theta = xb[added] / dpv;
+    for (int i = 0; i < m; i++) {
+        const double v = (i == added) ? theta : xb[i] - theta * dcol[i];
+        if (v < -1e-13) return false;
+    }
+    return true;
+}
+
+int Engine::solve_revised(const Problem &P, double tol, Start &s, gomilp_lp_stats *st, int *loop_rc) {
+    Work &w = *w_;
+    const int m = P.m, n = P.n;
+    std::vector<int32_t> &basic = s.basic;
+    std::vector<double> &xb = s.xb;
+    std::vector<int32_t> nonbasic;
+    int rc;
+    if (!s.feasible) {
         // ---- Phase I (simplex.go:529-606) ----
         st->phase1_used = 1;
         const int64_t minidx = min_idx(xb.data(), m);
-        // a_{n+1} = b - sum_{i != minidx} a_{basic_i}: for unit columns one exact "- 1" per row (floats.Sub, :536-542); a searched basis
-        // subtracts its full columns, on the device from general_min_rows on (k_gs_art, as solve_tableau)
-        std::vector<double> art(P.ld, 0.0);
-        const bool art_on_device = gen_rev && m >= general_min_rows_;
-        for (int k = 0; k < m; k++) art[k] = P.hb[k];
-        if (unit_basis) {
-            for (int i = 0; i < m; i++) { if (i == minidx) continue; art[rho[i]] = -1 * 1.0 + art[rho[i]]; }
-        } else if (art_on_device) {   // (w.basic holds the searched basis: uploaded for the x_B solve)
-            launch_gs_art(P.dAt, P.ld, m, w.basic, (int)minidx, P.db, P.dAt + (size_t)n * P.ld, stream_);
-            launches_++;
-            HIP_TRY(hipMemcpyAsync(art.data(), P.dAt + (size_t)n * P.ld, (size_t)P.ld * sizeof(double), hipMemcpyDeviceToHost, stream_));
-            HIP_TRY(sync_stream());
-        } else {
-            for (int i = 0; i < m; i++) {
-                if (i == minidx) continue;
-                for (int k = 0; k < m; k++) art[k] = -1 * P.hA[(size_t)k * n + basic[i]] + art[k];
-            }
-        }
-        bool art_zero = true;
-        for (int k = 0; k < m; k++) if (art[k] != 0) { art_zero = false; break; }
-        if (art_zero) { st->wrapped_status = GOMILP_ERR_ZERO_COLUMN; return finish(GOMILP_ERR_PHASE1_WRAPPED); }  // verifyInputs of the recursive call
-        if (!art_on_device) {
-            HIP_TRY(hipMemcpyAsync(P.dAt + (size_t)n * P.ld, art.data(), (size_t)P.ld * sizeof(double), hipMemcpyHostToDevice, stream_));
-            HIP_TRY(sync_stream());
-        }
+        std::vector<double> art(P.ld, 0.0);   // (w.basic holds a searched basis: uploaded for the x_B solve)
+        if ((rc = phase1_artificial(P, s, minidx, art, st)) != GOMILP_OK) return rc;
         // basis := slack basis with position minidx replaced by the artificial: one forced pivot builds its inverse
         w.st_host->done = 0; w.st_host->status = ST_RUNNING; w.st_host->pivots = 0; w.st_host->max_pivots = 0; w.st_host->rq = 0;
         sync_state_to_device();
@@ -1145,35 +1201,28 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
             cur_ ^= 1;
         }
         basic[minidx] = n;
-        build_nonbasic(n + 1);
-        if ((rc = upload_index_lists(basic, nonbasic)) != GOMILP_OK) return finish(rc);
+        build_nonbasic(basic, n + 1, nonbasic);
+        if ((rc = upload_index_lists(basic, nonbasic)) != GOMILP_OK) return rc;
         refresh_xb_y(P, P.dc1);  // xb = ab^-1 b (initializeFromBasic of the recursive call), y = ab^-T cb
         HIP_TRY(hipMemcpyAsync(w.h_vec, w.xb, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
         HIP_TRY(sync_stream());
-        for (int i = 0; i < m; i++) if (w.h_vec[i] < -1e-13) return finish(GOMILP_ERR_PANIC);  // simplex.go:155-158
+        for (int i = 0; i < m; i++) if (w.h_vec[i] < -1e-13) return GOMILP_ERR_PANIC;  // simplex.go:155-158
         rc = run_loop(P, 1, 1e-10, (int)nonbasic.size(), P.dc1, st);
-        if (rc == GOMILP_ERR_DEVICE) return finish(rc);
-        if (rc != GOMILP_OK) { st->wrapped_status = rc; return finish(GOMILP_ERR_PHASE1_WRAPPED); }  // :557-559
+        if (rc == GOMILP_ERR_DEVICE) return rc;
+        if (rc != GOMILP_OK) { st->wrapped_status = rc; return GOMILP_ERR_PHASE1_WRAPPED; }  // :557-559
         HIP_TRY(hipMemcpyAsync(w.h_idx, w.basic, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
         HIP_TRY(hipMemcpyAsync(w.h_vec, w.xb, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
         HIP_TRY(sync_stream());
         int added = -1;
         for (int i = 0; i < m; i++) { basic[i] = w.h_idx[i]; xb[i] = w.h_vec[i]; if (basic[i] == n) added = i; }
-        double xart = added >= 0 ? xb[added] : 0.0;
-        if (added >= 0 && fabs(xart) > 1e-13 && fabs(xart) < 1e-11) {
-            // too close to phaseIZeroTol to trust the updated x_B: take the reference's own value (fresh gonum-order solve)
-            if ((rc = final_solve(P, xb_exact, &singular)) != GOMILP_OK) return finish(rc);
-            if (!singular) xart = xb_exact[added];
-        }
-        if (fabs(xart) > 1e-12) return finish(GOMILP_ERR_INFEASIBLE);  // phaseIZeroTol, :563-565
+        if ((rc = phase1_art_level(P, added, xb)) != GOMILP_OK) return rc;
         if (added >= 0) {
             // :581-606 the artificial stayed basic at zero: exchange it for the first nonbasic column that keeps
-            // the basis nonsingular and feasible.  Guard on the pivot element instead of the LU condition estimate.
+            // the basis nonsingular and feasible
             bool exchanged = false;
-            std::vector<char> inb(n + 1, 0);
-            for (int i = 0; i < m; i++) inb[basic[i]] = 1;
-            for (int j = 0; j < n && !exchanged; j++) {
-                if (inb[j]) continue;
+            build_nonbasic(basic, n + 1, nonbasic);   // (the artificial is basic: structural columns only)
+            for (size_t c = 0; c < nonbasic.size() && !exchanged; c++) {
+                const int j = nonbasic[c];
                 w.st_host->done = 0; w.st_host->status = ST_RUNNING; w.st_host->rq = 0;
                 sync_state_to_device();
                 LPArgs a = make_args(P, 1, 1e-10, 0, P.dc1);
@@ -1181,17 +1230,7 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
                 launches_++;
                 HIP_TRY(hipMemcpyAsync(w.h_vec, w.dvec, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
                 HIP_TRY(sync_stream());
-                double dmax = 0;
-                for (int i = 0; i < m; i++) dmax = std::max(dmax, fabs(w.h_vec[i]));
-                const double dpv = w.h_vec[added];
-                if (!(fabs(dpv) > 1e-9 * std::max(1.0, dmax))) continue;
-                const double theta = xb[added] / dpv;
-                bool feas = true;
-                for (int i = 0; i < m && feas; i++) {
-                    const double v = (i == added) ? theta : xb[i] - theta * w.h_vec[i];
-                    if (v < -1e-13) feas = false;
-                }
-                if (!feas) continue;
+                if (!exchange_keeps_feasible(w.h_vec, xb, added, m)) continue;
                 launch_update(a, 0, added, 1, 0, stream_);
                 launches_++;
                 cur_ ^= 1;
@@ -1199,23 +1238,31 @@ int Engine::solve_locked(int64_t id, double tol, const int64_t *initial_basic, d
                 exchanged = true;
                 st->art_exchanges++;
             }
-            if (!exchanged) return finish(GOMILP_ERR_INFEASIBLE);  // :606
+            if (!exchanged) return GOMILP_ERR_INFEASIBLE;  // :606
         }
     }
 
     // ---- Phase II (simplex.go:169-293) ----
-    build_nonbasic(n);
-    if ((rc = upload_index_lists(basic, nonbasic)) != GOMILP_OK) return finish(rc);
+    build_nonbasic(basic, n, nonbasic);
+    if ((rc = upload_index_lists(basic, nonbasic)) != GOMILP_OK) return rc;
     if (st->phase1_used) {
         refresh_xb_y(P, P.dc);
     } else {
         launch_y_from_binv(w.binv[cur_], P.ld, m, P.dc, w.basic, w.yscratch, w.yb[ycur_], stream_);
         launches_ += 2;
     }
-    loop_rc = run_loop(P, 2, tol, (int)nonbasic.size(), P.dc, st);
-    }  // revised-simplex pipelines
-    rc = solve_tail(P, id, loop_rc, basic, xb, basic_start, unit_basis ? &rho : nullptr, opt_f, opt_x, has_x, basis_out, st);
-    return finish(rc);
+    *loop_rc = run_loop(P, 2, tol, (int)nonbasic.size(), P.dc, st);
+    return GOMILP_OK;
+}
+
+int Engine::fetch_trace(std::vector<DevPivot> &tr) {
+    Work &w = *w_;
+    HIP_TRY(hipMemcpyAsync(w.st_host, w.st, sizeof(DevState), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(sync_stream());
+    const int64_t cnt = std::min<int64_t>(w.st_host->trace_len, w.trace_cap);
+    tr.resize((size_t)cnt);
+    if (cnt) HIP_TRY(hipMemcpy(tr.data(), w.trace, (size_t)cnt * sizeof(DevPivot), hipMemcpyDeviceToHost));
+    return GOMILP_OK;
 }
 
 int Engine::solve_tail(const Problem &P, int64_t id, int loop_rc, std::vector<int32_t> &basic, std::vector<double> &xb,
@@ -1233,13 +1280,11 @@ int Engine::solve_tail(const Problem &P, int64_t id, int loop_rc, std::vector<in
     HIP_TRY(hipMemcpyAsync(w.h_vec, w.xb, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(sync_stream());
     for (int i = 0; i < m; i++) { basic[i] = w.h_idx[i]; xb[i] = w.h_vec[i]; }
+    std::vector<DevPivot> tr;
+    int rc;
     if (shadow_trace_ && (loop_rc == GOMILP_OK || loop_rc == GOMILP_ERR_BLAND || loop_unbounded)) {
         // ---- the reference's LU.Solve guards (mat/lu.go:301,321), replayed on the host with exact condition numbers
-        HIP_TRY(hipMemcpyAsync(w.st_host, w.st, sizeof(DevState), hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(sync_stream());
-        const int64_t cnt = std::min<int64_t>(w.st_host->trace_len, w.trace_cap);
-        std::vector<DevPivot> tr((size_t)cnt);
-        if (cnt) HIP_TRY(hipMemcpy(tr.data(), w.trace, (size_t)cnt * sizeof(DevPivot), hipMemcpyDeviceToHost));
+        if ((rc = fetch_trace(tr)) != GOMILP_OK) return rc;
         std::vector<std::pair<int, int>> piv;
         for (auto &e : tr) piv.emplace_back((int)e.replace, (int)e.entering);
         std::vector<int32_t> bas = basic_start;
@@ -1251,13 +1296,7 @@ int Engine::solve_tail(const Problem &P, int64_t id, int loop_rc, std::vector<in
             // the reference left its loop here with the point of that basis (simplex.go:296-301)
             std::vector<double> xs;
             if (general_solve_basis(P.hA, m, n, bas, P.hb, xs)) {
-                std::vector<double> cb(m);
-                for (int i = 0; i < m; i++) cb[i] = P.hc[bas[i]];
-                *opt_f = dot_unitary(cb.data(), xs.data(), m);
-                for (int j = 0; j < n; j++) opt_x[j] = 0;
-                for (int i = 0; i < m; i++) opt_x[bas[i]] = xs[i];
-                *has_x = 1;
-                if (basis_out) for (int i = 0; i < m; i++) basis_out[i] = bas[i];
+                return_point(P, bas, xs, opt_f, opt_x, has_x, basis_out);
                 st->pivots_phase2 = stop;
                 shadow_trace_ = false;
                 return cst;
@@ -1267,20 +1306,16 @@ int Engine::solve_tail(const Problem &P, int64_t id, int loop_rc, std::vector<in
     shadow_trace_ = false;
     if (loop_unbounded) { *opt_f = -inf; return loop_rc; }
     if (keep_id_ == id && loop_rc == GOMILP_OK) keep_capture(P, id, st->pipeline, basic, basic_start, rho_slack);
-    const int rc = epilogue(P, basic, xb, loop_rc, opt_f, opt_x, has_x, basis_out, st);
+    rc = epilogue(P, basic, xb, loop_rc, opt_f, opt_x, has_x, basis_out, st);
     if (rc == GOMILP_ERR_DEVICE) return rc;
     if (trace_on_) {
-        HIP_TRY(hipMemcpyAsync(w.st_host, w.st, sizeof(DevState), hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(sync_stream());
+        if (fetch_trace(tr) != GOMILP_OK) return GOMILP_ERR_DEVICE;
         last_trace_total_ = w.st_host->trace_len;
-        const int64_t cnt = std::min<int64_t>(last_trace_total_, w.trace_cap);
-        std::vector<DevPivot> tmp((size_t)cnt);
-        if (cnt) HIP_TRY(hipMemcpy(tmp.data(), w.trace, (size_t)cnt * sizeof(DevPivot), hipMemcpyDeviceToHost));
-        last_trace_.resize((size_t)cnt);
-        for (int64_t i = 0; i < cnt; i++) {
-            last_trace_[i].phase = tmp[i].phase; last_trace_[i].bland = tmp[i].bland;
-            last_trace_[i].min_idx = tmp[i].min_idx; last_trace_[i].replace = tmp[i].replace;
-            last_trace_[i].entering = tmp[i].entering; last_trace_[i].leaving = tmp[i].leaving;
+        last_trace_.resize(tr.size());
+        for (size_t i = 0; i < tr.size(); i++) {
+            last_trace_[i].phase = tr[i].phase; last_trace_[i].bland = tr[i].bland;
+            last_trace_[i].min_idx = tr[i].min_idx; last_trace_[i].replace = tr[i].replace;
+            last_trace_[i].entering = tr[i].entering; last_trace_[i].leaving = tr[i].leaving;
         }
     }
     return rc;
@@ -1304,14 +1339,21 @@ int Engine::epilogue(const Problem &P, std::vector<int32_t> &basic, std::vector<
     double drift = 0;
     for (int i = 0; i < m; i++) drift = std::max(drift, fabs(xb[i] - xb_exact[i]));
     st->drift_xb = drift;
+    return_point(P, basic, xb_exact, opt_f, opt_x, has_x, basis_out);
+    return loop_rc;
+}
+
+// z = DotUnitary(c_B, x_B) and the scatter of x_B into x (simplex.go:296-301)
+void Engine::return_point(const Problem &P, const std::vector<int32_t> &basic, const std::vector<double> &xb, double *opt_f, double *opt_x,
+                          int32_t *has_x, int64_t *basis_out) {
+    const int m = P.m;
     std::vector<double> cb(m);
     for (int i = 0; i < m; i++) cb[i] = P.hc[basic[i]];
-    *opt_f = dot_unitary(cb.data(), xb_exact.data(), m);
-    for (int j = 0; j < n; j++) opt_x[j] = 0;
-    for (int i = 0; i < m; i++) opt_x[basic[i]] = xb_exact[i];
+    *opt_f = dot_unitary(cb.data(), xb.data(), m);
+    for (int j = 0; j < P.n; j++) opt_x[j] = 0;
+    for (int i = 0; i < m; i++) opt_x[basic[i]] = xb[i];
     *has_x = 1;
     if (basis_out) for (int i = 0; i < m; i++) basis_out[i] = basic[i];
-    return loop_rc;
 }
 
 bool Engine::root_view(int64_t id, RootView *out) {
@@ -1360,13 +1402,11 @@ bool Engine::root_general(int64_t id, RootView *out) {
     std::vector<int32_t> basic;
     std::vector<double> binv;
     bool binv_dev = false;
-    const int rc = (m >= general_min_rows_ && general_device_) ? find_independent_device(P, basic, &binv, &binv_dev) : general_find_linearly_independent(P.hA, m, n, basic, &binv);
+    const int rc = (m >= knobs_.general_min_rows && knobs_.general_device) ? find_independent_device(P, basic, &binv, &binv_dev) : general_find_linearly_independent(P.hA, m, n, basic, &binv);
     if (rc != GOMILP_OK || (int)basic.size() != m) return false;
     if (!binv_dev && binv.size() != (size_t)m * m && !general_basis_inverse(P.hA, m, n, basic, n, std::vector<double>(), binv)) return false;
-    std::vector<char> inb(n, 0);
-    for (int i = 0; i < m; i++) inb[basic[i]] = 1;
     std::vector<int32_t> nonbasic, posvar(n);
-    for (int j = 0; j < n; j++) if (!inb[j]) nonbasic.push_back(j);
+    build_nonbasic(basic, n, nonbasic);
     const int nn = (int)nonbasic.size();
     for (int i = 0; i < m; i++) posvar[basic[i]] = i;
     for (int jp = 0; jp < nn; jp++) posvar[nonbasic[jp]] = -1 - jp;

@@ -107,6 +107,42 @@ struct BtPlan {
     static BtPlan make(int m, int ldt, const BtKnobs &k);
 };
 
+// The knobs that decide where a single solve goes (gomilp_ctx_set; the table of DESIGN.md §2.4 "Where a solve goes").
+struct SolveKnobs {
+    int64_t tableau = 1, blocked = 1, fused = 1;       // A/B knobs: 0 keeps a solve off the tableau pipelines / the block kernels / the fused revised pipeline
+    int64_t exact_degenerate = 1;                      // 0 never, 1 bases of up to 256 rows, non-slack starts and badly scaled inputs, 2 always: pivots whose winning ratio is (nearly) zero are decided on a fresh gonum-order x_B; 3 strict: EVERY pivot and the stop test are
+    int64_t cond_guard = 1;                            // the condition guards of the reference: a host replay for bases of up to 64 rows, measured from the tableau beyond
+    int64_t general_min_rows = 96, general_device = 1; // non-slack starts: from this many rows the column search and the artificial column are made on the device
+    int set(const std::string &key, int64_t v);        // GOMILP_OK, GOMILP_ERR_BAD_SHAPE (value out of range), -1: not one of these knobs
+};
+
+// Where one solve goes: ONE value, a pure function of the shape, the kind of starting basis, Problem::scale_span and the knobs above
+// (engine.cpp; no HIP call, no device query, no Problem; tests/test_solve_plan.py), made at the top of Engine::solve_locked /
+// warm_locked.  Everything downstream — set-up, make_args, make_bt_args, the loops, the tail — reads it; nothing looks at a routing knob
+// again.  What needs the device or the host copy of A (large_solve_fits, ensure_host_A) stays with the caller.
+struct SolvePlan {
+    enum StartKind : int { Slack, Searched, Supplied };   // the descending scan met m unit columns; findLinearlyIndependent; the caller's basis
+    int status = GOMILP_OK;           // GOMILP_ERR_UNSUPPORTED: nothing takes the solve (strict mode off the exact steps, non-slack starts beyond the LDS window or beyond both the tableau row and the host copy of A)
+    int pipeline = 0;                 // stats.pipeline: 0 three-kernel revised, 1 fused revised, 2 single-kernel tableau, 3 blocked tableau
+    bool use_tab = false, blocked = false;
+    bool gen_start = false;           // a searched or supplied (non-slack) basis: the degenerate-pivot guard stays on
+    bool gen_revised = false;         // ... on the three-kernel revised loop (beyond the tableau's LDS row, or knob tableau = 0)
+    bool badly_scaled = false;        // the entries of A span more than nine decades: guard on, tableau checked
+    double guard = 0.0;               // BTArgs::guard / LPArgs::guard: 0, 1e-9, or +Inf (strict); 0 on every pipeline without exact steps
+    double cguard = 0.0;              // BTArgs::cguard, and whether the exact steps and the end of the tableau loop measure the condition numbers (slack starts beyond 64 rows)
+    bool replay_if_feasible = false;  // bases of up to 64 rows: a feasible start records its pivots for the host replay of the condition guards
+    bool search_on_device = false, art_on_device = false;   // non-slack starts: the column search / the Phase-I artificial column on the device
+    bool needs_host_A = false;        // the solve cannot start without the host copy of A (Engine::ensure_host_A)
+    // does this solve decide degenerate pivots on fresh solves — the ONE statement of knob exact_degenerate (also RevBatchEngine::eligible,
+    // BatchEngine).  Non-slack starts: a tree's repeated branch rows make nearly dependent tableau rows on equality forms, and a pivot on
+    // their 1e-12 drift walks into a singular basis; badly scaled inputs: the updated tableau loses digits, the exact steps check and rebuild it
+    static bool exact_wanted(int64_t mode, int m, bool slack_start, double scale_span) {
+        return mode == 3 || mode == 2 || (mode == 1 && (m <= 256 || !slack_start || scale_span > 1e9));
+    }
+    static SolvePlan make(int m, int n, int ld, StartKind start, double scale_span, const SolveKnobs &k);   // m < n
+    static SolvePlan warm(int ld, double scale_span, const SolveKnobs &k);   // the dual loop + Phase II of a warm start: the revised pipelines, no guard
+};
+
 class Engine {
    public:
     explicit Engine(int device);
@@ -219,9 +255,32 @@ class Engine {
     TabArgs make_tab_args(const Problem &P, int phase, double tol, int nn);
     int tab_forced_pivot(const Problem &P, int phase, double tol, int nn, int q, int ent, double rq, int p, double dp, double xp,
                          int lea, int flags, long long t);
-    int solve_tableau(const Problem &P, double tol, std::vector<int32_t> &basic, const std::vector<int32_t> &rho,
-                      std::vector<double> &xb, bool feasible, gomilp_lp_stats *st, int *loop_rc,
-                      const std::vector<double> *binv_host);
+    // The stages of solve_locked between the plan and solve_tail.  Start: the starting basis as the reference builds it
+    struct Start {
+        std::vector<int32_t> basic, rho;   // positions; slack start: the row of each position's unit column
+        std::vector<double> xb, binv_host; // x_B = ab^-1 b; non-slack start: B^-1 from the host (empty when it is resident: gen_binv_dev_)
+        bool slack = true, feasible = true;
+    };
+    int solve_square(const Problem &P, double *opt_f, double *opt_x, int32_t *has_x, gomilp_lp_stats *st);   // m == n: one linear solve
+    int scan_start(const Problem &P, const int64_t *initial_basic, Start &s);    // the unit-column scan, or the caller's basis
+    int search_start(const Problem &P, bool supplied, Start &s);                 // non-slack: column search, B^-1, x_B and its feasibility
+    int upload_start(const Problem &P, const Start &s);                          // B^-1 / duals of the revised pipelines, x_B
+    // Phase I / Phase II of the revised pipelines (engine.cpp) and of the tableau pipelines (engine_tableau.cpp): on return s.basic /
+    // s.xb hold the final basis positions and updated x_B, *loop_rc the Phase-II loop result
+    int solve_revised(const Problem &P, double tol, Start &s, gomilp_lp_stats *st, int *loop_rc);
+    int solve_tableau(const Problem &P, double tol, Start &s, gomilp_lp_stats *st, int *loop_rc);
+    int ensure_tableau_work(const Problem &P, int ldt);
+    // Phase I, written once for both (engine.cpp).  phase1_artificial: a_{n+1} = b - sum_{i != minidx} a_{basic_i} into art (P.ld doubles)
+    // and row n of dAt — w.basic must hold s.basic; GOMILP_ERR_PHASE1_WRAPPED for a zero column.  phase1_art_level: the artificial's level
+    // at position `added` (-1: it left the basis) against phaseIZeroTol, GOMILP_ERR_INFEASIBLE beyond it
+    int phase1_artificial(const Problem &P, const Start &s, int64_t minidx, std::vector<double> &art, gomilp_lp_stats *st);
+    int phase1_art_level(const Problem &P, int added, const std::vector<double> &xb);
+    int upload_padded(double *dst, const std::vector<double> &v, int ld);
+    void return_point(const Problem &P, const std::vector<int32_t> &basic, const std::vector<double> &xb, double *opt_f, double *opt_x,
+                      int32_t *has_x, int64_t *basis_out);
+    int fetch_trace(std::vector<DevPivot> &tr);   // the device state into w.st_host, the recorded pivots (at most trace_cap) into tr
+    void open_stats();                            // per-solve counters, at the top of solve_locked / warm_locked;
+    int close_stats(gomilp_lp_stats *st, double t0, int code);   // ... and into the caller's stats on every way out (returns code)
     void bt_layout(const Problem &P, bool tiled);
     BTArgs make_bt_args(const Problem &P, int phase, double tol, int nn, int kmax);
     // the tableau's row length, and with it the plan of the blocked pipeline
@@ -286,33 +345,28 @@ class Engine {
     std::unique_ptr<Work> w_;
     // knobs (Engine::set)
     BtKnobs bt_knobs_;             // which block kernel runs, in which shape
-    int64_t refresh_ = 0, trace_on_ = 0, sample_events_ = 0, fused_ = 1, tableau_ = 1, blocked_ = 1, bt_upd_valu_ = 0, bt_fault_ = 0;
+    SolveKnobs knobs_;             // where a single solve goes
+    int64_t refresh_ = 0, trace_on_ = 0, sample_events_ = 0, bt_upd_valu_ = 0, bt_fault_ = 0;
     int64_t poll_delay_ = 0;       // loop kernel: 64-cycle units between a wave's post and its first poll of an exchange
-    int64_t general_device_ = 1, general_block_ = 1, general_min_rows_ = 96, lu_blocked_ = 3, lu_cross_ = -1;
+    int64_t general_block_ = 1, lu_blocked_ = 3, lu_cross_ = -1;
     int64_t lu_look_ = 1;          // 0 = never the look-ahead schedule (the workers of a pool)
     int64_t lu_large_ = 0;         // 1 = bases of 4097 .. 16384 rows take the compressed rounds on the eight-workgroup panel with several rows per lane (lu_cross.hip); 0 (default, and the workers of a pool) = one launch per column there
-    int64_t exact_degenerate_ = 1; // 0 never, 1 bases of up to 256 rows and every non-slack start, 2 always: pivots whose winning ratio is (nearly) zero are decided on a fresh gonum-order x_B; 3 strict: EVERY pivot and the stop test are decided on fresh gonum-order solves
-    int64_t cond_guard_ = 1;       // replay the condition guards of the reference on the host for bases of up to 64 rows
     int64_t row_chunk_ = 0;        // doubles per LDS chunk of the revised-simplex kernels' staged vectors; 0: one-pass staging up to ld = kLdsWindowLd, chunks of kAutoRowChunk beyond
     int64_t lu_look_faults_ = 0;   // final solves repeated with the plain schedule after a look-ahead launch gave up a wait
     int lu_look_fault_ = 0;        // ... in the running solve, one per fall-back (stats.device_retries)
     bool lds_window_only_ = false;   // refuse problems beyond the one-pass LDS window, as before the chunked form (pool workers)
-    bool badly_scaled_ = false;   // the current problem's entries span more than nine decades (Problem::scale_span): guard on, tableau checked
     bool gen_binv_dev_ = false;   // the searched basis' B^-1 = R^-1 Q^T is resident in the first B^-1 buffer (the device judged the square step): no upload
-    bool gen_start_ = false;      // the current solve starts from a searched (non-slack) basis: the degenerate-pivot guard stays on
-    bool gen_revised_ = false;    // ... and runs on the three-kernel revised loop (beyond the tableau's LDS row, or knob tableau = 0)
-    double lp_guard_ = 0.0;       // LPArgs::guard of that loop (0 for every other solve): the exact steps of Engine::run_loop
     std::vector<double> exact_xb_;   // the fresh x_B of the last exact step (exact_iter)
     bool xchg_timeout_ = false;   // the last pivot loop ended in ST_XCHG_TIMEOUT (Engine::solve repeats the solve once)
     bool shadow_trace_ = false;   // this solve records its pivots for the replay even when the caller did not ask for a trace
     // per-solve state
+    SolvePlan plan_;   // where the running solve goes
     int cur_ = 0;   // which Binv buffer is current
     int ycur_ = 0;  // which y buffer is current
     int grid_ratio_ = 1;
     int tcur_ = 0, rcur_ = 0, ldt_ = 0;   // tableau pipelines: current T / r buffer, row length of T (set_ldt)
     BtPlan bt_plan_;         // blocked tableau: the plan for (the problem being solved, ldt_)
     bool t_tiled_ = false;   // layout of T[tcur_]: 4x4 tiles (blocked pipeline, register-resident kernel) or row-major
-    bool use_bt_ = false;    // blocked tableau (deferred rank-K updates) instead of one launch per pivot
     int64_t launches_ = 0;
     double fs_device_ = 0, fs_host_ = 0;
     int64_t lu_dense_ = 0, lu_rounds_ = 0;
@@ -321,6 +375,10 @@ class Engine {
 };
 
 // engine_general.cpp
+// ascending ids below ncols that are not in the basis (simplex.go:174-184); the acceptance test of a candidate for the exchange of a
+// zero-level artificial at position `added` (simplex.go:581-606): dcol = B^-1 a_j
+void build_nonbasic(const std::vector<int32_t> &basic, int ncols, std::vector<int32_t> &nonbasic);
+bool exchange_keeps_feasible(const double *dcol, const std::vector<double> &xb, int added, int m);
 int general_find_linearly_independent(const std::vector<double> &A, int m, int n, std::vector<int32_t> &idxs, std::vector<double> *binv_out = nullptr);
 int general_finish_last_column(const std::vector<double> &A, int m, int n, std::vector<int32_t> &idxs, int start_col, std::vector<double> *binv_out);
 int general_find_linearly_independent_slow(const std::vector<double> &A, int m, int n, std::vector<int32_t> &idxs);

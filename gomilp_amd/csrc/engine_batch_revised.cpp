@@ -64,8 +64,8 @@ bool RevBatchEngine::eligible(const Engine::RootView &R, int K_min, int K_max, i
     if (R.verify_status != GOMILP_OK || !R.unit_basis) return false;
     const int m_lo = R.m + K_min, m_hi = R.m + K_max, n_hi = R.n + K_max;
     if (m_hi >= n_hi || (R.n - R.m) < 2 * m_hi) return false;   // the revised formulation (engine.cpp: use_tab's n - m < 2m rule)
-    // the exact-step guard is off for every shape (exact_wanted): the blocked tableau with exact steps stays on the workers
-    if (!(exact_degenerate == 0 || (exact_degenerate == 1 && m_lo > 256 && !(R.scale_span > 1e9)))) return false;
+    // the exact-step guard is off for every shape: the blocked tableau with exact steps stays on the workers
+    if (SolvePlan::exact_wanted(exact_degenerate, m_lo, true, R.scale_span)) return false;
     if (cond_guard && m_lo <= 64) return false;                  // the replay of gonum's condition guards runs in Engine::solve only
     // pools keep the row limit of one-pass LDS staging unless the knob large_rows lifts it (the chunked kernels of batch_revised.hip)
     if (!large_rows && ((m_hi + 1) & ~1) > kLdsWindowLd) return false;

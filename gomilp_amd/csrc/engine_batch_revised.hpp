@@ -20,7 +20,7 @@ class RevBatchEngine {
     explicit RevBatchEngine(int device);
     ~RevBatchEngine();
     // do children of this root with K_min..K_max branch rows run on the revised pipelines, unguarded, on a worker with these knobs?
-    // (the predicate of Engine::solve_locked: use_tab / exact_wanted / shadow_trace_)
+    // (what SolvePlan::make decides per solve — use_tab, SolvePlan::exact_wanted, replay_if_feasible — for the whole range of children)
     // large_rows (the pool knob): the row limit of one-pass LDS staging (ld <= kLdsWindowLd) is dropped, every other condition stays
     static bool eligible(const Engine::RootView &R, int K_min, int K_max, int exact_degenerate, int cond_guard, int large_rows = 0);
     // The wave (relaxation i is a child of roots[root_of[i]] — root_of null: of roots[0] — with rows koff[i]..koff[i+1] of var / sign /

@@ -297,9 +297,7 @@ BTArgs Engine::make_bt_args(const Problem &P, int phase, double tol, int nn, int
     // (and for inputs whose entries span more than nine decades: their updated tableau loses digits, the exact steps check and rebuild it)
     // (3, strict: an infinite guard — the block kernel stops in front of EVERY decision, stop test included, and the host repeats the
     // reference's iteration on fresh solves: slow by design, the mode that follows the reference wherever its rounding noise leads)
-    a.guard = exact_degenerate_ == 3 ? std::numeric_limits<double>::infinity()
-                                     : (exact_degenerate_ == 2 || (exact_degenerate_ == 1 && (P.m <= 256 || gen_start_ || badly_scaled_))) ? 1e-9 : 0.0;
-    a.cguard = (cond_guard_ && !gen_start_ && P.m > 64) ? 1e-9 : 0.0;   // (<= 64 rows: the per-pivot replay of Engine::solve; general starts: the guard above is on)
+    a.guard = plan_.guard; a.cguard = plan_.cguard;   // (SolvePlan::make)
     if (a.tiled) {   // (never under knob bt_old: BtPlan::make)
         const BtGroupCfg &gc = bt_plan_.cfg;
         a.groups = gc.groups; a.group_ri = gc.ri; a.group_nt = gc.nt; a.xbuf = w.xbuf;
@@ -399,14 +397,14 @@ int Engine::exact_iter(const Problem &P, int phase, double tol, int nn, double *
     // gonum's guards on the solves of this iteration (mat/lu.go:321: cond > 1e16 -> mat.Condition out of the duals' solve,
     // simplex.go:236-239; lp.ErrLinSolve out of computeMove, :316-318): the tableau of a slack-basis start holds B^-1, so the exact
     // kappa_1 / kappa_inf of the current basis cost three small launches (cond_check) — every exact step measures them
-    if (cond_guard_ && !gen_start_ && m > 64) {   // (Phase I too: the artificial column is a column of the basis like any other; tableau only: the revised route runs general starts)
+    if (plan_.cguard > 0) {   // (Phase I too: the artificial column is a column of the basis like any other; tableau only: the revised route runs general starts)
         double k1 = 0, kinf = 0;
         int rc0 = cond_check(P, nn, &k1, &kinf);
         if (rc0 != GOMILP_OK) return -rc0;
         // (kappa_inf belongs to the x_B solve that closed the PREVIOUS iteration, simplex.go:289-292: the reference would have left
         // its loop there with mat.Condition, before this iteration's computeMove could report lp.ErrLinSolve)
         if (k1 > 1e16 || k1 != k1 || kinf > 1e16 || kinf != kinf) return -GOMILP_ERR_CONDITION;
-    } else if (cond_guard_ && exact_degenerate_ == 3) {
+    } else if (knobs_.cond_guard && knobs_.exact_degenerate == 3) {
         // strict mode on a searched start basis (or a small one): no B^-1 inside the tableau — the same verdict from a fresh host inverse,
         // every pivot (the mode is slow by design: it exists to follow the reference wherever its solves' rounding noise leads)
         double k1 = 0, kinf = 0;
@@ -421,11 +419,7 @@ int Engine::exact_iter(const Problem &P, int phase, double tol, int nn, double *
     int rc;
     if ((rc = final_solve(P, y, &sing, basic.data(), true, cb.data())) != GOMILP_OK) return -rc;
     if (sing) { if (GOMILP_DBG_ENV("GOMILP_DEBUG_LOOP")) fprintf(stderr, "exact_step: ab^T singular (phase %d, m %d)\n", phase, m); return -GOMILP_ERR_LINSOLVE; }
-    {
-        std::vector<double> ypad(P.ld, 0.0);
-        std::copy(y.begin(), y.begin() + m, ypad.begin());
-        if ((rc = stage_upload(y_dev, ypad.data(), (size_t)P.ld * sizeof(double))) != GOMILP_OK) return -rc;
-    }
+    if ((rc = upload_padded(y_dev, y, P.ld)) != GOMILP_OK) return -rc;
     launch_exact_r(P.dAt, P.ld, m, nn, w.nonbasic, y_dev, phase == 1 ? P.dc1 : P.dc, r_dev, ldr, stream_);
     launches_++;
     std::vector<double> r(nn);
@@ -439,11 +433,7 @@ int Engine::exact_iter(const Problem &P, int phase, double tol, int nn, double *
     if (sing) { if (GOMILP_DBG_ENV("GOMILP_DEBUG_LOOP")) fprintf(stderr, "exact_step: ab singular for x_B (phase %d, m %d)\n", phase, m); return -GOMILP_ERR_LINSOLVE; }
     if ((rc = lu_solve(P, xb)) != GOMILP_OK) return -rc;
     exact_xb_ = xb;
-    {
-        std::vector<double> xpad(P.ld, 0.0);
-        std::copy(xb.begin(), xb.begin() + m, xpad.begin());
-        if ((rc = stage_upload(w.xb, xpad.data(), (size_t)P.ld * sizeof(double))) != GOMILP_OK) return -rc;
-    }
+    if ((rc = upload_padded(w.xb, xb, P.ld)) != GOMILP_OK) return -rc;
     if (st) st->cond_fallbacks++;
     const int64_t q = min_idx(r.data(), nn);   // simplex.go:247
     if (r[q] >= -tol) return 1;                // :248
@@ -458,14 +448,17 @@ int Engine::exact_iter(const Problem &P, int phase, double tol, int nn, double *
     if ((rc = lu_solve(P, dsol, col.data())) != GOMILP_OK) return -rc;
     if ((rc = check_column((int)q, nonbasic[q], basic, dsol)) != GOMILP_OK) return -rc;
     std::vector<double> move(m);
-    bool anyneg = false;
-    for (int i = 0; i < m; i++) {
-        double d = -dsol[i];
-        if (fabs(d) < 1e-13) d = 0;            // dRoundTol, :321-325
-        if (d < 0) anyneg = true;
-        move[i] = d >= 0 ? std::numeric_limits<double>::infinity() : xb[i] / fabs(d);   // :334-340
-    }
-    if (!anyneg) return 2;                      // :328-330
+    auto compute_move = [&]() {   // false: no row limits the step
+        bool anyneg = false;
+        for (int i = 0; i < m; i++) {
+            double d = -dsol[i];
+            if (fabs(d) < 1e-13) d = 0;            // dRoundTol, :321-325
+            if (d < 0) anyneg = true;
+            move[i] = d >= 0 ? std::numeric_limits<double>::infinity() : xb[i] / fabs(d);   // :334-340
+        }
+        return anyneg;
+    };
+    if (!compute_move()) return 2;              // :328-330
     const int64_t p = min_idx(move.data(), m);  // :268
     if (!(move[p] <= 0)) {
         *q_out = (int)q; *p_out = (int)p; return 0;
@@ -488,14 +481,7 @@ int Engine::exact_iter(const Problem &P, int phase, double tol, int nn, double *
         const int var = nonbasic[i];
         for (int t = 0; t < m; t++) col[t] = var < n ? P.hA[(size_t)t * n + var] : art[t];
         if ((rc = lu_solve(P, dsol, col.data())) != GOMILP_OK) return -rc;
-        bool neg = false;
-        for (int t = 0; t < m; t++) {
-            double d = -dsol[t];
-            if (fabs(d) < 1e-13) d = 0;
-            if (d < 0) neg = true;
-            move[t] = d >= 0 ? std::numeric_limits<double>::infinity() : xb[t] / fabs(d);
-        }
-        if (!neg) return 2;                     // computeMove inside Bland: ErrUnbounded, :356-360
+        if (!compute_move()) return 2;          // computeMove inside Bland: ErrUnbounded, :356-360
         const int64_t rp0 = min_idx(move.data(), m);
         if (fabs(move[rp0]) > 1e-12) { *q_out = i; *p_out = (int)rp0; return 0; }   // blandZeroTol, :362
         for (int rp = 0; rp < m; rp++) {
@@ -741,30 +727,60 @@ int Engine::run_loop_bt(const Problem &P, int phase, double tol, int nn, gomilp_
     return ret;
 }
 
-// Phase I / Phase II on the tableau pipeline.  Called by Engine::solve after the initial (slack) basis is known.
-// On return `basic` / `xb` hold the final basis positions and updated x_B; *loop_rc is the Phase-II loop result.
-int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &basic, const std::vector<int32_t> &rho,
-                          std::vector<double> &xb, bool feasible, gomilp_lp_stats *st, int *loop_rc,
-                          const std::vector<double> *binv_host) {
+// The work buffers of the tableau pipelines for rows of ldt doubles (the Phase-I tableau: the widest of the solve)
+int Engine::ensure_tableau_work(const Problem &P, int ldt) {
+    Work &w = *w_;
+    const int m = P.m;
+    if (w.cap_T < (size_t)(m + 3) * ldt || w.cap_ldt < ldt) {   // + 3 rows: the tiled layout pads m to a multiple of 4
+        for (double **pp : {&w.T[0], &w.T[1], &w.R[0], &w.R[1], &w.tscratch, &w.btV}) { if (*pp) hipFree(*pp); *pp = nullptr; }
+        if (w.srcpos) hipFree(w.srcpos); w.srcpos = nullptr;
+        const size_t cap = std::max(w.cap_T, (size_t)(m + 3 + 32 + m / 16) * ldt);   // head-room for deeper children
+        const int cl = std::max(w.cap_ldt, ldt);
+        HIP_TRY(dmalloc(&w.T[0], cap)); HIP_TRY(dmalloc(&w.T[1], cap));
+        HIP_TRY(dmalloc(&w.R[0], (size_t)cl)); HIP_TRY(dmalloc(&w.R[1], (size_t)cl));
+        HIP_TRY(dmalloc(&w.tscratch, (size_t)64 * cl)); HIP_TRY(dmalloc(&w.srcpos, (size_t)cl));
+        HIP_TRY(dmalloc(&w.btV, (size_t)bt_max_k() * cl));
+        w.cap_T = cap; w.cap_ldt = cl; w.cap_btU = 0;
+    }
+    // the rank-1 u terms are rows of P.ld doubles: sized by the ROW count, which can grow while the T buffers
+    // (sized by m * ldt) still fit — a wide problem followed by a taller, narrower one on the same context
+    if (w.cap_btU < (size_t)bt_max_k() * (size_t)P.ld) {
+        if (w.btU) hipFree(w.btU); w.btU = nullptr;
+        const size_t cap = (size_t)bt_max_k() * (size_t)std::max(w.cap_ld, P.ld);
+        HIP_TRY(dmalloc(&w.btU, cap));
+        w.cap_btU = cap;
+    }
+    if (plan_.blocked && !w.xbuf) {   // exchange records of the multi-workgroup block kernel: zero = no exchange has happened
+        HIP_TRY(dmalloc(&w.xbuf, bt_xbuf_doubles()));
+        HIP_TRY(hipMemsetAsync(w.xbuf, 0, bt_xbuf_doubles() * sizeof(double), stream_));
+    }
+    if (!plan_.blocked) {   // the blocked kernels never read the padding of r
+        HIP_TRY(hipMemsetAsync(w.R[0], 0, (size_t)w.cap_ldt * sizeof(double), stream_));
+        HIP_TRY(hipMemsetAsync(w.R[1], 0, (size_t)w.cap_ldt * sizeof(double), stream_));
+    }
+    return GOMILP_OK;
+}
+
+int Engine::solve_tableau(const Problem &P, double tol, Start &s, gomilp_lp_stats *st, int *loop_rc) {
     Work &w = *w_;
     const int m = P.m, n = P.n;
+    std::vector<int32_t> &basic = s.basic;
+    const std::vector<int32_t> &rho = s.rho;
+    std::vector<double> &xb = s.xb;
+    const std::vector<double> *binv_host = s.slack ? nullptr : &s.binv_host;
+    const bool use_bt = plan_.blocked;
     int rc;
+    if ((rc = ensure_tableau_work(P, tab_ld(n + 1 - m))) != GOMILP_OK) return rc;
     std::vector<int32_t> nonbasic;
-    auto build_nonbasic = [&](int ncols) {
-        std::vector<char> inb(ncols, 0);
-        for (int i = 0; i < m; i++) inb[basic[i]] = 1;
-        nonbasic.clear();
-        for (int j = 0; j < ncols; j++) if (!inb[j]) nonbasic.push_back(j);
-    };
     tcur_ = 0; rcur_ = 0; t_tiled_ = false;
     if (!binv_host && (rc = stage_upload(w.rho, rho.data(), (size_t)m * sizeof(int32_t))) != GOMILP_OK) return rc;
-    // (x_B itself was uploaded by Engine::solve)
+    // (x_B itself was uploaded by Engine::upload_start)
     std::vector<double> art(P.ld, 0.0);  // Phase-I artificial column (simplex.go:533-542)
     bool binv_on_device = gen_binv_dev_;   // (the device search left B^-1 = R^-1 Q^T in place: engine.cpp find_independent_device)
     auto set_up_T = [&](int nn) -> int {  // T = B^-1 A_N
         set_ldt(P, tab_ld(nn));
         // straight into the layout the block kernels want: no conversion pass before the first pivot
-        t_tiled_ = use_bt_ && bt_plan_.tiled;
+        t_tiled_ = use_bt && bt_plan_.tiled;
         if (!binv_host) {  // slack basis: B^-1 is the permutation rho
             launch_tab_gather(P.dAt, P.ld, m, nn, w.nonbasic, w.rho, w.T[0], ldt_, t_tiled_, stream_);
             launches_++;
@@ -784,46 +800,27 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
     };
     int nn;
     const double t_st0 = now_s();
-    if (!feasible) {
+    if (!s.feasible) {
         // ---- Phase I (simplex.go:529-606) ----
         st->phase1_used = 1;
         const int64_t minidx = min_idx(xb.data(), m);
-        const bool art_on_device = binv_host && m >= general_min_rows_;   // (large general starts: the same subtractions, element by element, by k_gs_art)
-        for (int k = 0; k < m; k++) art[k] = P.hb[k];
-        if (!binv_host) {
-            for (int i = 0; i < m; i++) { if (i == minidx) continue; art[rho[i]] = -1 * 1.0 + art[rho[i]]; }  // floats.Sub, :536-542
-        } else if (!art_on_device) {
-            for (int i = 0; i < m; i++) {  // same loop over full columns
-                if (i == minidx) continue;
-                for (int k = 0; k < m; k++) art[k] = -1 * P.hA[(size_t)k * n + basic[i]] + art[k];
-            }
-        }
         // tableau over the n+1-m columns that are nonbasic w.r.t. the slack basis (the artificial is the last one),
         // then one forced pivot brings the artificial into position minidx (the basis of simplex.go:551)
-        build_nonbasic(n + 1);
+        build_nonbasic(basic, n + 1, nonbasic);
         nn = (int)nonbasic.size();
         if ((rc = upload_index_lists(basic, nonbasic)) != GOMILP_OK) return rc;
-        if (art_on_device) {
-            launch_gs_art(P.dAt, P.ld, m, w.basic, (int)minidx, P.db, P.dAt + (size_t)n * P.ld, stream_);
-            launches_++;
-            HIP_TRY(hipMemcpyAsync(art.data(), P.dAt + (size_t)n * P.ld, (size_t)P.ld * sizeof(double), hipMemcpyDeviceToHost, stream_));
-            HIP_TRY(sync_stream());
-        }
-        bool art_zero = true;
-        for (int k = 0; k < m; k++) if (art[k] != 0) { art_zero = false; break; }
-        if (art_zero) { st->wrapped_status = GOMILP_ERR_ZERO_COLUMN; return GOMILP_ERR_PHASE1_WRAPPED; }
-        if (!art_on_device && (rc = stage_upload(P.dAt + (size_t)n * P.ld, art.data(), (size_t)P.ld * sizeof(double))) != GOMILP_OK) return rc;
+        if ((rc = phase1_artificial(P, s, minidx, art, st)) != GOMILP_OK) return rc;
         const double t_st1 = now_s();
         if ((rc = set_up_T(nn)) != GOMILP_OK) return rc;
         if (binv_host && GOMILP_DBG_ENV("GOMILP_DEBUG_GS")) { (void)sync_stream(); fprintf(stderr, "phase I set-up: artificial column + lists %.2f ms, B^-1 upload + T = B^-1 A_N %.2f ms\n", 1e3 * (t_st1 - t_st0), 1e3 * (now_s() - t_st1)); }
         const int qa = nn - 1;  // position of the artificial
-        if (!use_bt_) {   // the single-kernel pipeline's forced pivot takes the column from dvec; the block kernel reads T itself
+        if (!use_bt) {   // the single-kernel pipeline's forced pivot takes the column from dvec; the block kernel reads T itself
             launch_tab_column(w.T[0], ldt_, m, qa, w.xb, w.dvec, w.move, t_tiled_, stream_);
             launches_++;
         }
         double dp = 0;  // pivot element of the forced pivot: (B^-1 a_art)[minidx]
         if (!binv_host) dp = art[rho[minidx]];
-        else if (!use_bt_) {   // (only the single-kernel pipeline's forced pivot takes it from the host)
+        else if (!use_bt) {   // (only the single-kernel pipeline's forced pivot takes it from the host)
             std::vector<double> brow(m);
             if (gen_binv_dev_) { HIP_TRY(hipMemcpyAsync(brow.data(), w.binv[0] + (size_t)minidx * P.ld, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_)); HIP_TRY(sync_stream()); }
             else for (int i = 0; i < m; i++) brow[i] = (*binv_host)[(size_t)minidx * m + i];
@@ -832,8 +829,8 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
         const int slack = basic[minidx];
         // the register-resident block kernel exchanges the two list entries itself (uncounted), which saves the second
         // upload of the lists when no re-sort follows
-        const bool swap_on_device = use_bt_ && t_tiled_;
-        if (use_bt_) rc = bt_forced_pivot(P, 1, 1e-10, nn, qa, (int)minidx, swap_on_device ? 2 : 1);
+        const bool swap_on_device = use_bt && t_tiled_;
+        if (use_bt) rc = bt_forced_pivot(P, 1, 1e-10, nn, qa, (int)minidx, swap_on_device ? 2 : 1);
         else rc = tab_forced_pivot(P, 1, 1e-10, nn, qa, n, 0.0, (int)minidx, dp, xb[minidx], slack, 4, 0);
         if (rc != GOMILP_OK) return rc;
         basic[minidx] = n;
@@ -862,7 +859,7 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
         // simplex.go:155-158): its x_B is copied out here and inspected after the loop's first host wait — a violation
         // discards whatever the loop did
         HIP_TRY(hipMemcpyAsync(w.h_chk, w.xb, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        rc = use_bt_ ? run_loop_bt(P, 1, 1e-10, nn, st) : run_loop_tab(P, 1, 1e-10, nn, st);
+        rc = use_bt ? run_loop_bt(P, 1, 1e-10, nn, st) : run_loop_tab(P, 1, 1e-10, nn, st);
         if (rc == GOMILP_ERR_DEVICE) return rc;
         for (int i = 0; i < m; i++) if (w.h_chk[i] < -1e-13) return GOMILP_ERR_PANIC;
         if (rc != GOMILP_OK) { st->wrapped_status = rc; return GOMILP_ERR_PHASE1_WRAPPED; }  // :557-559
@@ -873,14 +870,7 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
         int added = -1;
         for (int i = 0; i < m; i++) { basic[i] = w.h_idx[i]; xb[i] = w.h_vec[i]; if (basic[i] == n) added = i; }
         for (int jp = 0; jp < nn; jp++) nonbasic[jp] = w.h_idx[gap + jp];
-        double xart = added >= 0 ? xb[added] : 0.0;
-        if (added >= 0 && fabs(xart) > 1e-13 && fabs(xart) < 1e-11) {
-            std::vector<double> xe;
-            bool sing = false;
-            if ((rc = final_solve(P, xe, &sing)) != GOMILP_OK) return rc;
-            if (!sing) xart = xe[added];
-        }
-        if (fabs(xart) > 1e-12) return GOMILP_ERR_INFEASIBLE;  // phaseIZeroTol, :563-565
+        if ((rc = phase1_art_level(P, added, xb)) != GOMILP_OK) return rc;
         if (added >= 0) {
             // :581-606 exchange the zero-level artificial for the first nonbasic variable (ascending id) that works
             std::vector<std::pair<int32_t, int>> cand;  // (variable id, position)
@@ -900,18 +890,9 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
                 launches_++;
                 HIP_TRY(hipMemcpyAsync(w.h_vec, w.dvec, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream_));
                 HIP_TRY(sync_stream());
-                double dmax = 0;
-                for (int i = 0; i < m; i++) dmax = std::max(dmax, fabs(w.h_vec[i]));
+                if (!exchange_keeps_feasible(w.h_vec, xb, added, m)) continue;
                 const double dpv = w.h_vec[added];
-                if (!(fabs(dpv) > 1e-9 * std::max(1.0, dmax))) continue;
-                const double theta = xb[added] / dpv;
-                bool feas = true;
-                for (int i = 0; i < m && feas; i++) {
-                    const double v = (i == added) ? theta : xb[i] - theta * w.h_vec[i];
-                    if (v < -1e-13) feas = false;
-                }
-                if (!feas) continue;
-                if (use_bt_) rc = bt_forced_pivot(P, 1, 1e-10, nn, jp, added, 1);
+                if (use_bt) rc = bt_forced_pivot(P, 1, 1e-10, nn, jp, added, 1);
                 else rc = tab_forced_pivot(P, 1, 1e-10, nn, jp, cv.first, 0.0, added, dpv, xb[added], n, 4, 0);
                 if (rc != GOMILP_OK) return rc;
                 basic[added] = cv.first;
@@ -925,7 +906,7 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
         }
         // ---- Phase I -> Phase II: nonbasic list rebuilt in ascending order (simplex.go:174-184), T columns follow
         std::vector<int32_t> old_nb = nonbasic;
-        build_nonbasic(n);
+        build_nonbasic(basic, n, nonbasic);
         const int nn2 = (int)nonbasic.size();
         std::vector<int32_t> pos_of(n + 1, -1), srcpos(nn2);
         for (int jp = 0; jp < nn; jp++) pos_of[old_nb[jp]] = jp;
@@ -939,7 +920,7 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
         nn = nn2;
         if ((rc = upload_index_lists(basic, nonbasic)) != GOMILP_OK) return rc;
     } else {
-        build_nonbasic(n);
+        build_nonbasic(basic, n, nonbasic);
         nn = (int)nonbasic.size();
         if ((rc = upload_index_lists(basic, nonbasic)) != GOMILP_OK) return rc;
         if ((rc = set_up_T(nn)) != GOMILP_OK) return rc;
@@ -947,11 +928,11 @@ int Engine::solve_tableau(const Problem &P, double tol, std::vector<int32_t> &ba
     // ---- Phase II ----
     launch_tab_r(w.T[tcur_], ldt_, m, nn, P.dc, w.basic, w.nonbasic, w.tscratch, w.R[rcur_], t_tiled_, stream_);
     launches_ += 2;
-    *loop_rc = use_bt_ ? run_loop_bt(P, 2, tol, nn, st) : run_loop_tab(P, 2, tol, nn, st);
+    *loop_rc = use_bt ? run_loop_bt(P, 2, tol, nn, st) : run_loop_tab(P, 2, tol, nn, st);
     // gonum's condition guard on the basis the loop ends with (mat/lu.go:321 through simplex.go:236-239: the duals' solve of the
     // iteration that finds the optimum reports mat.Condition when cond > 1e16 and the loop leaves with the current point): exact
     // kappa_1 from the tableau for slack-basis starts of any size (bases of up to 64 rows have the pivot-by-pivot replay instead)
-    if (*loop_rc == GOMILP_OK && cond_guard_ && !binv_host && m > 64) {
+    if (*loop_rc == GOMILP_OK && plan_.cguard > 0) {
         double k1 = 0, kinf = 0;
         if ((rc = cond_check(P, nn, &k1, &kinf)) != GOMILP_OK) return rc;
         st->cond1_final = k1; st->condinf_final = kinf;

@@ -42,7 +42,7 @@ void Engine::keep_capture(const Problem &P, int64_t id, int pipeline, const std:
     Kept k;
     k.m = m; k.ld = P.ld; k.basic = basic;
     const bool tab = pipeline >= 2;
-    if (!rho_slack && (tab || gen_revised_)) { k.no_warm = true; kept_[id] = std::move(k); return; }
+    if (!rho_slack && (tab || plan_.gen_revised)) { k.no_warm = true; kept_[id] = std::move(k); return; }
     const size_t need = (size_t)m * P.ld;
     for (size_t i = 0; i < keep_pool_.size(); i++)
         if (keep_pool_[i].second >= need) {
@@ -116,7 +116,7 @@ int Engine::solve_warm(int64_t id, int64_t parent, int keep, int dual_budget, do
     else {
         K = &kept_.at(parent);
         const Problem &P = *problems_[id];
-        if (K->no_warm || exact_degenerate_ == 3 || P.verify_status != GOMILP_OK || P.m >= P.n) fb = 5;
+        if (K->no_warm || knobs_.exact_degenerate == 3 || P.verify_status != GOMILP_OK || P.m >= P.n) fb = 5;
         else if (!K->d) fb = 2;
     }
     ws->new_rows = J;
@@ -151,17 +151,8 @@ int Engine::warm_locked(int64_t id, const Kept &K, int J, int dual_budget, doubl
     *opt_f = std::numeric_limits<double>::quiet_NaN();
     const Problem &P = *problems_[id];
     st->seconds_upload = P.seconds_upload;
-    auto finish = [&](int code) {
-        st->seconds_total = now_s() - t0; st->kernel_launches = launches_;
-        st->seconds_final_device = fs_device_; st->seconds_final_host = fs_host_;
-        st->lu_dense_steps = lu_dense_; st->lu_rounds = lu_rounds_;
-        if (lu_look_fault_) st->device_retries = lu_look_fault_;
-        return code;
-    };
-    launches_ = 0;
-    fs_device_ = fs_host_ = 0; lu_look_fault_ = 0;
-    last_trace_.clear();
-    last_trace_total_ = 0;
+    auto finish = [&](int code) { return close_stats(st, t0, code); };
+    open_stats();
     const int m = P.m, n = P.n, mp = K.m, Kc = (int)P.kvar.size();
     if (mp + J != m || (int)K.basic.size() != mp) return kWarmNoPath;
     if (P.ld > kLdsWindowLd && !large_solve_fits(P)) return kWarmNoPath;
@@ -169,8 +160,8 @@ int Engine::warm_locked(int64_t id, const Kept &K, int J, int dual_budget, doubl
     if (rc != GOMILP_OK) return finish(rc);
     Work &w = *w_;
     w.st_host->trace_len = 0;
-    gen_start_ = false; gen_binv_dev_ = false; shadow_trace_ = false;
-    badly_scaled_ = P.scale_span > 1e9;
+    plan_ = SolvePlan::warm(P.ld, P.scale_span, knobs_);
+    gen_binv_dev_ = false; shadow_trace_ = false;
     // ---- start: the parent's positions, then the slacks of the J new rows (the last J columns of the problem)
     std::vector<int32_t> basic(K.basic), posof(n, -1);
     for (int p = 0; p < mp; p++) posof[K.basic[p]] = p;
@@ -182,11 +173,7 @@ int Engine::warm_locked(int64_t id, const Kept &K, int J, int dual_budget, doubl
         ksg[k] = P.ksign[Kc - J + k];
     }
     std::vector<int32_t> nonbasic;
-    {
-        std::vector<char> inb(n, 0);
-        for (int i = 0; i < m; i++) inb[basic[i]] = 1;
-        for (int j = 0; j < n; j++) if (!inb[j]) nonbasic.push_back(j);
-    }
+    build_nonbasic(basic, n, nonbasic);
     const int nn = (int)nonbasic.size();
     if ((rc = stage_upload(w.rho, kpos.data(), (size_t)J * sizeof(int32_t))) != GOMILP_OK) return finish(rc);
     if ((rc = stage_upload(w.move, ksg.data(), (size_t)J * sizeof(double))) != GOMILP_OK) return finish(rc);
@@ -200,7 +187,7 @@ int Engine::warm_locked(int64_t id, const Kept &K, int J, int dual_budget, doubl
     HIP_TRY(sync_stream());
     ws->seconds_setup = now_s() - t0;
     // ---- dual loop
-    st->pipeline = (fused_ && fused_supported(P.ld)) ? 1 : 0;
+    st->pipeline = plan_.pipeline;
     rc = run_dual_loop(P, kDualFeasTol, nn, dual_budget, ws);
     if (rc == kWarmBudgetSpent) return rc;
     if (rc != GOMILP_OK) return finish(rc);   // GOMILP_ERR_INFEASIBLE (no x), or a device failure
@@ -208,12 +195,7 @@ int Engine::warm_locked(int64_t id, const Kept &K, int J, int dual_budget, doubl
     HIP_TRY(hipMemcpyAsync(w.h_idx, w.basic, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(sync_stream());
     for (int i = 0; i < m; i++) basic[i] = w.h_idx[i];
-    {
-        std::vector<char> inb(n, 0);
-        for (int i = 0; i < m; i++) inb[basic[i]] = 1;
-        nonbasic.clear();
-        for (int j = 0; j < n; j++) if (!inb[j]) nonbasic.push_back(j);
-    }
+    build_nonbasic(basic, n, nonbasic);
     if ((rc = upload_index_lists(basic, nonbasic)) != GOMILP_OK) return finish(rc);
     refresh_xb_y(P, P.dc);
     const int loop_rc = run_loop(P, 2, tol, nn, P.dc, st);

@@ -72,7 +72,7 @@ class FrontierStats(C.Structure):
 
 EXPORTS = [
     "gomilp_lp_solve_warm", "gomilp_frontier_solve_warm", "gomilp_pool_release_warm",
-    "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond", "gomilp_debug_lu_host_solve", "gomilp_debug_bt_plan", "gomilp_debug_wave_plan", "gomilp_debug_rev_footprint",
+    "gomilp_lp_upload_child", "gomilp_pool_create", "gomilp_pool_destroy", "gomilp_pool_set", "gomilp_pool_set_root", "gomilp_frontier_solve", "gomilp_pool_add_root", "gomilp_frontier_solve_roots", "gomilp_pool_solve_root", "gomilp_debug_find_independent", "gomilp_debug_find_independent_device", "gomilp_debug_cond_estimate", "gomilp_debug_gonum_lu_cond", "gomilp_debug_lu_host_solve", "gomilp_debug_bt_plan", "gomilp_debug_solve_plan", "gomilp_debug_wave_plan", "gomilp_debug_rev_footprint",
     "gomilp_lp_simplex", "gomilp_ctx_create", "gomilp_ctx_destroy", "gomilp_ctx_device", "gomilp_ctx_set",
     "gomilp_lp_upload", "gomilp_lp_free", "gomilp_lp_solve_resident", "gomilp_lp_last_trace", "gomilp_version",
     "gomilp_device_count", "gomilp_compiled_arch", "gomilp_comm_unique_id", "gomilp_comm_create", "gomilp_comm_destroy",
@@ -134,6 +134,8 @@ def lib():
     L.gomilp_debug_lu_host_solve.argtypes = [C.c_int64, C.c_int64, i32p, i32p, dp, dp, C.c_int, dp, dp]
     L.gomilp_debug_bt_plan.restype = C.c_int
     L.gomilp_debug_bt_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_char_p), ip, C.c_int64, ip]
+    L.gomilp_debug_solve_plan.restype = C.c_int
+    L.gomilp_debug_solve_plan.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.POINTER(C.c_char_p), ip, dp]
     L.gomilp_debug_wave_plan.restype = C.c_int
     L.gomilp_debug_wave_plan.argtypes = [C.c_int64, ip, ip, i32p, dp, C.c_int64, i32p, ip, i32p, dp, C.c_int32, i32p, C.c_int64, ip, C.c_int64,
                                          C.POINTER(C.c_char_p), ip, i32p, i32p, i32p, i32p]
@@ -606,6 +608,26 @@ def debug_bt_plan(m: int, ldt: int, ncu: int = 256, **knobs) -> dict:
     plan = dict(zip(BT_PLAN_FIELDS, out))
     plan["loop"], plan["rep"] = BT_LOOP_INSTANCES[plan["loop"]], BT_LOOP_INSTANCES[plan["rep"]]
     return plan
+
+
+# the doubles of gomilp_debug_solve_plan, in order; every field but guard / cguard comes back as an int (status: a status code; pipeline:
+# the value of stats["pipeline"])
+SOLVE_PLAN_FIELDS = ["status", "pipeline", "use_tab", "blocked", "gen_start", "gen_revised", "badly_scaled", "guard", "cguard",
+                     "replay_if_feasible", "search_on_device", "art_on_device", "needs_host_A"]
+SOLVE_PLAN_STARTS = ["slack", "searched", "supplied"]
+
+
+def debug_solve_plan(m: int, n: int, start: str = "slack", scale_span: float = 1.0, **knobs) -> dict:
+    """The engine's SolvePlan (gomilp_amd/csrc/engine.hpp) for a single solve of an m x n problem from a starting basis of kind `start`
+    (a name of SOLVE_PLAN_STARTS) under `knobs` — host only (no device).  ValueError for a key that is no routing knob, or a value
+    gomilp_ctx_set would refuse."""
+    keys = (C.c_char_p * max(1, len(knobs)))(*[k.encode() for k in knobs])
+    vals = (C.c_int64 * max(1, len(knobs)))(*[int(v) for v in knobs.values()])
+    out = (C.c_double * len(SOLVE_PLAN_FIELDS))()
+    cnt = lib().gomilp_debug_solve_plan(m, n, SOLVE_PLAN_STARTS.index(start), scale_span, len(knobs), keys, vals, out)
+    if cnt != len(SOLVE_PLAN_FIELDS):
+        raise ValueError("bad shape, key or value: %r" % ((m, n, start, knobs),))
+    return {f: (v if f in ("guard", "cguard") else int(v)) for f, v in zip(SOLVE_PLAN_FIELDS, out)}
 
 
 # gomilp_debug_wave_plan: root flags in, route / cut / group ids out (include/gomilp_lp.h)

@@ -412,6 +412,16 @@ int gomilp_debug_lu_host_solve(int64_t m, int64_t nd, const int32_t *dl, const i
 #define GOMILP_BT_PLAN_FIELDS 23
 int gomilp_debug_bt_plan(int64_t m, int64_t ldt, int64_t nknobs, const char *const *keys, const int64_t *values, int64_t ncu, int64_t *out);
 
+/* Diagnostic (host only, no device): where a single solve of an m x n problem (m < n) goes from a starting basis of kind `start` (0 slack:
+ * the last m columns are unit columns, 1 searched: findLinearlyIndependent, 2 supplied by the caller) with Problem scale span
+ * scale_span (max |a_ij| / min nonzero |a_ij|) under the given knobs (key / value pairs through the range checks of gomilp_ctx_set; only
+ * the routing knobs tableau, blocked, fused, exact_degenerate, cond_guard, general_min_rows, general_device) — the fields of the engine's
+ * SolvePlan (gomilp_amd/csrc/engine.hpp; the table of DESIGN.md section 2.4) as doubles, in the order of SOLVE_PLAN_FIELDS in
+ * gomilp_amd/lp.py.  out has room for GOMILP_SOLVE_PLAN_FIELDS entries; returns their count, or -GOMILP_ERR_BAD_SHAPE for a bad shape,
+ * key or value. */
+#define GOMILP_SOLVE_PLAN_FIELDS 13
+int gomilp_debug_solve_plan(int64_t m, int64_t n, int32_t start, double scale_span, int64_t nknobs, const char *const *keys, const int64_t *values, double *out);
+
 /* Diagnostic (host only, no device): where a pool that holds the given roots would send one frontier wave under the given pool knobs
  * (nknobs key / value pairs of gomilp_pool_set's own keys) — the routing table of DESIGN.md section 2.5f.  A root is its m, n,
  * scale_span and GOMILP_WP_ROOT_* flags (a root with B_NEGATIVE has some b_i < 0); the wave is count / root_of (NULL: all of root 0) /
