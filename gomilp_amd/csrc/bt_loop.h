@@ -40,6 +40,12 @@ __device__ __forceinline__ void xstore(xpair *p, xpair v, bool fast) {
     if (fast) asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
     else asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
 }
+// four consecutive slots from ONE lane (the wave records of btg_kernels.hip xchg_wave): still one 16-byte store per slot, the
+// wait states of the last one inside the string
+__device__ __forceinline__ void xstore4(xpair *p, xpair v0, xpair v1, xpair v2, xpair v3, bool fast) {
+    if (fast) asm volatile("global_store_dwordx4 %0, %1, off\n\tglobal_store_dwordx4 %0, %2, off offset:16\n\tglobal_store_dwordx4 %0, %3, off offset:32\n\tglobal_store_dwordx4 %0, %4, off offset:48\n\ts_nop 1" : : "v"(p), "v"(v0), "v"(v1), "v"(v2), "v"(v3) : "memory");
+    else asm volatile("global_store_dwordx4 %0, %1, off sc1\n\tglobal_store_dwordx4 %0, %2, off offset:16 sc1\n\tglobal_store_dwordx4 %0, %3, off offset:32 sc1\n\tglobal_store_dwordx4 %0, %4, off offset:48 sc1\n\ts_nop 1" : : "v"(p), "v"(v0), "v"(v1), "v"(v2), "v"(v3) : "memory");
+}
 template <int H> struct XLoad;
 template <> struct XLoad<1> {
     static __device__ __forceinline__ void run(const xpair *p, xpair (&v)[1], bool fast) {

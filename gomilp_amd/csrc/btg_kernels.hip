@@ -340,8 +340,8 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
     // The exchange with one record per WAVE (WREC).  A workgroup's 128-byte line holds two half-records, wave w owns slots 4 w .. 4 w + 3;
     // a slot is {64-bit integer tag, double}: tag = low 32 bits of the sequence number << 32 | a 32-bit integer.  Slot 0: first index,
     // minimum; slot 1: the winner's variable id, r_q resp. d_p; slot 2: the XCC id, x_B[p]; slot 3: -, the winner's newest block term.
-    // A wave posts right behind its own argmin: the winner lane's values reach lanes 0..3 by v_readlane, one 16-byte store per lane —
-    // no LDS, no barrier, no fold over the workgroup's waves.  The poll reads the same 16 lines with the same two loads per lane as the
+    // A wave posts right behind its own argmin: the winner's lane, which holds every value of the record, stores the four slots itself, one
+    // 16-byte store per slot — no LDS, no barrier, no fold over the workgroup's waves.  The poll reads the same 16 lines with the same two loads per lane as the
     // workgroup records: lane l takes half-record l & 31, slots 2 (l >> 5) and + 1.  Tags are compared as INTEGERS (a packed tag may be
     // a NaN pattern).  The lexicographic minimum over the 32 wave candidates is the one over 16 workgroup winners of two waves each.
     // Term stores: a wave's s_waitcnt vmcnt(0) in its row phase precedes its own next post, so whoever has seen a wave's post may read
@@ -355,17 +355,17 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
         const unsigned int seq32 = (unsigned int)xs;
         const int par = (int)(xs & 1);
         const int wl = w.i != 0xFFFFFFFFu ? (int)(w.i & 63u) : 0;   // the winner's lane (every candidate NaN: lane 0, the record never wins)
-        const unsigned long long b1 = (unsigned long long)__double_as_longlong(readlane_f64(v1, wl));
-        const unsigned int i1 = (unsigned int)__builtin_amdgcn_readlane(id1, wl);
-        const unsigned long long b2 = (unsigned long long)__double_as_longlong(readlane_f64(v2, wl));
-        const unsigned long long b3 = (unsigned long long)__double_as_longlong(readlane_f64(v3, wl));
-        if (lane < 4) {
-            // (independent selects, not a chain on `lane`: a chain compiles to a switch with a branch per slot)
-            const unsigned int ti = (lane == 0 ? w.i : 0u) | (lane == 1 ? i1 : 0u) | (lane == 2 ? myxcc : 0u);
-            xtag2 v;
-            v.x = ((unsigned long long)seq32 << 32) | ti;
-            v.y = (lane == 0 ? (unsigned long long)__double_as_longlong(w.m) : 0ull) | (lane == 1 ? b1 : 0ull) | (lane == 2 ? b2 : 0ull) | (lane == 3 ? b3 : 0ull);
-            xstore(recs + ((size_t)(par * G + g) * kXSlots + 4 * wv + lane), __builtin_bit_cast(xpair, v), fast);
+        if (lane == wl) {
+            // the winner's lane holds every value of the record in its own registers: it builds the four slots and stores them itself
+            // (one 16-byte store per slot) — no v_readlane to scalar registers and back into lanes 0..3, no select network over the slots
+            const unsigned long long tg = (unsigned long long)seq32 << 32;
+            xtag2 s0, s1, s2, s3;
+            s0.x = tg | w.i;                   s0.y = (unsigned long long)__double_as_longlong(w.m);
+            s1.x = tg | (unsigned int)id1;     s1.y = (unsigned long long)__double_as_longlong(v1);
+            s2.x = tg | myxcc;                 s2.y = (unsigned long long)__double_as_longlong(v2);
+            s3.x = tg;                         s3.y = (unsigned long long)__double_as_longlong(v3);
+            xstore4(recs + ((size_t)(par * G + g) * kXSlots + 4 * wv), __builtin_bit_cast(xpair, s0), __builtin_bit_cast(xpair, s1), __builtin_bit_cast(xpair, s2),
+                    __builtin_bit_cast(xpair, s3), fast);
         }
         stamp(which * 5 + 2);
         for (int dl = 0; dl < a.poll_delay; dl++) __builtin_amdgcn_s_sleep(1);
@@ -627,38 +627,65 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
         double *Uk = a.U + (size_t)(cur0 + k) * a.ldu;
         const bool commit_lists = !(forced && a.forced_nocommit) || (forced && a.forced_nocommit >= 2);
         double vrow[RI];
-#pragma unroll
-        for (int s = 0; s < RI; s++) {
-            const int j = gidx(s);
-            vrow[s] = j < a.ldt ? ldT(tile_off_g((unsigned int)p, (unsigned int)j, ldt)) : 0.0;
-        }
         double up[KR];   // u_j[p] of the block's k earlier pivots, newest first (loop mode: then the lagging ones)
-        if constexpr (LOOP) {
-            const int l = lane & 31;   // (KR <= 32; lanes beyond the terms in use fetch nothing)
+        if constexpr (LOOP && WREC) {
+            // wave records: the row side — u, x_B, the shift of the u terms, the basis list — needs dcol, rinv and theta alone and runs under
+            // the latency of the row load; only its term store waits for the previous pivot's stores
+            static_assert(!WREC || (RI == 1 && KR == 16), "one row and one column per thread (index 0 below), sixteen terms");
+            const int i = gidx(0), j = gidx(0), l = lane & 31;
+            vrow[0] = j < a.ldt ? ldT(tile_off_g((unsigned int)p, (unsigned int)j, ldt)) : 0.0;
             const int trow = l < k ? cur0 + k - 1 - l : lag0 + nl - 1 - (l - k);
             double tv = l < k + nl ? ld_term(a.U + (size_t)trow * a.ldu + p) : 0.0;
+            const double u = (i == p) ? rinv - 1.0 : dcol[0] * nrinv;
+            if (i < a.m) xbv[0] = (i == p) ? theta : __builtin_fma(-theta, dcol[0], xbv[0]);
+            // (no test of i against ldu around the shift: a thread beyond the rows of U has a zero d and shifts zeros nobody reads — dcol is
+            // masked by i < m, and only the store below must stay inside U.  The shift is spelled out: plain assignments are register copies
+            // that the compiler places at the end of the pivot, behind the wait)
+#pragma unroll
+            for (int jj = KR - 1; jj > 0; jj--) asm volatile("v_mov_b64 %0, %1" : "=v"(ureg[0][jj]) : "v"(ureg[0][jj - 1]));
+            ureg[0][0] = u;
+            if (i == p && commit_lists) basv[0] = ent;
+            asm volatile("" : "+v"(ureg[0][0]), "+v"(xbv[0]), "+v"(basv[0]));   // (computed here, not where the compiler would sink them to)
+            __builtin_amdgcn_sched_barrier(0);
             if (l == 0 && k + nl > 0) tv = unew;
-            if constexpr (STAMP) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(12); }   // row + term loads: issue -> data
+            if constexpr (STAMP) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(12); }   // row + term loads: issue -> data, the row side under it
 #pragma unroll
             for (int jj = 0; jj < KR; jj++) up[jj] = readlane_f64(tv, jj);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the previous pivot's term stores have landed (see below)
+            if (i < a.ldu) st_term(Uk + i, u);
         } else {
 #pragma unroll
-            for (int jj = 0; jj < KR; jj++) up[jj] = jj < k ? ld_term(a.U + (size_t)(k - 1 - jj) * a.ldu + p) : 0.0;
-        }
-        // loop mode: the previous pivot's term stores have landed before this pivot's are issued — by this pivot's posts (which carry
-        // only the newest term) every older term is in U / V for the readers; in practice they landed during the exchanges
-        if constexpr (LOOP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            for (int s = 0; s < RI; s++) {
+                const int j = gidx(s);
+                vrow[s] = j < a.ldt ? ldT(tile_off_g((unsigned int)p, (unsigned int)j, ldt)) : 0.0;
+            }
+            if constexpr (LOOP) {
+                const int l = lane & 31;   // (KR <= 32; lanes beyond the terms in use fetch nothing)
+                const int trow = l < k ? cur0 + k - 1 - l : lag0 + nl - 1 - (l - k);
+                double tv = l < k + nl ? ld_term(a.U + (size_t)trow * a.ldu + p) : 0.0;
+                if (l == 0 && k + nl > 0) tv = unew;
+                if constexpr (STAMP) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(12); }   // row + term loads: issue -> data
 #pragma unroll
-        for (int s = 0; s < RI; s++) {
-            const int i = gidx(s);
-            if (i < a.ldu) {
-                const double u = (i == p) ? rinv - 1.0 : dcol[s] * nrinv;
-                if (i < a.m) xbv[s] = (i == p) ? theta : __builtin_fma(-theta, dcol[s], xbv[s]);
-                st_term(Uk + i, u);
+                for (int jj = 0; jj < KR; jj++) up[jj] = readlane_f64(tv, jj);
+            } else {
 #pragma unroll
-                for (int jj = KR - 1; jj > 0; jj--) ureg[s][jj] = ureg[s][jj - 1];
-                ureg[s][0] = u;
-                if (i == p && commit_lists) basv[s] = ent;
+                for (int jj = 0; jj < KR; jj++) up[jj] = jj < k ? ld_term(a.U + (size_t)(k - 1 - jj) * a.ldu + p) : 0.0;
+            }
+            // loop mode: the previous pivot's term stores have landed before this pivot's are issued — by this pivot's posts (which carry
+            // only the newest term) every older term is in U / V for the readers; in practice they landed during the exchanges
+            if constexpr (LOOP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int s = 0; s < RI; s++) {
+                const int i = gidx(s);
+                if (i < a.ldu) {
+                    const double u = (i == p) ? rinv - 1.0 : dcol[s] * nrinv;
+                    if (i < a.m) xbv[s] = (i == p) ? theta : __builtin_fma(-theta, dcol[s], xbv[s]);
+                    st_term(Uk + i, u);
+#pragma unroll
+                    for (int jj = KR - 1; jj > 0; jj--) ureg[s][jj] = ureg[s][jj - 1];
+                    ureg[s][0] = u;
+                    if (i == p && commit_lists) basv[s] = ent;
+                }
             }
         }
 #pragma unroll
@@ -798,6 +825,13 @@ __global__ __launch_bounds__(NT) void k_bt_innerG_batch(const BatchLP *__restric
 // 760 cycles from post to "all seen").
 // (Built since for the 16 x 128 instance with HALF-line records, two per workgroup line, so that the poll keeps its two loads per lane
 // over 16 lines: xchg_wave, 11.53 -> 10.28 ms per loop of the metric LP.)
+// Tried and dropped (wave-record instance, with the post from the winner's lane and the row side under the row load, which stayed): the column
+// and row loads issued inside xchg_wave, right behind the winner's index and in front of the payload, the `fast` test and every exit of the pivot
+// (speculative, index clamped, results of the exits ended by an empty asm use).  The object code had the loads 15-17 instructions behind the index
+// instead of 61 / ~50, same pivots and bits, but the loop of the metric LP did not gain: alone 10.141 against 10.225 ms (parent's spread 0.03), and
+// together with the other two 10.163 against 9.832 ms without it.  The stamped build shows why: pick + loads 1682 -> 1298 cycles on the column side,
+// but the pick in front of the issue grew by 216 / 388 cycles (reloads of spilled scalar registers and wait states now sit in front of the load
+// instead of behind it) and the following poll by 170 — the waves reach the next exchange no earlier (profiles/loop_early_loads_timing.log).
 // Tried and dropped (round 5, loop mode): 16 pivot workgroups of ONE wave, two rows / columns per thread (k_bt_loop<16,64,2,8>: no workgroup
 // stage and no real barrier in front of a post).  Same pivots, 4.45-4.68 instead of 3.87 us per pivot at 2048 rows (grid 256 / 136): the
 // wave's doubled row / column work costs more than the stage saved.

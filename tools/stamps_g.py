@@ -10,7 +10,7 @@ print("segments: 0 local-min A | 1 barrier | 2 block-min + post | 3 poll | 4 pic
 m, seed = synth.CONFIGS[name]
 c, A, b = synth.dense_lp_standard_form(m, seed)
 knobs = dict((k, int(v)) for k, v in (a.split("=") for a in sys.argv[3:]))
-print("loop kernel (default at M): 0 local-min A | 1 wait+barrier | 2 combine+post | 3 poll | 4 pick | 11 column loads | 5 corrections+ratios+local-min B | 6 wait+barrier | 7 combine+post | 8 poll | 9 pick | 12 row loads | 10 rest of the row phase")
+print("loop kernel (default at M): 0 local-min A | 1 wait+barrier | 2 combine+post | 3 poll | 4 pick | 11 column loads | 5 corrections+ratios+local-min B | 6 wait+barrier | 7 combine+post | 8 poll | 9 pick | 12 row loads (wave records: with the row side of the row phase under them) | 10 rest of the row phase")
 knobs.setdefault("bt_stamps", 1)
 cx = lp.Context(bt_groups=G, **knobs)
 r = cx.upload(c, A, b).solve(0.0)
