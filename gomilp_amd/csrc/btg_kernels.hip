@@ -347,7 +347,8 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
     // Term stores: a wave's s_waitcnt vmcnt(0) in its row phase precedes its own next post, so whoever has seen a wave's post may read
     // that wave's older terms from U / V.  (The buffer is shared with the workgroup-record kernels of the same context, whose slots
     // hold {(double)sequence number, value}: a stale one of those reads as this exchange's tag only 2^30 exchanges later.)
-    auto xchg_wave = [&](int which, const BtWinG w, double v1, int id1, double v2, double v3) -> XWin {
+    // under_poll: work of the caller that nobody waits for, placed between the post and the poll (reduce_cols).
+    auto xchg_wave = [&](int which, const BtWinG w, double v1, int id1, double v2, double v3, auto under_poll) -> XWin {
         typedef unsigned long long xtag2 __attribute__((ext_vector_type(2)));
         stamp(which * 5 + 0);
         stamp(which * 5 + 1);   // (no wait, no barrier: the segment stays for the comparison with the workgroup form)
@@ -368,6 +369,7 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
                     __builtin_bit_cast(xpair, s3), fast);
         }
         stamp(which * 5 + 2);
+        under_poll();   // (the record is on its way)
         for (int dl = 0; dl < a.poll_delay; dl++) __builtin_amdgcn_s_sleep(1);
         const int h = lane & 31;   // half-record h: wave h & 1 of workgroup h >> 1
         const xpair *src = recs + (size_t)par * G * kXSlots + (h >> 1) * kXSlots + (h & 1) * 4 + 2 * (lane >> 5);
@@ -418,10 +420,29 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
         stamp(which * 5 + 4);
         return r;
     };
-    // entering column: (min, q); payload r_q, the entering variable
-    auto reduce_cols = [&](const double (&val)[RI]) -> XWin {
+    // Wave records: the row phase leaves the newest v' term of this thread's column in `vnew` and the fifteen older ones where they are; the
+    // shift vreg[j] = vreg[j - 1], vreg[0] = vnew runs behind the post of the next pivot's first exchange 0, under its poll, instead of between
+    // the update of r and the argmin over it.  Unconditional: in front of the first pivot of a launch it shifts zeros.  Between the row phase
+    // and that point nothing reads vreg (the payload of the post is vnew itself; every exit taken there ends the launch, and after an exit
+    // nothing reads the terms); the start of a block clears one entry earlier, because the shift is still to come (see there).  The copies are
+    // asm moves with tied destinations, closed by a sched_barrier, and stand ONCE in the object code (see the pivot loop): as plain
+    // assignments, or called from two places, the compiler keeps the terms in two register sets and copies one into the other at the loop's
+    // back edge, on the chain again.
+    double vnew = 0;
+    auto shift_v = [&]() {
+#pragma unroll
+        for (int jj = KR - 1; jj > 0; jj--) asm volatile("v_mov_b64 %0, %1" : "+v"(vreg[0][jj]) : "v"(vreg[0][jj - 1]));
+        asm volatile("v_mov_b64 %0, %1" : "+v"(vreg[0][0]) : "v"(vnew));
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // entering column: (min, q); payload r_q, the entering variable.  first_of_pivot (std::true_type / std::false_type): the first exchange 0
+    // of a pivot (the later ones of a Bland step are not); the wave-record form hangs the shift of the v' terms behind that post
+    auto reduce_cols = [&](const double (&val)[RI], auto first_of_pivot) -> XWin {
         const BtWinG w = wave_first_min(val);
-        if constexpr (WREC) return xchg_wave(0, w, rv[0], nbasv[0], 0.0, vreg[0][0]);
+        if constexpr (WREC) {
+            if constexpr (decltype(first_of_pivot)::value) return xchg_wave(0, w, rv[0], nbasv[0], 0.0, vnew, shift_v);
+            else return xchg_wave(0, w, rv[0], nbasv[0], 0.0, vnew, [] {});
+        }
 #pragma unroll
         for (int s = 0; s < RI; s++)
             if ((unsigned int)gidx(s) == w.i) {
@@ -435,7 +456,7 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
     // leaving row: (min, p); payload d_p, x_B[p], the leaving variable
     auto reduce_rows = [&](const double (&val)[RI], const double (&dcol)[RI]) -> XWin {
         const BtWinG w = wave_first_min(val);
-        if constexpr (WREC) return xchg_wave(1, w, dcol[0], basv[0], xbv[0], ureg[0][0]);
+        if constexpr (WREC) return xchg_wave(1, w, dcol[0], basv[0], xbv[0], ureg[0][0], [] {});
 #pragma unroll
         for (int s = 0; s < RI; s++)
             if ((unsigned int)gidx(s) == w.i) {
@@ -520,6 +541,7 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
             for (int s = 0; s < RI; s++) {
 #pragma unroll
                 for (int j = KB; j < KR; j++) { ureg[s][j] = 0; vreg[s][j] = 0; }
+                if constexpr (WREC) vreg[s][KB - 1] = 0;   // (the shift of the last pivot's v' terms is still to come, shift_v: this entry is entry KB then)
             }
         }
         kd = 0;
@@ -531,8 +553,15 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
         double rq = 0, dpv = 1.0, xbp = 0, unew = 0;   // (unew: the newest u term of row p, out of the winner's record)
         bool bland = false;
         double dcol[RI];
+        XWin f0;   // the first exchange 0 of the pivot
+        if constexpr (WREC) {   // forced or not, ONE call: the shift behind its post stands once in the object code (shift_v)
+            double c0[RI];
+            c0[0] = forced ? (gidx(0) == a.forced_q ? 0.0 : inf) : rv[0];
+            f0 = reduce_cols(c0, std::true_type{});
+        }
         if (!forced) {
-            const XWin fq = reduce_cols(rv);
+            if constexpr (!WREC) f0 = reduce_cols(rv, std::true_type{});
+            const XWin fq = f0;
             if (dead) break;
             q = (int)fq.i; rq = fq.p0; ent = (int)fq.p1;
             if (fq.i >= (unsigned int)a.nn) { q = 0; rq = __builtin_nan(""); }   // every r_j is NaN: MinIdx returns 0
@@ -566,7 +595,7 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
                         if (fabs(rr) < 1e-13) rr = 0;
                         fl[s] = (j < a.nn && j > cand && !(rr > -1e-14)) ? 0.0 : inf;
                     }
-                    const XWin fc = reduce_cols(fl);
+                    const XWin fc = reduce_cols(fl, std::false_type{});
                     if (dead) break;
                     if (fc.m != 0.0) break;   // candidates exhausted -> ErrBland
                     cand = (int)fc.i;
@@ -607,7 +636,8 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
             double fl[RI];
 #pragma unroll
             for (int s = 0; s < RI; s++) fl[s] = (gidx(s) == q) ? 0.0 : inf;
-            const XWin fc = reduce_cols(fl);
+            if constexpr (!WREC) f0 = reduce_cols(fl, std::true_type{});
+            const XWin fc = f0;
             if (dead) break;
             ent = (int)fc.p1;
             if (!a.forced_nocommit) rq = fc.p0;   // a pivot the host decided on fresh solves (exact_step): a pivot like any other
@@ -706,9 +736,12 @@ __device__ __forceinline__ void bt_innerG_body(const BTArgs &a, const int g, con
                 rv[s] = (j == q) ? -mult : __builtin_fma(-mult, v, rv[s]);
                 const double vprime = (j == q) ? dpv + 1.0 : v;
                 st_term(Vk + j, vprime);
+                if constexpr (WREC) vnew = vprime;   // (the shift follows the next pivot's first post: shift_v)
+                else {
 #pragma unroll
-                for (int jj = KR - 1; jj > 0; jj--) vreg[s][jj] = vreg[s][jj - 1];
-                vreg[s][0] = vprime;
+                    for (int jj = KR - 1; jj > 0; jj--) vreg[s][jj] = vreg[s][jj - 1];
+                    vreg[s][0] = vprime;
+                }
                 if (j == q && commit_lists) nbasv[s] = lea;
             }
         }
@@ -832,6 +865,11 @@ __global__ __launch_bounds__(NT) void k_bt_innerG_batch(const BatchLP *__restric
 // together with the other two 10.163 against 9.832 ms without it.  The stamped build shows why: pick + loads 1682 -> 1298 cycles on the column side,
 // but the pick in front of the issue grew by 216 / 388 cycles (reloads of spilled scalar registers and wait states now sit in front of the load
 // instead of behind it) and the following poll by 170 — the waves reach the next exchange no earlier (profiles/loop_early_loads_timing.log).
+// Tried and dropped (wave-record instance): the two correction sums of a pivot by row broadcast — term l fetched by lane l & 15, sixteen
+// v_fmac_f64_dpp acc, tv, v row_newbcast:j per sum instead of 32 v_readlane_b32 and 16 multiply-adds with scalar operands.  Same pivots and bits,
+// 4117 -> 3930 instructions, 18 spilled scalars fewer, and the loop of the metric LP 10.484 against 10.016 ms: in the stamped build sixteen DPP
+// multiply-adds cost 190 cycles more than sixteen plain ones (the 64-bit DPP form issues at about a quarter of the rate), more than the readlanes
+// they save (profiles/loop_term_broadcast_timing.log).
 // Tried and dropped (round 5, loop mode): 16 pivot workgroups of ONE wave, two rows / columns per thread (k_bt_loop<16,64,2,8>: no workgroup
 // stage and no real barrier in front of a post).  Same pivots, 4.45-4.68 instead of 3.87 us per pivot at 2048 rows (grid 256 / 136): the
 // wave's doubled row / column work costs more than the stage saved.
