@@ -16,7 +16,8 @@ enum : int32_t {
     RS_RUN = 0,    // set-up launches or a pivot loop are running
     RS_DONE = 1,   // terminal: `status` holds the outcome (GOMILP_OK / ERR_BLAND / ERR_UNSUPPORTED after Phase II: basis + x_B ready for the final solve)
     RS_HOST = 2,   // terminal: a branch the schedule leaves to a worker's whole solve: the |x_art| band (1e-13 < |x_art| < 1e-11: the verdict
-                   // needs a fresh gonum-order solve), and the zero-level artificial exchange where the wave runs without it (rev_exchange = 0)
+                   // needs a fresh gonum-order solve), the zero-level artificial exchange where the wave runs without it (rev_exchange = 0),
+                   // and of a searched start (RevLP::gen) the start guard of k_rv_gen_start and every exact step (ST_NEED_EXACT)
     RS_COLD = 3    // a warm start that spent its dual-pivot budget: the host re-initialises the slot and the same run solves it cold
 };
 // RevLP::after: what k_rv_check does behind the set-up launches of a superstep
@@ -93,6 +94,16 @@ struct RevLP {
     // is the relaxation's own row `art` (ld doubles of the zeroed work arena, written by k_rv_init<true>)
     int32_t inplace, pad4;
     double *art;
+    // ---- a root without a slack basis (pool knob rev_general; written by the host, at the tail, for the same reason): gen != 0: the
+    // relaxation's root carries its searched basis (RootView::GeneralRev) — B0^-1 (m0 x ldg, padding column zero), x_B0, the basis list
+    // and the position of every root variable (-1: nonbasic).  k_rv_gen_start builds the start (k_rv_init leaves the relaxation alone),
+    // k_rv_gen_art the Phase-I artificial column of the start with gminidx >= 0 (the position the artificial is forced into), and the
+    // pivots of its loops are the G = true instances of K1-K3 with this guard; pk_price / pk_ratio then hold 2 * kMaxPartials keys
+    const double *gB0inv, *gxb0;
+    const int32_t *gbasic0, *gposvar0;
+    int32_t ldg, gen;
+    int32_t gminidx, pad5;
+    double guard;
 };
 
 // what the host reads of every active relaxation after a superstep
@@ -125,6 +136,13 @@ void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t
 // a dual pivot of the relaxations in the dual loop: leaving row, dual pricing, K2 / K3 in their kDualPick form (4 launches;
 // lds2: bytes of the TWO staged vectors of the one-pass pricing kernel, ld_max <= kRevDualLd; ck2d > 0: the chunked pricing kernel
 // instead, each of its two vectors ck2d <= kRevDualLd / 2 double2 at a time — 64 KB of LDS at most)
+// searched starts (RevLP::gen; one-pass staging only): launch_rv_gen_start behind launch_rv_init — B^-1, x_B, the lists, b, c1, the start
+// guard and the orders of every relaxation with gen != 0 (one launch for the wave, grid rows x count); launch_rv_gen_art behind it — the
+// Phase-I artificial column of those that start infeasible (one workgroup per relaxation; reads the assembled At, or the root in place);
+// launch_rv_pivot_g: K1-K3 of a loop pivot in their G = true instances over a list of such relaxations (3 launches: no Bland step)
+void launch_rv_gen_start(RevLP *lps, int count, int m_max, hipStream_t s);
+void launch_rv_gen_art(RevLP *lps, int count, int inplace, hipStream_t s);
+void launch_rv_pivot_g(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int inplace, hipStream_t s);
 constexpr int kRevDualLd = 4096;
 void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s);
 void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, int ck2, int ck2d, int inplace, hipStream_t s);

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(kBlock) void k_rv_init(RevLP *lps) {
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
     RevLP *d = lps + blockIdx.x;
-    if (d->warm) return;   // k_rv_warm_binv starts it
+    if (d->warm || d->gen) return;   // k_rv_warm_binv / k_rv_gen_start starts it
     const int m = d->m, n = d->n, ld = d->ld, m0 = d->m0, K = d->K;
     const int32_t *rho0 = d->rho0;
     double *b = d->b, *xb = d->xb, *binv0 = d->binv[0], *c1 = d->c1;
@@ -190,6 +190,121 @@ __global__ __launch_bounds__(kBlock) void k_rv_warm_binv(RevLP *lps) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// start of a relaxation whose root has no slack basis, from the root's searched basis (RevLP::gen; k_b_setup's general branch on B^-1
+// instead of the tableau): the child's basis is its K branch slacks — position pos < K: the slack of branch row kk = K - 1 - pos, the
+// descending scan of findLinearlyIndependent meets them first — then the root's basis, and by block elimination, copies and sign flips only,
+//   B^-1 row pos < K:   [-sign_kk * B0^-1[p0(var_kk), :] | e_{m0 + kk}]  (zeros where var_kk is nonbasic at the root),   row K + i: [B0^-1 row i | 0],
+//   x_B = [rhs_kk - sign_kk * x0[var_kk] ; x_B0].
+// A worker computes this x_B by a fresh gonum-order solve of the child's basis, whose last bits may differ: where the start's decisions
+// (feasible at -1e-13; the position of the minimum) could turn on them — an entry within 1e-9 of the threshold, the minimum and its
+// runner-up within 1e-9 max(1, |min|) — the relaxation goes to a worker's whole solve (RS_HOST).  Else the orders of the Phase-II start, or
+// of the Phase-I set-up with gminidx for k_rv_gen_art.  grid: (rows of the tallest relaxation, relaxations); workgroup 0 of a relaxation
+// does everything but the rows of B^-1.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_rv_gen_start(RevLP *lps) {
+    __shared__ unsigned long long sk[kWavesPerBlock];
+    __shared__ unsigned int si[kWavesPerBlock];
+    __shared__ unsigned long long ss[kWavesPerBlock];
+    RevLP *d = lps + blockIdx.y;
+    if (!d->gen) return;
+    const int i = blockIdx.x, m = d->m, n = d->n, ld = d->ld, m0 = d->m0, n0 = d->n0, K = d->K, ldg = d->ldg;
+    if (i >= m) return;
+    const double *B0 = d->gB0inv;
+    const int32_t *posvar = d->gposvar0;
+    double *dst = d->binv[0] + (size_t)i * ld;
+    if (i >= K) {
+        const double *src = B0 + (size_t)(i - K) * ldg;
+        for (int c = threadIdx.x; c < ld; c += kBlock) dst[c] = c < m0 ? src[c] : 0.0;
+    } else {
+        const int kk = K - 1 - i, pos = posvar[d->avar[kk]];
+        const double s = -d->asign[kk];
+        const double *src = pos >= 0 ? B0 + (size_t)pos * ldg : nullptr;
+        for (int c = threadIdx.x; c < ld; c += kBlock) dst[c] = c < m0 ? (src ? s * src[c] : 0.0) : (c == m0 + kk ? 1.0 : 0.0);
+    }
+    if (i != 0) return;
+    double *b = d->b, *xb = d->xb, *c1 = d->c1;
+    int32_t *basic = d->basic;
+    const double *xb0 = d->gxb0;
+    const int32_t *basic0 = d->gbasic0;
+    for (int r = threadIdx.x; r < ld; r += kBlock) b[r] = r < m0 ? d->b0[r] : (r < m ? d->rhs[r - m0] : 0.0);
+    for (int j = threadIdx.x; j <= n; j += kBlock) c1[j] = j == n ? 1.0 : 0.0;
+    int infeasible = 0, close = 0;
+    unsigned long long bk = ~0ull, b2 = ~0ull;
+    unsigned int bi = 0xFFFFFFFFu;
+    for (int pos = threadIdx.x; pos < m; pos += kBlock) {
+        double v;
+        if (pos < K) {
+            const int kk = K - 1 - pos, pv = posvar[d->avar[kk]];
+            v = d->rhs[kk] - d->asign[kk] * (pv >= 0 ? xb0[pv] : 0.0);
+            basic[pos] = n0 + kk;
+        } else {
+            v = xb0[pos - K];
+            basic[pos] = basic0[pos - K];
+        }
+        xb[pos] = v;
+        if (v < -1e-13) infeasible = 1;
+        if (fabs(v + 1e-13) <= 1e-9) close = 1;
+        amin2_take(bk, bi, b2, ordkey(v), (unsigned int)pos, ~0ull);
+    }
+    infeasible = __syncthreads_or(infeasible);
+    close = __syncthreads_or(close);
+    block_argmin2(bk, bi, b2, sk, si, ss);
+    if (threadIdx.x != 0) return;
+    const double vmin = orddecode(bk), v2 = orddecode(b2);
+    if (close || (b2 != ~0ull && v2 - vmin <= 1e-9 * fmax(1.0, fabs(vmin)))) {
+        d->stage = RS_HOST; d->run = RR_NONE;
+        return;
+    }
+    if (!infeasible) {
+        d->run = RR_NONE; d->do_lists = 2; d->do_refresh = 2; d->after = RA_P2_LOOP;
+    } else {
+        d->phase1_used = 1; d->gminidx = (int)bi;   // floats.MinIdx(xb), simplex.go:531
+        d->f_var = n; d->f_pos = -1; d->f_p = (int)bi; d->f_noswap = 1;
+        d->run = RR_FORCED; d->do_lists = 1; d->do_refresh = 1; d->after = RA_P1_LOOP;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Phase-I artificial column of a searched start (k_gs_art of general_kernels.hip per relaxation; simplex.go:536-542): a_{n+1} = b minus
+// every basic column but the one at position gminidx, by ascending position, element by element as `-1 * a + art` (floats.Sub per column),
+// into row n of At (IP: the relaxation's row `art`).  One thread per row — consecutive threads read consecutive elements of a column —
+// and one workgroup per relaxation, which therefore sees whether the column is empty (verifyInputs of the recursive call).
+// ------------------------------------------------------------------------------------------------
+template <bool IP>
+__global__ __launch_bounds__(kBlock) void k_rv_gen_art(RevLP *lps) {
+    RevLP *d = lps + blockIdx.x;
+    if (!d->gen || d->stage != RS_RUN || d->run != RR_FORCED || d->gminidx < 0) return;
+    const int m = d->m, n = d->n, ld = d->ld, minidx = d->gminidx;
+    const double *At = d->At, *b = d->b;
+    const int32_t *basic = d->basic;
+    double *art = IP ? d->art : d->At + (size_t)n * ld;
+    int nonzero = 0;
+    for (int r = threadIdx.x; r < ld; r += kBlock) {
+        double acc = 0.0;
+        if (r < m) {
+            acc = b[r];
+            for (int pos = 0; pos < m; pos++) {
+                if (pos == minidx) continue;
+                const int j = basic[pos];
+                double a;
+                if constexpr (IP) a = ChildCol(d, j).elem(r);
+                else a = At[(size_t)j * ld + r];
+                acc = __dadd_rn(__dmul_rn(-1.0, a), acc);
+            }
+        }
+        art[r] = acc;
+        if (acc != 0) nonzero = 1;
+    }
+    nonzero = __syncthreads_or(nonzero);
+    if (threadIdx.x == 0) {
+        d->gminidx = -1;
+        if (!nonzero) {
+            d->status = GOMILP_ERR_PHASE1_WRAPPED; d->wrapped = GOMILP_ERR_ZERO_COLUMN; d->stage = RS_DONE; d->run = RR_NONE; clear_orders(d);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K1-K3, relaxation = blockIdx.y.  MODE = RR_LOOP: a pivot of the loop; RR_FORCED: the forced pivot of the Phase-I set-up;
 // RR_DUAL (K2 / K3 only): a dual pivot of a warm start — the entering position from the partials of k_rv_dual_price, the leaving
 // row from the state (kDualPick).
@@ -236,12 +351,14 @@ __device__ __forceinline__ auto child_col(const RevLP *d, const double *At, int 
     else return PlainCol(At + (size_t)j * ld);
 }
 
-template <bool IP, bool CK>
+// G (K1-K3): the exact-step guard of simplex_helpers.h for the relaxations of a searched start (RevLP::gen, RevLP::guard): the runner-up keys
+// beside the winners, ST_NEED_EXACT where a worker's loop takes an exact step (k_rv_ctrl: RS_HOST).  G = false is the kernel as it was.
+template <bool IP, bool CK, bool G = false>
 __global__ __launch_bounds__(kBlock) void k_rv_price(RevLP *__restrict__ lps, const int *__restrict__ act, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
-    __shared__ unsigned long long ss[1];
+    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
     const RevLP *d = lps + act[blockIdx.y];
     if (d->run != RR_LOOP || d->bl) return;
     DevState *st = d->st;
@@ -258,16 +375,16 @@ __global__ __launch_bounds__(kBlock) void k_rv_price(RevLP *__restrict__ lps, co
     unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
     sweep_rows<CK, 1>([&](int pos) { return child_col<IP>(d, At, ld, nonbasic[pos]); }, {PlainCol(y)}, nn, wave, nwaves, ld, svec, ck2, lane,
-                      [&](int pos, const double (&dot)[1]) { price_elem<false>(cost, rvec, pos, nonbasic[pos], dot[0], lane, bk, bi, b2); });
-    publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
+                      [&](int pos, const double (&dot)[1]) { price_elem<G>(cost, rvec, pos, nonbasic[pos], dot[0], lane, bk, bi, b2); });
+    publish<G>(bk, bi, b2, sk, si, ss, pk, pi);
 }
 
-template <int MODE, bool IP, bool CK>
+template <int MODE, bool IP, bool CK, bool G = false>
 __global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_price, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
-    __shared__ unsigned long long ss[1];
+    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
     RevLP *d = lps + act[blockIdx.y];
     if (d->run != MODE) return;
     DevState *st = d->st;
@@ -284,7 +401,9 @@ __global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, co
     unsigned long long *pk = d->pk_ratio;
     unsigned int *pi = d->pi_ratio;
     int var;
-    if (!pick_entering<false>(st, pkp, pip, nparts_price, rvec, nonbasic, tol, 0.0, forced_pos, forced_var, sk, si, ss, var)) return;
+    double guard = 0.0;
+    if constexpr (G) guard = d->guard;
+    if (!pick_entering<G>(st, pkp, pip, nparts_price, rvec, nonbasic, tol, guard, forced_pos, forced_var, sk, si, ss, var)) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) d->flips_k2 = flips;   // K3 of this pivot reads the parity K2 worked on
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
@@ -292,8 +411,8 @@ __global__ __launch_bounds__(kBlock) void k_rv_ftran(RevLP *__restrict__ lps, co
     unsigned long long bk = ~0ull, b2 = ~0ull;
     unsigned int bi = 0xFFFFFFFFu;
     sweep_rows<CK, 1>([&](int i) { return PlainCol(binv_cur + (size_t)i * ld); }, {child_col<IP>(d, At, ld, var)}, m, wave, nwaves, ld, svec, ck2, lane,
-                      [&](int i, const double (&dot)[1]) { ratio_elem<false>(xb, dvec, move, i, dot[0], lane, bk, bi, b2); });
-    publish<false>(bk, bi, b2, sk, si, ss, pk, pi);
+                      [&](int i, const double (&dot)[1]) { ratio_elem<G>(xb, dvec, move, i, dot[0], lane, bk, bi, b2); });
+    publish<G>(bk, bi, b2, sk, si, ss, pk, pi);
 }
 
 // replaceBland's leaving row for the candidate whose FTRAN just ran (Engine::host_bland; simplex.go:357-380): the first-index
@@ -317,12 +436,12 @@ __device__ __forceinline__ bool bland_leaving(DevState *st, const unsigned long 
     return true;
 }
 
-template <int MODE, bool CK>
+template <int MODE, bool CK, bool G = false>
 __global__ __launch_bounds__(kBlock) void k_rv_update(RevLP *__restrict__ lps, const int *__restrict__ act, int nparts_ratio, int ck2) {
     extern __shared__ __attribute__((aligned(16))) double2 svec[];
     __shared__ unsigned long long sk[kWavesPerBlock];
     __shared__ unsigned int si[kWavesPerBlock];
-    __shared__ unsigned long long ss[1];
+    __shared__ unsigned long long ss[G ? kWavesPerBlock : 1];
     RevLP *d = lps + act[blockIdx.y];
     if (d->run != MODE) return;
     DevState *st = d->st;
@@ -339,8 +458,10 @@ __global__ __launch_bounds__(kBlock) void k_rv_update(RevLP *__restrict__ lps, c
     int p;
     if (bland) {
         if (!bland_leaving(st, pk, pi, nparts_ratio, move, m, sk, si, p)) return;
-    } else if (!pick_leaving<false>(st, pk, pi, nparts_ratio, move, dvec, 0.0, forced_p, sk, si, ss, p)) {
-        return;
+    } else {
+        double guard = 0.0;
+        if constexpr (G) guard = d->guard;
+        if (!pick_leaving<G>(st, pk, pi, nparts_ratio, move, dvec, guard, forced_p, sk, si, ss, p)) return;
     }
     const double dpv = dvec[p];
     const double *rowp_g = binv_cur + (size_t)p * ld;   // old row p
@@ -556,6 +677,10 @@ __global__ __launch_bounds__(kBlock) void k_rv_ctrl(RevLP *__restrict__ lps, con
                 else { d->piv2 = st->pivots; d->status = GOMILP_ERR_BLAND; }
                 d->stage = RS_DONE; d->run = RR_NONE;
             }
+        } else if (status == ST_NEED_EXACT) {
+            // a guarded loop (RevLP::gen) stopped where a worker's loop takes an exact step — a decision on a fresh gonum-order solve: a
+            // worker solves the relaxation, whole
+            if (threadIdx.x == 0) { d->stage = RS_HOST; d->run = RR_NONE; }
         } else {
             const int rc = status == ST_OPTIMAL ? GOMILP_OK : status == ST_UNBOUNDED ? GOMILP_ERR_UNBOUNDED
                          : status == ST_MAX_PIVOTS ? GOMILP_ERR_UNSUPPORTED : GOMILP_ERR_DEVICE;
@@ -738,6 +863,18 @@ void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t
     const auto kx = ck2 > 0 ? (inplace ? k_rv_exch<true, true> : k_rv_exch<false, true>) : (inplace ? k_rv_exch<true, false> : k_rv_exch<false, false>);
     hipLaunchKernelGGL(kx, dim3(nn_max, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, ck2);
     hipLaunchKernelGGL(k_rv_exch_pick, dim3(nact), dim3(64), 0, s, lps, act);
+}
+void launch_rv_gen_start(RevLP *lps, int count, int m_max, hipStream_t s) {
+    hipLaunchKernelGGL(k_rv_gen_start, dim3(m_max, count), dim3(kBlock), 0, s, lps);
+}
+void launch_rv_gen_art(RevLP *lps, int count, int inplace, hipStream_t s) {
+    hipLaunchKernelGGL(inplace ? k_rv_gen_art<true> : k_rv_gen_art<false>, dim3(count), dim3(kBlock), 0, s, lps);
+}
+// (one-pass forms only: a wave with a searched start does not stage in chunks)
+void launch_rv_pivot_g(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int inplace, hipStream_t s) {
+    hipLaunchKernelGGL((inplace ? k_rv_price<true, false, true> : k_rv_price<false, false, true>), dim3(gp, nact), dim3(kBlock), lds, s, lps, act, 0);
+    hipLaunchKernelGGL((inplace ? k_rv_ftran<RR_LOOP, true, false, true> : k_rv_ftran<RR_LOOP, false, false, true>), dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp, 0);
+    hipLaunchKernelGGL((k_rv_update<RR_LOOP, false, true>), dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr, 0);
 }
 void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s) {
     hipLaunchKernelGGL(k_rv_warm_binv, dim3(m_max, count), dim3(kBlock), 0, s, lps);

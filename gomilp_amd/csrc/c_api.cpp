@@ -319,7 +319,7 @@ int gomilp_debug_solve_plan(int64_t m, int64_t n, int32_t start, double scale_sp
 }
 
 // diagnostic (host only, no device): the routing of one frontier wave.  The root views are made here from the fields WavePlan reads; a
-// General made on the host holds null pointers, which its destructor leaves alone.
+// General / GeneralRev made on the host holds null pointers, which its destructor leaves alone.
 int gomilp_debug_wave_plan(int64_t nroots, const int64_t *root_m, const int64_t *root_n, const int32_t *root_flags, const double *root_scale_span,
                            int64_t count, const int32_t *root_of, const int64_t *koff, const int32_t *var, const double *rhs, int32_t warm_call,
                            const int32_t *warm, int64_t nspent, const int64_t *spent, int64_t nknobs, const char *const *keys, const int64_t *values,
@@ -334,7 +334,9 @@ int gomilp_debug_wave_plan(int64_t nroots, const int64_t *root_m, const int64_t 
         Engine::RootView &V = roots[(size_t)r];
         V.m = (int)root_m[r]; V.n = (int)root_n[r]; V.scale_span = root_scale_span[r];
         V.unit_basis = (root_flags[r] & GOMILP_WP_ROOT_UNIT_BASIS) != 0;
-        if (root_flags[r] & GOMILP_WP_ROOT_GENERAL) V.gen = std::make_shared<Engine::RootView::General>();
+        // (as Engine::root_general: a narrow root keeps its tableau, a wide one within the limits its B0^-1)
+        if ((root_flags[r] & GOMILP_WP_ROOT_GENERAL) && Engine::RootView::general_rev_shape(V.m, V.n)) V.genrev = std::make_shared<Engine::RootView::GeneralRev>();
+        else if (root_flags[r] & GOMILP_WP_ROOT_GENERAL) V.gen = std::make_shared<Engine::RootView::General>();
         V.hb.assign((size_t)V.m, 1.0);
         if (root_flags[r] & GOMILP_WP_ROOT_B_NEGATIVE) V.hb[0] = -1.0;
         V.verify_status = (root_flags[r] & GOMILP_WP_ROOT_VERIFY_BAD) ? GOMILP_ERR_BAD_SHAPE : GOMILP_OK;

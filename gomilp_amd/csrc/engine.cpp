@@ -1360,7 +1360,7 @@ bool Engine::root_view(int64_t id, RootView *out) {
     std::lock_guard<std::mutex> g(mu_);
     if (id < 0 || (size_t)id >= problems_.size() || !problems_[id]) return false;
     const Problem &P = *problems_[id];
-    out->gen.reset();   // a view is reused across roots (gomilp_pool_set_root): never keep the previous root's searched basis
+    out->gen.reset(); out->genrev.reset();   // a view is reused across roots (gomilp_pool_set_root): never keep the previous root's searched basis
     out->m = P.m; out->n = P.n; out->ld = P.ld; out->dAt = P.dAt; out->dc = P.dc; out->db = P.db;
     out->verify_status = P.verify_status; out->serial = P.serial; out->hb = P.hb; out->hc = P.hc; out->scale_span = P.scale_span;
     out->rho0.assign(P.m, 0);
@@ -1390,13 +1390,18 @@ Engine::RootView::RowMajor::~RowMajor() { if (dA) hipFree(dA); }
 Engine::RootView::General::~General() {
     for (void *p : {(void *)dT0, (void *)dxb0, (void *)dbasic0, (void *)dnonbasic0, (void *)dposvar0}) if (p) hipFree(p);
 }
+Engine::RootView::GeneralRev::~GeneralRev() {
+    for (void *p : {(void *)dB0inv, (void *)dxb0, (void *)dbasic0, (void *)dposvar0}) if (p) hipFree(p);
+}
 
 bool Engine::root_general(int64_t id, RootView *out) {
     std::lock_guard<std::mutex> g(mu_);
     if (id < 0 || (size_t)id >= problems_.size() || !problems_[id]) return false;
     const Problem &P = *problems_[id];
     const int m = P.m, n = P.n;
-    if (P.verify_status != GOMILP_OK || m >= n || !((n - m) < 2 * m) || !ensure_host_A(P)) return false;
+    // a wide root (n - m >= 2m) keeps B0^-1 instead of the tableau (GeneralRev), within the limits of SolvePlan::gen_revised
+    const bool wide = m < n && (n - m) >= 2 * m;
+    if (P.verify_status != GOMILP_OK || m >= n || (wide && !RootView::general_rev_shape(m, n)) || !ensure_host_A(P)) return false;
     if (ensure_work(m, n + 1) != GOMILP_OK) return false;
     Work &w = *w_;
     std::vector<int32_t> basic;
@@ -1415,6 +1420,27 @@ bool Engine::root_general(int64_t id, RootView *out) {
     std::vector<double> xb;
     bool sing = false;
     if (final_solve(P, xb, &sing, basic.data()) != GOMILP_OK || sing) return false;
+    if (wide) {
+        std::shared_ptr<RootView::GeneralRev> R(new RootView::GeneralRev);
+        R->m = m; R->ld = P.ld;
+        auto ok = [](hipError_t e) { return e == hipSuccess; };
+        for (int i = 0; i < m; i++) posvar[basic[i]] = i;
+        for (int jp = 0; jp < nn; jp++) posvar[nonbasic[jp]] = -1;
+        if (!ok(dmalloc(&R->dB0inv, (size_t)m * P.ld)) || !ok(dmalloc(&R->dxb0, (size_t)m)) || !ok(dmalloc(&R->dbasic0, (size_t)m)) ||
+            !ok(dmalloc(&R->dposvar0, (size_t)n))) return false;
+        // m x ld with a zeroed padding column: in place from the device search (R^-1 Q^T in the first B^-1 buffer), else the host inverse
+        if (!ok(hipMemsetAsync(R->dB0inv, 0, (size_t)m * P.ld * sizeof(double), stream_))) return false;
+        if (!ok(binv_dev ? hipMemcpy2DAsync(R->dB0inv, (size_t)P.ld * sizeof(double), w.binv[0], (size_t)P.ld * sizeof(double), (size_t)m * sizeof(double), m,
+                                            hipMemcpyDeviceToDevice, stream_)
+                         : hipMemcpy2DAsync(R->dB0inv, (size_t)P.ld * sizeof(double), binv.data(), (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
+                                            hipMemcpyHostToDevice, stream_)))
+            return false;
+        if (!ok(hipMemcpyAsync(R->dxb0, xb.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, stream_)) ||
+            !ok(hipMemcpyAsync(R->dbasic0, basic.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, stream_)) ||
+            !ok(hipMemcpyAsync(R->dposvar0, posvar.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream_)) || !ok(sync_stream())) return false;
+        out->genrev = R;
+        return true;
+    }
     std::shared_ptr<RootView::General> G(new RootView::General);
     G->m = m; G->nn = nn; G->ldt = tab_ld(nn);
     auto ok = [](hipError_t e) { return e == hipSuccess; };

@@ -221,12 +221,27 @@ class Engine {
             ~General();
         };
         std::shared_ptr<General> gen;     // null: slack basis, or no usable basis (the single-relaxation engine reports why)
+        // the same search for a WIDE root (n - m >= 2m: the tableau row is what does not fit): the searched basis with its inverse instead
+        // of its tableau, for the batched revised simplex (k_rv_gen_start of batch_revised.hip builds a child's B^-1 from it by copies and
+        // sign flips).  Within the limits of SolvePlan::gen_revised only (general_rev_shape)
+        struct GeneralRev {
+            int m = 0, ld = 0;
+            double *dB0inv = nullptr, *dxb0 = nullptr;       // m x ld row-major B0^-1, padding column zero; x_B0 of the gonum-order solve
+            int32_t *dbasic0 = nullptr, *dposvar0 = nullptr; // m basis positions; per variable (n) its basis position, -1: nonbasic
+            ~GeneralRev();
+        };
+        std::shared_ptr<GeneralRev> genrev;   // null: slack basis, a narrow root, outside the limits, or no usable basis
+        // does a root of this shape get a GeneralRev: wide, the host copy of A within 2^25 entries, the rows within the LDS window
+        static bool general_rev_shape(int64_t m, int64_t n) {
+            return m < n && (n - m) >= 2 * m && m * n <= ((int64_t)1 << 25) && ((m + 1) & ~(int64_t)1) <= kLdsWindowLd;
+        }
         // the root's A row-major on the device (one transposing copy per root): rows of the virtual tableau of a wide wave (BatchLP::A0r)
         struct RowMajor { double *dA = nullptr; int lda = 0; ~RowMajor(); };
         std::shared_ptr<RowMajor> rm;     // null: not made (large roots)
     };
     bool root_view(int64_t id, RootView *out);
-    // fills out->gen for a root without a slack basis (false: not possible — too large for the host copy of A, singular, ...)
+    // fills out->gen (narrow roots) or out->genrev (wide roots) for a root without a slack basis (false: not possible — too large for the
+    // host copy of A, singular, ...)
     bool root_general(int64_t id, RootView *out);
     // epilogue of simplex() (simplex.go:296-301) for a relaxation whose pivot loop ran elsewhere: final basis positions
     // `basic` (m entries) and updated x_B in, gonum-order solve of that basis, z, x out; `loop_rc` as Engine::solve

@@ -61,11 +61,20 @@ void RevBatchEngine::release() {
 }
 
 bool RevBatchEngine::eligible(const Engine::RootView &R, int K_min, int K_max, int exact_degenerate, int cond_guard, int large_rows) {
-    if (R.verify_status != GOMILP_OK || !R.unit_basis) return false;
+    // a wide root without a slack basis counts where it carries its searched basis (RootView::GeneralRev: pool knob rev_general)
+    const bool gen = !R.unit_basis && R.genrev;
+    if (R.verify_status != GOMILP_OK || !(R.unit_basis || gen)) return false;
     const int m_lo = R.m + K_min, m_hi = R.m + K_max, n_hi = R.n + K_max;
     if (m_hi >= n_hi || (R.n - R.m) < 2 * m_hi) return false;   // the revised formulation (engine.cpp: use_tab's n - m < 2m rule)
-    // the exact-step guard is off for every shape: the blocked tableau with exact steps stays on the workers
-    if (SolvePlan::exact_wanted(exact_degenerate, m_lo, true, R.scale_span)) return false;
+    if (gen) {
+        // the guarded loop (G = true of K1-K3) with the hand-over of exact steps: modes 1 and 2, where a worker's solve of such a start
+        // runs with guard = 1e-9; mode 0 (no guard) and strict mode stay on the workers.  One-pass staging only, up to kRevGeneralMaxRows
+        if (exact_degenerate != 1 && exact_degenerate != 2) return false;
+        if (m_hi > kRevGeneralMaxRows || ((m_hi + 1) & ~1) > kLdsWindowLd) return false;
+    } else if (SolvePlan::exact_wanted(exact_degenerate, m_lo, true, R.scale_span)) {
+        // the exact-step guard is off for every shape: the blocked tableau with exact steps stays on the workers
+        return false;
+    }
     if (cond_guard && m_lo <= 64) return false;                  // the replay of gonum's condition guards runs in Engine::solve only
     // pools keep the row limit of one-pass LDS staging unless the knob large_rows lifts it (the chunked kernels of batch_revised.hip)
     if (!large_rows && ((m_hi + 1) & ~1) > kLdsWindowLd) return false;
@@ -73,7 +82,7 @@ bool RevBatchEngine::eligible(const Engine::RootView &R, int K_min, int K_max, i
 }
 
 void RevBatchEngine::layout(const int64_t *root_m, const int64_t *root_n, int64_t count, const int32_t *root_of, const int64_t *koff, bool inplace,
-                            Lay *lay, size_t *at_tot_out, size_t *wk_tot_out) {
+                            Lay *lay, size_t *at_tot_out, size_t *wk_tot_out, const char *root_gen) {
     size_t at_tot = 0, wk_tot = 0;
     for (int64_t i = 0; i < count; i++) {
         const int r = root_of ? root_of[i] : 0;
@@ -90,6 +99,10 @@ void RevBatchEngine::layout(const int64_t *root_m, const int64_t *root_n, int64_
         L.pkp = take(kMaxPartials); L.pkr = take(kMaxPartials); L.pip = take(kMaxPartials / 2); L.pir = take(kMaxPartials / 2);
         L.st = take((sizeof(DevState) + 7) / 8);
         L.art = inplace ? take(ld) : 0;   // (behind everything else: the other offsets of a relaxation are those of the assembled layout)
+        // a searched start: the price / ratio keys with the workgroups' runner-up keys behind them (pk2 = pk + kMaxPartials of the G helpers);
+        // behind everything else too — a relaxation of a slack root keeps its layout
+        L.gpkp = L.gpkr = 0;
+        if (root_gen && root_gen[r]) { L.gpkp = take(2 * kMaxPartials); L.gpkr = take(2 * kMaxPartials); }
         L.wk1 = wk_tot;
         if (lay) lay[i] = L;
     }
@@ -121,6 +134,12 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
         root_used[(size_t)(root_of ? root_of[i] : 0)] = 1;
     }
     const int ld_max = (m_max + 1) & ~1;
+    // roots without a slack basis (pool knob rev_general): their relaxations start from the root's searched basis and run the guarded loop
+    std::vector<char> root_gen((size_t)nroots, 0);
+    int64_t ngen = 0;
+    for (int r = 0; r < nroots; r++) root_gen[(size_t)r] = root_used[(size_t)r] && !roots[r]->unit_basis && roots[r]->genrev ? 1 : 0;
+    for (int64_t i = 0; i < count; i++) ngen += root_gen[(size_t)(root_of ? root_of[i] : 0)];
+    if (ngen && (ld_max > kLdsWindowLd || (large_rows_ && row_chunk_ > 0))) return GOMILP_ERR_BAD_SHAPE;   // (WavePlan: one-pass staging only)
 
     // ---- warm starts: the kept WK_REVISED state that parent[i] names, where this relaxation's rows extend its rows (bitwise prefix) by J >= 1
     struct Plan { std::shared_ptr<WarmEntry> e; int J = 0; size_t kp = 0; };
@@ -134,6 +153,7 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
             if (warm->parent[i] < 0 || K < 1) continue;
             std::shared_ptr<WarmEntry> e = warm->store->find(warm->parent[i]);
             const Engine::RootView &R = root_at(i);
+            if (!R.unit_basis) continue;   // (a searched start runs cold)
             if (!e || e->kind != WK_REVISED || e->root_serial != R.serial || e->K >= K || e->m != R.m + e->K || e->n != R.n + e->K ||
                 (int)e->hbasic.size() != e->m || (int)e->kvar.size() != e->K) continue;
             const int64_t k0 = koff[i];
@@ -157,7 +177,7 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
     {
         std::vector<int64_t> root_m((size_t)nroots), root_n((size_t)nroots);
         for (int r = 0; r < nroots; r++) if (root_used[(size_t)r]) { root_m[(size_t)r] = roots[r]->m; root_n[(size_t)r] = roots[r]->n; }
-        layout(root_m.data(), root_n.data(), count, root_of, koff, inplace, lay.data(), &at_tot, &wk_tot);
+        layout(root_m.data(), root_n.data(), count, root_of, koff, inplace, lay.data(), &at_tot, &wk_tot, root_gen.data());
     }
     // one block per used root in the shared arena: b0 (m_r) | c2 = [c, 0...] (n_r + K_max + 2) among the doubles, rho0 (m_r + 1) among the ints
     struct RootBlk { size_t b0 = 0, c2 = 0, rho = 0; };
@@ -230,7 +250,7 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
         const Engine::RootView &R = *roots[r];
         double *h_b0 = hk.data() + blk[(size_t)r].b0, *h_c2 = hk.data() + blk[(size_t)r].c2;
         int32_t *h_rho = h_var + blk[(size_t)r].rho;
-        for (int i = 0; i < R.m; i++) { h_b0[i] = R.hb[(size_t)i]; h_rho[i] = R.rho0[(size_t)i]; }
+        for (int i = 0; i < R.m; i++) { h_b0[i] = R.hb[(size_t)i]; h_rho[i] = R.unit_basis ? R.rho0[(size_t)i] : 0; }
         for (int j = 0; j < R.n; j++) h_c2[j] = R.hc[(size_t)j];   // c' = [c, 0] (subproblem.go:110-114)
     }
     for (int64_t i = 0; i < count && nwarm; i++) {
@@ -275,6 +295,13 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
         d.exch_on = exchange_ ? 1 : 0; d.x_added = -1; d.x_best = 0xFFFFFFFFu;
         d.At0 = R.dAt; d.ld0 = R.ld; d.avar = d_var + (koff[i] - k_base); d.asign = d_sign + (koff[i] - k_base);
         d.inplace = inplace ? 1 : 0; d.art = inplace ? w + L.art : nullptr;
+        d.gminidx = -1;
+        if (root_gen[(size_t)(root_of ? root_of[i] : 0)]) {
+            const Engine::RootView::GeneralRev &G = *R.genrev;
+            d.gen = 1; d.gB0inv = G.dB0inv; d.gxb0 = G.dxb0; d.gbasic0 = G.dbasic0; d.gposvar0 = G.dposvar0; d.ldg = G.ld;
+            d.guard = 1e-9;   // (SolvePlan::guard of a searched start at exact_degenerate 1 / 2: RevBatchEngine::eligible)
+            d.pk_price = reinterpret_cast<unsigned long long *>(w + L.gpkp); d.pk_ratio = reinterpret_cast<unsigned long long *>(w + L.gpkr);
+        }
         const Plan &P = plan[(size_t)i];
         if (P.e) {
             d.warm = 1; d.wJ = P.J; d.wmp = P.e->m; d.wldp = P.e->ld;
@@ -293,6 +320,11 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
     launch_rv_init(b.d_lps, (int)count, ip, stream_);
     launches++;
     if (nwarm) { launch_rv_warm_binv(b.d_lps, (int)count, m_max, stream_); launches++; }
+    if (ngen) {
+        launch_rv_gen_start(b.d_lps, (int)count, m_max, stream_);
+        launch_rv_gen_art(b.d_lps, (int)count, ip, stream_);
+        launches += 2;
+    }
     RV_TRY(hipStreamSynchronize(stream_));   // (the pageable staging vectors go out of use here)
     RV_TRY(hipGetLastError());
 
@@ -318,23 +350,35 @@ int RevBatchEngine::run(const Engine::RootView *const *roots, int nroots, const 
     int64_t kept = 0;
     int64_t steps = 0;
     int rc = GOMILP_OK;
+    std::vector<char> is_gen((size_t)count, 0);
+    for (int64_t i = 0; i < count; i++) is_gen[(size_t)i] = root_gen[(size_t)(root_of ? root_of[i] : 0)];
     while (!act.empty()) {
         const int nact = (int)act.size();
+        // (the relaxations of searched starts behind the others: their loop pivots are launches of their own over that part of the list)
+        if (ngen) std::stable_partition(act.begin(), act.end(), [&](int id) { return !is_gen[(size_t)id]; });
+        int nslack = 0;
+        for (int id : act) nslack += is_gen[(size_t)id] ? 0 : 1;
         memcpy(b.h_act, act.data(), (size_t)nact * sizeof(int));
         RV_TRY(hipMemcpyAsync(b.d_act, b.h_act, (size_t)nact * sizeof(int), hipMemcpyHostToDevice, stream_));
         // (the dual launches only while some active relaxation is in the dual stage: a cold wave's list is setup, chunk x pivot, ctrl)
         bool any_dual = false, any_primal = false, any_scan = false;
-        for (int id : act) { (in_dual[(size_t)id] ? any_dual : any_primal) = true; if (in_scan[(size_t)id]) any_scan = true; }
+        for (int id : act) {
+            if (is_gen[(size_t)id]) continue;
+            (in_dual[(size_t)id] ? any_dual : any_primal) = true;
+        }
+        for (int id : act) if (in_scan[(size_t)id]) any_scan = true;
+        const int ng = nact - nslack;
         // (the scan's verdict orders the forced pivot that the set-up launches behind it run: an exchange costs no superstep of its own)
         if (any_scan) { launch_rv_exchange(b.d_lps, b.d_act, nact, nn_max, lds, ck2, ip, stream_); launches += 2; }
         launch_rv_setup(b.d_lps, b.d_act, nact, gr, ld_max, lds, ck2, ip, stream_);
         const int chunk = steps < 2 ? kFirstChunk : kChunk;
         for (int t = 0; t < chunk; t++) {
-            if (any_dual) launch_rv_dual_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, 2 * lds, ck2, ck2d, ip, stream_);
-            if (any_primal) launch_rv_pivot(b.d_lps, b.d_act, nact, gp, gr, lds, ck2, ip, stream_);
+            if (any_dual) launch_rv_dual_pivot(b.d_lps, b.d_act, nslack, gp, gr, lds, 2 * lds, ck2, ck2d, ip, stream_);
+            if (any_primal) launch_rv_pivot(b.d_lps, b.d_act, nslack, gp, gr, lds, ck2, ip, stream_);
+            if (ng) launch_rv_pivot_g(b.d_lps, b.d_act + nslack, ng, gp, gr, lds, ip, stream_);
         }
         launch_rv_ctrl(b.d_lps, b.d_act, nact, b.d_out, stream_);
-        launches += 7 + 4 * chunk * ((any_dual ? 1 : 0) + (any_primal ? 1 : 0)) + 1;
+        launches += 7 + 4 * chunk * ((any_dual ? 1 : 0) + (any_primal ? 1 : 0)) + (ng ? 3 * chunk : 0) + 1;
         RV_TRY(hipMemcpyAsync(b.h_out, b.d_out, (size_t)count * sizeof(RevOut), hipMemcpyDeviceToHost, stream_));
         RV_TRY(hipStreamSynchronize(stream_));
         RV_TRY(hipGetLastError());

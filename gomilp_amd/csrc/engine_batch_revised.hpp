@@ -3,6 +3,8 @@
 // fixed list of launches per superstep for the whole wave, one host round trip per superstep.  It takes exactly the waves whose
 // relaxations a worker's Engine::solve would run on the revised pipelines without the exact-step guard, and computes what that
 // solve computes: the kernels run the helpers of simplex_helpers.h, the stages follow Engine::solve_locked / run_loop / host_bland.
+// With pool knob rev_general it also takes the children of wide roots WITHOUT a slack basis, from the root's searched basis: those run
+// the guarded loop and leave the schedule (BS_HOST) wherever a worker's solve would decide on a fresh gonum-order solve.
 #pragma once
 #include <stdint.h>
 
@@ -22,6 +24,12 @@ class RevBatchEngine {
     // do children of this root with K_min..K_max branch rows run on the revised pipelines, unguarded, on a worker with these knobs?
     // (what SolvePlan::make decides per solve — use_tab, SolvePlan::exact_wanted, replay_if_feasible — for the whole range of children)
     // large_rows (the pool knob): the row limit of one-pass LDS staging (ld <= kLdsWindowLd) is dropped, every other condition stays
+    // A wide root WITHOUT a slack basis passes where it carries RootView::genrev (pool knob rev_general, DESIGN.md section 2.5e "Equality-form
+    // roots"): its children run the guarded loop (guard = 1e-9, exact_degenerate 1 or 2) and leave the schedule where a worker would take
+    // an exact step; children of up to kRevGeneralMaxRows rows (the range the route is tested and timed over), one-pass staging only.
+    // kRevGeneralAutoRows: what WavePlan routes at rev_general = 1 — at 81 rows the schedule runs a 24-child wave as fast as eight workers,
+    // at 161 rows 11 % and at 300 rows 43 % slower (the workers solve such children on the blocked tableau, eight pivots per launch)
+    static constexpr int kRevGeneralMaxRows = 300, kRevGeneralAutoRows = 96;
     static bool eligible(const Engine::RootView &R, int K_min, int K_max, int exact_degenerate, int cond_guard, int large_rows = 0);
     // The wave (relaxation i is a child of roots[root_of[i]] — root_of null: of roots[0] — with rows koff[i]..koff[i+1] of var / sign /
     // rhs; every root the wave uses must pass `eligible` with its own children's K range).  One schedule for the whole wave: each
@@ -61,12 +69,13 @@ class RevBatchEngine {
     // The layout of a wave's two arenas, in doubles, per relaxation: offsets into the work arena (cleared per wave; [wk0, wk1) is the
     // relaxation's own part) and `at` into the At arena.  inplace: no At (at = 0 everywhere, *at_tot = 0) and `art`, the ld-long row of
     // the artificial column, in the work arena (unused otherwise).
-    struct Lay { size_t wk0, wk1; size_t at, binv0, binv1, xb, y, dvec, move, bb, rvec, c1, ysc, basic, nonbasic, inb, pkp, pkr, pip, pir, st, art; };
+    struct Lay { size_t wk0, wk1; size_t at, binv0, binv1, xb, y, dvec, move, bb, rvec, c1, ysc, basic, nonbasic, inb, pkp, pkr, pip, pir, st, art, gpkp, gpkr; };
     // A pure function of the shapes (no HIP call): relaxation i is a child of root root_of[i] (null: of root 0; the caller has checked the
     // range) with koff[i + 1] - koff[i] branch rows.  lay: null, or room for count entries.  run sizes its buffers from it, and
-    // gomilp_debug_rev_footprint reports it.
+    // gomilp_debug_rev_footprint reports it.  root_gen: null, or per root whether it has no slack basis but a searched one (RootView::genrev):
+    // its relaxations take 4 * kMaxPartials doubles more, at the tail (gpkp / gpkr: the price and ratio keys with their runner-ups).
     static void layout(const int64_t *root_m, const int64_t *root_n, int64_t count, const int32_t *root_of, const int64_t *koff, bool inplace,
-                       Lay *lay, size_t *at_tot, size_t *wk_tot);
+                       Lay *lay, size_t *at_tot, size_t *wk_tot, const char *root_gen = nullptr);
 
     // gives the wave buffers back (they grow with the largest wave seen: 5 MB per 300 x 1500 relaxation); the pool calls it when the
     // root changes

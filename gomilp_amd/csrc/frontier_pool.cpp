@@ -20,7 +20,7 @@ namespace gomilp {
 PoolKnobs::Scope PoolKnobs::scope(const char *key) {
     const std::string k(key);
     for (const char *p : {"batched", "batch_revised", "warm_revised", "rev_exchange", "rev_roots", "split_large", "split_phase", "large_loop",
-                          "batch_virt", "batch_res", "batch_loop", "sample_batch", "lu_large", "large_rows", "rev_inplace", "rev_mem_limit"})
+                          "batch_virt", "batch_res", "batch_loop", "sample_batch", "lu_large", "large_rows", "rev_inplace", "rev_mem_limit", "rev_general"})
         if (k == p) return Scope::Pool;
 #ifdef GOMILP_DEBUG
     if (k == "bt_fault") return Scope::PoolAndWorkers;
@@ -39,6 +39,11 @@ bool PoolKnobs::set(const char *key, int64_t value) {
         {"large_rows", &large_rows}, {"rev_inplace", &rev_inplace}};
     for (auto &f : flags) if (k == f.name) { *f.at = value ? 1 : 0; return true; }
     if (k == "lu_large") return true;
+    if (k == "rev_general") {   // 0 off, 1 up to kRevGeneralAutoRows rows, 2 up to kRevGeneralMaxRows
+        if (value < 0 || value > 2) return false;
+        rev_general = (int)value;
+        return true;
+    }
     if (k == "rev_mem_limit") {   // MiB; 0: none
         if (value < 0) return false;
         rev_mem_limit = value;
@@ -103,7 +108,8 @@ WavePlan WavePlan::make(const Engine::RootView *const *views, int nroots, const 
     // knob warm_revised the warm call: relaxations whose parent's kept state is of this schedule start from it (section 2.6b).
     // Rows beyond the LDS window (ld > 8192) only with the knob large_rows: the chunked kernels of batch_revised.hip.
     // The test runs over the roots the WAVE uses, each with the K range of its own children; roots the pool merely holds do not count.
-    // One used root that fails (narrow, no slack basis, a guarded size, a verify verdict) sends the wave where it went before, whole.
+    // One used root that fails (narrow, no basis to start from, a guarded size, a verify verdict) sends the wave where it went before, whole.
+    // A used root without a slack basis passes with its searched basis (RootView::genrev, knob rev_general): the guarded loop, per relaxation.
     if (!knobs.batch_revised || (warm_call && !knobs.warm_revised) || knobs.refresh != 0) return p;
     std::vector<int> k_lo((size_t)nroots, INT32_MAX), k_hi((size_t)nroots, -1);
     bool other_root = false;   // the wave uses more than one root, or a root other than the set_root problem
@@ -113,6 +119,12 @@ WavePlan WavePlan::make(const Engine::RootView *const *views, int nroots, const 
         if (ri != 0) other_root = true;
     }
     bool use_rev = knobs.rev_roots || !other_root;
+    // a used root without a slack basis (RootView::genrev): knob rev_general, cold calls, one-pass staging (no CK x G kernel instances),
+    // and children of up to kRevGeneralAutoRows rows (measured no slower than the workers) unless the knob is 2
+    const int gen_rows = knobs.rev_general >= 2 ? RevBatchEngine::kRevGeneralMaxRows : RevBatchEngine::kRevGeneralAutoRows;
+    for (int r = 0; r < nroots && use_rev; r++)
+        if (k_hi[(size_t)r] >= 0 && !views[r]->unit_basis &&
+            (!knobs.rev_general || warm_call || (knobs.large_rows && knobs.row_chunk > 0) || views[r]->m + k_hi[(size_t)r] > gen_rows)) use_rev = false;
     for (int r = 0; r < nroots && use_rev; r++)
         if (k_hi[(size_t)r] >= 0) use_rev = RevBatchEngine::eligible(*views[r], k_lo[(size_t)r], k_hi[(size_t)r], knobs.exact_degenerate, knobs.cond_guard, knobs.large_rows);
     // (a branch row on one of its root's slack columns: the child has no slack basis)
@@ -319,7 +331,7 @@ struct Wave {
             if (tableau) cold_again.push_back(i);
             return;
         }
-        if (o.stage != gomilp::BS_DONE) {   // a path the device schedule does not cover (revised: the |x_art| band; with rev_exchange = 0 the zero-level artificial exchange)
+        if (o.stage != gomilp::BS_DONE) {   // a path the device schedule does not cover (revised: the |x_art| band; with rev_exchange = 0 the zero-level artificial exchange; a searched start's start guard and exact steps)
             agg.host_fallbacks++;
             submit_whole(i);
             return;

@@ -52,6 +52,12 @@ struct PoolKnobs {
                                 // A^T in place and synthesise the K branch entries and unit columns (rev_child_col.h) — no At arena ((n + 1) x ld
                                 // doubles per relaxation), no k_rv_assemble launch, bit-identical results; 0: today's launches.  Routing does not
                                 // depend on it
+    int rev_general = 1;        // wide waves of roots WITHOUT a slack basis (equality rows; RootView::genrev) run on the batched revised simplex too:
+                                // a child starts from its root's searched basis + its branch slacks (k_rv_gen_start), runs the guarded loop, and
+                                // goes to a worker's whole solve where that would take an exact step (host_fallbacks); cold calls, one-pass
+                                // staging, exact_degenerate 1 or 2.  1: children of up to RevBatchEngine::kRevGeneralAutoRows rows (beyond, the
+                                // workers' blocked tableau is faster: DESIGN.md section 2.5e); 2: up to kRevGeneralMaxRows rows; 0: such waves on
+                                // the workers, whole
     int64_t rev_mem_limit = 0;  // MiB, 0: none.  Where it is below the free device memory it takes its place in RevBatchEngine::run's test of
                                 // whether a wave's buffers fit (a wave that does not fit runs on the workers, whole): a cap for a shared card
     int64_t max_pivots = 0;     // the workers' knob of this name, as the batched revised simplex needs it (negative: 0)

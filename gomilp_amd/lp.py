@@ -368,7 +368,10 @@ class FrontierPool:
         "large_rows" (1: roots and children beyond 8192 rows, wide waves on that schedule's chunked kernels; default 0: refused),
         "rev_inplace" (1: that schedule reads the root's A^T in place instead of a copy per child — bit-identical, most of a wave's memory
         saved, see debug_rev_footprint; default 0), "rev_mem_limit" (MiB, 0: none: a cap on the free memory that schedule's wave buffers
-        must fit; a wave that does not fit runs on the workers), the other pool knobs of include/gomilp_lp.h, or any Context knob."""
+        must fit; a wave that does not fit runs on the workers), "rev_general" (1, default: wide waves of a root without a slack basis —
+        equality rows — run on that schedule too, from the root's searched basis, handing a relaxation to a worker where a decision needs a
+        fresh solve: host_fallbacks — children of up to 96 rows; 2: of up to 300 rows, slower than the workers there; 0: on the workers,
+        whole), the other pool knobs of include/gomilp_lp.h, or any Context knob."""
         rc = lib().gomilp_pool_set(self._h, key.encode(), int(value))
         if rc != OK:
             raise ValueError("bad knob %s=%s" % (key, value))
@@ -409,7 +412,8 @@ class FrontierPool:
         """children: list of constraint lists [(var, sign, rhs), ...]; roots: per child the index of its root
         (default: all children of the set_root problem).  Independent LPs: children [] of different roots.  The wave runs
         device-batched when one schedule takes every root it uses: narrow roots (n - m < 2m) the tableau schedule, wide roots with a
-        slack basis the batched revised simplex (knobs batch_revised, rev_roots; the roots may differ in shape).  A wave that mixes the
+        slack basis — and, knob rev_general, wide roots with equality rows — the batched revised simplex (knobs batch_revised, rev_roots;
+        the roots may differ in shape).  A wave that mixes the
         two kinds runs on the workers, whole; roots the pool holds but the wave does not use play no part."""
         pk = pack_children(children)   # (a PackedChildren is taken as is)
         count, koff, var, sign, rhs = pk.count, pk.koff, pk.var, pk.sign, pk.rhs

@@ -296,7 +296,15 @@ void gomilp_pool_destroy(gomilp_pool *pool);
  * device.  Routing does not depend on it; 0: the launches as they were.  gomilp_debug_rev_footprint gives both footprints),
  * "rev_mem_limit" (MiB, default 0: none; a negative value is GOMILP_ERR_BAD_SHAPE: where it is below the free device memory it takes its
  * place in that schedule's test of whether a wave's buffers fit — a cap on the wave buffers for a caller on a shared card; a wave that does
- * not fit runs on the workers, whole); any gomilp_ctx_set key is forwarded to the worker contexts ("row_chunk" is remembered
+ * not fit runs on the workers, whole), "rev_general" (default 1: a WIDE wave of a root WITHOUT a slack basis — equality rows, the
+ * standard form [[A, 0], [G, I]] — takes that schedule too.  The column search runs once per root (gomilp_pool_set_root /
+ * gomilp_pool_add_root keep the searched basis, its inverse and its x_B); a child starts from that basis and its K branch slacks, built on
+ * the device by copies and sign flips, runs the loops with the exact-step guard of such starts (1e-9), and is handed to a worker's whole
+ * solve — counted in host_fallbacks — wherever its start or a pivot has to be decided on a fresh gonum-order solve.  Bit-identical to the
+ * worker path.  Cold calls, exact_degenerate 1 or 2, one-pass staging (not with "large_rows" and "row_chunk" set), roots of up to 2^25
+ * entries, children of up to 96 rows — where a 24-child wave runs as fast as on eight workers; 2: children of up to 300 rows, measured 11 %
+ * slower at 160 and 43 % slower at 300 rows than the workers, which solve such children on the blocked tableau.  Everything else, and the
+ * knob at 0: such waves on the workers, whole, as before; other values are GOMILP_ERR_BAD_SHAPE.  DESIGN.md section 2.5e); any gomilp_ctx_set key is forwarded to the worker contexts ("row_chunk" is remembered
  * by the pool as well). */
 int gomilp_pool_set(gomilp_pool *pool, const char *key, int64_t value);
 /* Upload the root standard form (row-major A0, stride lda) to every worker context of the pool. */
@@ -370,9 +378,10 @@ int gomilp_pool_release_warm(gomilp_pool *pool, int64_t tag);   /* tag < 0: all 
 /* Several roots in one pool: relaxation i of a wave is a child (K_i >= 0 rows) of root root_of[i]; index 0 is the root of
  * gomilp_pool_set_root, gomilp_pool_add_root returns 1, 2, ... (or -(gomilp_status)).  Independent LPs of similar shape
  * are children with K = 0 of different roots: they advance together through the device-batched schedule (one launch per
- * kernel type for all of them) — narrow relaxations (n - m < 2m) on the tableau schedule, WIDE ones (n - m >= 2m, slack
- * starts) on the batched revised simplex of pool knob "batch_revised" (pool knob "rev_roots"), where the roots may differ in
- * rows and columns.  Which schedule takes the wave is decided over the roots the wave uses; a wave that mixes roots of both
+ * kernel type for all of them) — narrow relaxations (n - m < 2m) on the tableau schedule, WIDE ones (n - m >= 2m: slack
+ * starts, and with pool knob "rev_general" roots without a slack basis) on the batched revised simplex of pool knob
+ * "batch_revised" (pool knob "rev_roots"), where the roots may differ in rows and columns and a wave may mix the two kinds of
+ * wide roots: one schedule, the exact-step guard per relaxation.  Which schedule takes the wave is decided over the roots the wave uses; a wave that mixes roots of both
  * kinds, or uses a root no schedule takes, runs on the workers, whole (one relaxation per stream): it is not split.
  * gomilp_frontier_solve_warm names no roots: its wave is one of root 0, whatever else the pool holds.
  * x_out has row stride ldx >= the widest root; gomilp_pool_set_root drops the added roots. */
@@ -424,7 +433,9 @@ int gomilp_debug_solve_plan(int64_t m, int64_t n, int32_t start, double scale_sp
 
 /* Diagnostic (host only, no device): where a pool that holds the given roots would send one frontier wave under the given pool knobs
  * (nknobs key / value pairs of gomilp_pool_set's own keys) — the routing table of DESIGN.md section 2.5f.  A root is its m, n,
- * scale_span and GOMILP_WP_ROOT_* flags (a root with B_NEGATIVE has some b_i < 0); the wave is count / root_of (NULL: all of root 0) /
+ * scale_span and GOMILP_WP_ROOT_* flags (a root with B_NEGATIVE has some b_i < 0; one with GENERAL carries its searched basis as
+ * gomilp_pool_set_root would give it: the tableau of a narrow root, the inverse of a wide one with m n <= 2^25 — pool knob "rev_general");
+ * the wave is count / root_of (NULL: all of root 0) /
  * koff / var / rhs as gomilp_frontier_solve_roots takes them.  warm_call: the wave comes through gomilp_frontier_solve_warm; then warm[i]
  * != 0 says that relaxation i names a parent whose kept tableau is resident, and spent[0 .. nspent) lists warm starts that spend their
  * dual budget and come back into the cold part.  Out: *route (0 workers, 1 batched revised simplex, 2 tableau schedule), *cut (how the
@@ -446,7 +457,8 @@ int gomilp_debug_wave_plan(int64_t nroots, const int64_t *root_m, const int64_t 
  * columns and ld_i = m_i rounded up to even: out[0], doubles of the arena of assembled A^T copies, is the sum of (n_i + 1) * ld_i, or 0
  * with inplace; out[1], doubles of the work arena (both B^-1, the vectors, the lists), is larger by the sum of ld_i with inplace — the
  * rows of the artificial columns.  The schedule takes the wave when (out[0] + out[1]) * 8 bytes, plus a sixteenth, plus 256 MiB fit the
- * free device memory (or pool knob "rev_mem_limit").  Returns GOMILP_OK, or -GOMILP_ERR_BAD_SHAPE for a bad shape or list. */
+ * free device memory (or pool knob "rev_mem_limit").  The probe describes roots with a slack basis; a child of a root without one (pool knob
+ * "rev_general") takes 4 * kMaxPartials doubles more of the work arena, the runner-up keys of its guarded pivots.  Returns GOMILP_OK, or -GOMILP_ERR_BAD_SHAPE for a bad shape or list. */
 int gomilp_debug_rev_footprint(int64_t nroots, const int64_t *root_m, const int64_t *root_n, int64_t count, const int32_t *root_of,
                                const int64_t *koff, int32_t inplace, int64_t *out /* [2] */);
 
