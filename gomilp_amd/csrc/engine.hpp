@@ -454,6 +454,7 @@ void launch_gs_init_perm(double *QT, double *Rinv, int ldq, int m, const int32_t
 void launch_gs_candidate(const double *acol, double *QT, double *Rinv, int ldq, int m, double *w, double *t, double *ypart, int cand, int32_t *idxs, GsState *st, hipStream_t s,
                          int last = 0);
 int launch_luc_rounds_cross(const LUArgs &base, int32_t *pivrow, int nrounds, int round_base, double *xrec, int G, int slots, hipStream_t s);
+void launch_luc_cross_panel(const LUArgs &a, int32_t *pivrow, double *xrec, int G, int slots, int nrole, hipStream_t s);   // lu_cross.hip: one panel launch of those rounds
 size_t luc_cross_doubles();
 void launch_luc_lpos_final(const LUArgs &a, hipStream_t s);
 int luc_cross_groups(int m, int want);

@@ -33,6 +33,7 @@
 #include <algorithm>
 
 #include "device_types.h"
+#include "engine.hpp"
 #include "kernels_common.h"
 #include "luc_role.h"
 
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(T) void k_luc_panel_slots(LUArgs a, int32_t *__rest
     const size_t ldw = (size_t)a.ldw;
     const int k0 = a.ctl_prev->k_next;
     if (k0 >= m) {
-        if (tid == 0) { ctl->nsteps = 0; ctl->ndrop = 0; ctl->nnext = 0; ctl->k_next = k0; ctl->k0 = k0; ctl->k1 = k0; ctl->rounds = a.ctl_prev->rounds; }
+        if (tid == 0) luc_ctl_empty(ctl, a.ctl_prev, k0, false);
         return;
     }
     for (int R = tid; R < MAXM; R += T) {
@@ -126,20 +127,8 @@ __global__ __launch_bounds__(T) void k_luc_panel_slots(LUArgs a, int32_t *__rest
     }
     if (w == 0) {
         // the first NB columns >= k0 that are dense for sure
-        int n = 0;
-        for (int base = k0; base < m && n < NB; base += 64) {
-            const int k = base + lane;
-            bool dense = false;
-            if (k < m) {
-                const idx_t ur = s_unit[k];
-                dense = ur == NONE || !s_active[ur];
-            }
-            const unsigned long long mask = __ballot(dense);
-            const int rank = __popcll(mask & ((1ull << lane) - 1ull));
-            if (dense && n + rank < NB) s_slotcol[n + rank] = k;
-            n += __popcll(mask);
-        }
-        if (lane == 0) s_nload = n < NB ? n : NB;
+        const int n = luc_scan_dense<NB>(k0, m, s_unit, s_active, s_slotcol);
+        if (lane == 0) s_nload = n;
     }
     __syncthreads();
     const int nload = s_nload;
@@ -155,7 +144,7 @@ __global__ __launch_bounds__(T) void k_luc_panel_slots(LUArgs a, int32_t *__rest
         if (!s_stop) {
             if (tid == 0) {
                 a.ctl_base->fault = 1;
-                ctl->nsteps = 0; ctl->ndrop = 0; ctl->nnext = 0; ctl->k_next = k0; ctl->k0 = k0; ctl->k1 = k0; ctl->rounds = a.ctl_prev->rounds;
+                luc_ctl_empty(ctl, a.ctl_prev, k0, false);
             }
             return;
         }
@@ -380,20 +369,8 @@ __global__ __launch_bounds__(T) void k_luc_panel_slots(LUArgs a, int32_t *__rest
     if (w == 0) {
         if (LK && a.look) {
             // the columns the next round's panel will load: its own scan (above), run on the state this round leaves
-            int n = 0;
-            for (int base = k1; base < m && n < NB; base += 64) {
-                const int k = base + lane;
-                bool dense = false;
-                if (k < m) {
-                    const idx_t ur = s_unit[k];
-                    dense = ur == NONE || !s_active[ur];
-                }
-                const unsigned long long mask = __ballot(dense);
-                const int rank = __popcll(mask & ((1ull << lane) - 1ull));
-                if (dense && n + rank < NB) ctl->next[n + rank] = k;
-                n += __popcll(mask);
-            }
-            if (lane == 0) ctl->nnext = n < NB ? n : NB;
+            const int n = luc_scan_dense<NB>(k1, m, s_unit, s_active, ctl->next);
+            if (lane == 0) ctl->nnext = n;
         } else if (lane == 0) ctl->nnext = 0;
         const bool on = lane < NB && ((live >> lane) & 1u);
         const unsigned long long msk = __ballot(on);
@@ -705,18 +682,14 @@ static void luc_rounds_slots(const LUArgs &base, int32_t *pivrow, int nrounds, i
 
 // the rows of a round's panel on G workgroups of one XCD (lu_cross.hip, knob lu_cross) with 16 or 32 register slots: the plain schedule
 // with that panel, or (base.look, 32 slots) the look-ahead schedule with it — one launch per round, parities as in luc_rounds_slots
-// (bases beyond 4096 rows, knob lu_large: the eight-workgroup panel with several rows per lane, plain schedule only)
-void launch_luc_cross_panel(const LUArgs &a, int32_t *pivrow, double *xrec, int G, int slots, int nrole, hipStream_t s);
-void launch_luc_large_panel(const LUArgs &a, int32_t *pivrow, double *xrec, int slots, hipStream_t s);
-int luc_large_rpt(int m);
+// (bases beyond 4096 rows, knob lu_large: the same panel with several rows per lane — the launcher picks it by the row count —, plain schedule only)
 int launch_luc_rounds_cross(const LUArgs &base, int32_t *pivrow, int nrounds, int round_base, double *xrec, int G, int slots, hipStream_t s) {
     const int m = base.m, nt = (m + 63) / 64;
     if (!base.look) {
         LUArgs a = base;
         a.ctl_prev = a.ctl; a.Lp_prev = a.Lp; a.Up_prev = a.Up; a.rowsnap_prev = a.rowsnap;
         for (int r = 0; r < nrounds; r++) {
-            if (luc_large_rpt(m)) launch_luc_large_panel(a, pivrow, xrec, slots, s);
-            else launch_luc_cross_panel(a, pivrow, xrec, G, slots, 0, s);
+            launch_luc_cross_panel(a, pivrow, xrec, G, slots, 0, s);
             hipLaunchKernelGGL((k_luc_usolve<kLucSlotSteps>), dim3(nt), dim3(256), 0, s, a);
             hipLaunchKernelGGL((k_luc_trail<kLucSlotSteps>), dim3(nt, nt), dim3(256), 0, s, a);
         }

@@ -25,6 +25,35 @@ __device__ __forceinline__ void luc_st_agent(double *p, double v) {
     __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- what every panel does at the edges of a round ---------------------------------------------------------------------------------
+// The first NB columns >= k that are dense for sure (not the unit column of a row still active: unit / active are the panel's LDS maps,
+// 0xFFFF = no unit column), ascending, into out[]; returns how many, NB at the most.  Called by ONE whole wave, the result is uniform.
+// The start of a round lists the columns it loads with it, the look-ahead hand-over (LUCtl::next) the columns the next round will.
+template <int NB>
+__device__ __forceinline__ int luc_scan_dense(int k, int m, const unsigned short *unit, const unsigned char *active, int *out) {
+    const int lane = (int)threadIdx.x & 63;
+    int n = 0;
+    for (int base = k; base < m && n < NB; base += 64) {
+        const int kk = base + lane;
+        bool dense = false;
+        if (kk < m) {
+            const unsigned short ur = unit[kk];
+            dense = ur == 0xFFFF || !active[ur];
+        }
+        const unsigned long long mask = __ballot(dense);
+        const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+        if (dense && n + rank < NB) out[n + rank] = kk;
+        n += __popcll(mask);
+    }
+    return n < NB ? n : NB;
+}
+// The control block of a round that does nothing (no step left, or a wait that was given up): the next round starts where this one did.
+// ksync: the cross-workgroup panel's replay mark travels along.
+__device__ __forceinline__ void luc_ctl_empty(LUCtl *ctl, const LUCtl *prev, int k0, bool ksync) {
+    ctl->nsteps = 0; ctl->ndrop = 0; ctl->nnext = 0; ctl->k_next = k0; ctl->k0 = k0; ctl->k1 = k0; ctl->rounds = prev->rounds;
+    if (ksync) ctl->ksync = prev->ksync;
+}
+
 // ---- the trailing update of a round, cell by cell (look-ahead schedule) ------------------------------------------------------------
 // a[R][j] += sum_s Lp[s][R] * Up[s][j] in ascending s, zero multipliers skipped — the arithmetic of k_luc_trail (lu_compressed.hip), with the
 // round's panels read straight from L2 (no staging, no barrier): the body of every 256-thread group of the workgroups that run

@@ -1,5 +1,5 @@
 """The compressed LU rounds of the final solve for bases of 4097 .. 16384 rows (context knob lu_large, off by default): eight workgroups
-of one XCD, four (up to 8192 rows) or eight rows per lane (lu_cross.hip k_luc_panel_xl), plain schedule — against one launch per column
+of one XCD, four (up to 8192 rows) or eight rows per lane (lu_cross.hip k_luc_panel_x<8, 4 or 8, ..>), plain schedule — against one launch per column
 (lu_blocked = 0), which tests/test_gpu_revised_reference.py pins to the reference at these sizes.  Bar: identical status and positional
 basis, x and z BIT-IDENTICAL, no fall-back (stats.device_retries == 0).
 

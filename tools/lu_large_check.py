@@ -1,4 +1,4 @@
-"""Developer tool: the compressed LU rounds beyond 4096 rows (lu_cross.hip k_luc_panel_xl, knob lu_large) against one launch per column
+"""Developer tool: the compressed LU rounds beyond 4096 rows (lu_cross.hip k_luc_panel_x with four or eight rows per lane, knob lu_large) against one launch per column
 (lu_blocked = 0: the path these sizes take by default) — same bits — and what the final solve costs with each.  The LPs are those of
 tests/test_gpu_large_rows.py; per schedule one warm-up solve, then three.  lu_cross = 1 / 2 name 16 / 32 register slots where a lane
 holds four rows (up to 8192 rows); eight rows per lane always have 16.
