@@ -114,37 +114,45 @@ struct RevOut {
     int32_t scan, exch;    // 1: the candidate scan of the exchange is ordered (run == RR_EXCH); exchanges done
 };
 
-// launches (batch_revised.hip).  act: list positions -> relaxation; nact entries.  gp / gr: workgroups per relaxation of the pricing
-// kernel and of the row kernels (grid_for_rows of the wave's largest nn / m); lds: bytes of the largest staged vector.
+// the launch geometry of a run: fixed from its first launch to its last, handed to every wrapper below
+struct RevGeom {
+    int gp, gr;                      // workgroups per relaxation of the pricing kernel and of the row kernels (grid_for_rows of the wave's largest nn / m)
+    int ld_max, nn_max, m_max, n_max;   // the wave's largest ld, n + 1 - m, m and n: they size the grids (a relaxation's values do not depend on them)
+    size_t lds;                      // bytes of the largest staged vector of the one-pass kernels (ck2 == 0)
+    // ck2: 0: the one-pass kernels with `lds` bytes, exactly the launches of a wave within the LDS window; > 0: the chunked forms (CK = true), the
+    // staged vector streamed through LDS ck2 double2 at a time (a multiple of 256, at most 4096: ck2 * sizeof(double2) bytes of dynamic LDS,
+    // never more than 64 KB) — the same values, whatever the chunk.  ck2d: the same for the dual pricing kernel, which stages TWO vectors:
+    // 0: one pass with 2 * lds bytes (ld_max <= kRevDualLd); > 0: each vector ck2d <= kRevDualLd / 2 double2 at a time
+    int ck2, ck2d;
+    // 0: the kernels on the assembled At; 1: the wave was not assembled (pool knob rev_inplace) — the IP = true instantiations of the kernels
+    // that read a child's column, which take it from the relaxation's root through ChildCol; the other kernels of a list are the same either way
+    int inplace;
+    hipStream_t stream;
+};
+constexpr int kRevDualLd = 4096;
+
+// launches (batch_revised.hip).  lps, count: the whole wave; act, nact: list positions -> relaxation.  Each returns the number of kernels it
+// launched: the host sums them (RevBatchEngine::Stats::launches).
 // the whole wave's At in one launch, in front of launch_rv_init: grid (n_max + 1 child columns, count relaxations); writes what
 // k_child_assemble (simplex_kernels.hip) writes per child
-void launch_rv_assemble(const RevLP *lps, int count, int n_max, hipStream_t s);
-// inplace (launch_rv_init / _setup / _pivot / _exchange / _dual_pivot): 0: today's kernels on the assembled At, launch for launch; 1: the wave
-// was not assembled (pool knob rev_inplace) — the IP = true instantiations of the kernels that read a child's column, which take it from the
-// relaxation's root through ChildCol; the other kernels of a list are the same either way
-void launch_rv_init(RevLP *lps, int count, int inplace, hipStream_t s);
-// ck2 (launch_rv_setup / _pivot / _exchange / _dual_pivot): 0: the one-pass kernels with `lds` bytes, exactly the launches of a wave within
-// the LDS window; > 0: the chunked forms (CK = true), the staged vector streamed through LDS ck2 double2 at a time (a multiple of 256, at most
-// 4096: ck2 * sizeof(double2) bytes of dynamic LDS, never more than 64 KB) — the same values, whatever the chunk
-void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, int ck2, int inplace, hipStream_t s);   // forced pivot, lists, refresh, check: 7 launches
-void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int ck2, int inplace, hipStream_t s);       // Bland step?, K1, K2, K3: 4 launches
-void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s);
-// the candidate scan of the relaxations with run == RR_EXCH, in front of launch_rv_setup: one workgroup per nonbasic position (nn_max: the
-// wave's largest n + 1 - m), then the verdict and the orders of the forced pivot (2 launches)
-void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, int ck2, int inplace, hipStream_t s);
-// warm starts: B^-1, basis list, b and the orders of every relaxation with warm != 0 (one launch for the wave, grid rows x count);
-// a dual pivot of the relaxations in the dual loop: leaving row, dual pricing, K2 / K3 in their kDualPick form (4 launches;
-// lds2: bytes of the TWO staged vectors of the one-pass pricing kernel, ld_max <= kRevDualLd; ck2d > 0: the chunked pricing kernel
-// instead, each of its two vectors ck2d <= kRevDualLd / 2 double2 at a time — 64 KB of LDS at most)
+int launch_rv_assemble(const RevLP *lps, int count, const RevGeom &g);
+int launch_rv_init(RevLP *lps, int count, const RevGeom &g);
+// warm starts: B^-1, basis list, b and the orders of every relaxation with warm != 0 (grid rows x count)
+int launch_rv_warm_binv(RevLP *lps, int count, const RevGeom &g);
 // searched starts (RevLP::gen; one-pass staging only): launch_rv_gen_start behind launch_rv_init — B^-1, x_B, the lists, b, c1, the start
-// guard and the orders of every relaxation with gen != 0 (one launch for the wave, grid rows x count); launch_rv_gen_art behind it — the
-// Phase-I artificial column of those that start infeasible (one workgroup per relaxation; reads the assembled At, or the root in place);
-// launch_rv_pivot_g: K1-K3 of a loop pivot in their G = true instances over a list of such relaxations (3 launches: no Bland step)
-void launch_rv_gen_start(RevLP *lps, int count, int m_max, hipStream_t s);
-void launch_rv_gen_art(RevLP *lps, int count, int inplace, hipStream_t s);
-void launch_rv_pivot_g(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int inplace, hipStream_t s);
-constexpr int kRevDualLd = 4096;
-void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s);
-void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, int ck2, int ck2d, int inplace, hipStream_t s);
+// guard and the orders of every relaxation with gen != 0 (grid rows x count); launch_rv_gen_art behind it — the Phase-I artificial column of
+// those that start infeasible (one workgroup per relaxation; reads the assembled At, or the root in place)
+int launch_rv_gen_start(RevLP *lps, int count, const RevGeom &g);
+int launch_rv_gen_art(RevLP *lps, int count, const RevGeom &g);
+// the candidate scan of the relaxations with run == RR_EXCH, in front of launch_rv_setup: one workgroup per nonbasic position, then the
+// verdict and the orders of the forced pivot
+int launch_rv_exchange(RevLP *lps, const int *act, int nact, const RevGeom &g);
+int launch_rv_setup(RevLP *lps, const int *act, int nact, const RevGeom &g);        // forced pivot, lists, refresh, check
+int launch_rv_pivot(RevLP *lps, const int *act, int nact, const RevGeom &g);        // a loop pivot: Bland step?, K1, K2, K3
+// a dual pivot of the relaxations in the dual loop: leaving row, dual pricing, K2 / K3 in their kDualPick form
+int launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, const RevGeom &g);
+// K1-K3 of a loop pivot in their G = true instances over a list of relaxations of searched starts (no Bland step)
+int launch_rv_pivot_g(RevLP *lps, const int *act, int nact, const RevGeom &g);
+int launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, const RevGeom &g);
 
 }  // namespace gomilp

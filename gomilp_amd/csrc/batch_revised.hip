@@ -822,71 +822,78 @@ __global__ void k_rv_exch_pick(RevLP *__restrict__ lps, const int *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-// host-callable launch wrappers
+// host-callable launch wrappers: each takes the run's RevGeom and returns how many kernels it launched (rv_launch: one, counted)
 // ------------------------------------------------------------------------------------------------
-void launch_rv_assemble(const RevLP *lps, int count, int n_max, hipStream_t s) {
-    hipLaunchKernelGGL(k_rv_assemble, dim3(n_max + 1, count), dim3(kBlock), 0, s, lps);
+template <class... P, class... A>
+static int rv_launch(void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A... a) {
+    hipLaunchKernelGGL(k, grid, block, lds, s, a...);
+    return 1;
+}
+
+int launch_rv_assemble(const RevLP *lps, int count, const RevGeom &g) {
+    return rv_launch(k_rv_assemble, dim3(g.n_max + 1, count), dim3(kBlock), 0, g.stream, lps);
 }
 // (inplace: the IP = true instantiation of every kernel that reads a child's column; 0: the IP = false ones, the kernels as they were)
-void launch_rv_init(RevLP *lps, int count, int inplace, hipStream_t s) {
-    hipLaunchKernelGGL(inplace ? k_rv_init<true> : k_rv_init<false>, dim3(count), dim3(kBlock), 0, s, lps);
+int launch_rv_init(RevLP *lps, int count, const RevGeom &g) {
+    return rv_launch(g.inplace ? k_rv_init<true> : k_rv_init<false>, dim3(count), dim3(kBlock), 0, g.stream, lps);
 }
 // (ck2 > 0: the CK = true instances, ck2 double2 of dynamic LDS; 0: the one-pass instances with `lds` bytes)
 static size_t rv_lds(size_t lds, int ck2) { return ck2 > 0 ? (size_t)ck2 * sizeof(double2) : lds; }
 
 // K2 and K3 of one pivot of MODE (nparts_price: the workgroups of the pricing launch in front, 0: none)
 template <int MODE>
-static void launch_rv_k23(RevLP *lps, const int *act, int nact, int gr, int nparts_price, size_t lds, int ck2, int inplace, hipStream_t s) {
-    const auto k2 = ck2 > 0 ? (inplace ? k_rv_ftran<MODE, true, true> : k_rv_ftran<MODE, false, true>)
-                            : (inplace ? k_rv_ftran<MODE, true, false> : k_rv_ftran<MODE, false, false>);
-    hipLaunchKernelGGL(k2, dim3(gr, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, nparts_price, ck2);
-    hipLaunchKernelGGL((ck2 > 0 ? k_rv_update<MODE, true> : k_rv_update<MODE, false>), dim3(gr, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, gr, ck2);
+static int launch_rv_k23(RevLP *lps, const int *act, int nact, int nparts_price, const RevGeom &g) {
+    const auto k2 = g.ck2 > 0 ? (g.inplace ? k_rv_ftran<MODE, true, true> : k_rv_ftran<MODE, false, true>)
+                              : (g.inplace ? k_rv_ftran<MODE, true, false> : k_rv_ftran<MODE, false, false>);
+    const int n = rv_launch(k2, dim3(g.gr, nact), dim3(kBlock), rv_lds(g.lds, g.ck2), g.stream, lps, act, nparts_price, g.ck2);
+    return n + rv_launch((g.ck2 > 0 ? k_rv_update<MODE, true> : k_rv_update<MODE, false>), dim3(g.gr, nact), dim3(kBlock), rv_lds(g.lds, g.ck2), g.stream, lps, act, g.gr, g.ck2);
 }
-void launch_rv_setup(RevLP *lps, const int *act, int nact, int gr, int ld_max, size_t lds, int ck2, int inplace, hipStream_t s) {
-    launch_rv_k23<RR_FORCED>(lps, act, nact, gr, 0, lds, ck2, inplace, s);
-    hipLaunchKernelGGL(k_rv_lists, dim3(nact), dim3(kBlock), 0, s, lps, act);
-    hipLaunchKernelGGL((ck2 > 0 ? k_rv_matvec<true> : k_rv_matvec<false>), dim3(gr, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, ck2);
-    hipLaunchKernelGGL(k_rv_y_partial, dim3((ld_max + kBlock - 1) / kBlock, 64, nact), dim3(kBlock), 0, s, lps, act);
-    hipLaunchKernelGGL(k_rv_y_reduce, dim3((ld_max + kBlock - 1) / kBlock, nact), dim3(kBlock), 0, s, lps, act);
-    hipLaunchKernelGGL(k_rv_check, dim3(nact), dim3(kBlock), 0, s, lps, act);
+int launch_rv_setup(RevLP *lps, const int *act, int nact, const RevGeom &g) {
+    int n = launch_rv_k23<RR_FORCED>(lps, act, nact, 0, g);
+    const int gy = (g.ld_max + kBlock - 1) / kBlock;
+    n += rv_launch(k_rv_lists, dim3(nact), dim3(kBlock), 0, g.stream, lps, act);
+    n += rv_launch((g.ck2 > 0 ? k_rv_matvec<true> : k_rv_matvec<false>), dim3(g.gr, nact), dim3(kBlock), rv_lds(g.lds, g.ck2), g.stream, lps, act, g.ck2);
+    n += rv_launch(k_rv_y_partial, dim3(gy, 64, nact), dim3(kBlock), 0, g.stream, lps, act);
+    n += rv_launch(k_rv_y_reduce, dim3(gy, nact), dim3(kBlock), 0, g.stream, lps, act);
+    return n + rv_launch(k_rv_check, dim3(nact), dim3(kBlock), 0, g.stream, lps, act);
 }
-void launch_rv_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int ck2, int inplace, hipStream_t s) {
-    hipLaunchKernelGGL(k_rv_bland, dim3(nact), dim3(kBlock), 0, s, lps, act);
-    const auto k1 = ck2 > 0 ? (inplace ? k_rv_price<true, true> : k_rv_price<false, true>) : (inplace ? k_rv_price<true, false> : k_rv_price<false, false>);
-    hipLaunchKernelGGL(k1, dim3(gp, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, ck2);
-    launch_rv_k23<RR_LOOP>(lps, act, nact, gr, gp, lds, ck2, inplace, s);
+int launch_rv_pivot(RevLP *lps, const int *act, int nact, const RevGeom &g) {
+    int n = rv_launch(k_rv_bland, dim3(nact), dim3(kBlock), 0, g.stream, lps, act);
+    const auto k1 = g.ck2 > 0 ? (g.inplace ? k_rv_price<true, true> : k_rv_price<false, true>) : (g.inplace ? k_rv_price<true, false> : k_rv_price<false, false>);
+    n += rv_launch(k1, dim3(g.gp, nact), dim3(kBlock), rv_lds(g.lds, g.ck2), g.stream, lps, act, g.ck2);
+    return n + launch_rv_k23<RR_LOOP>(lps, act, nact, g.gp, g);
 }
-void launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_rv_ctrl, dim3(nact), dim3(kBlock), 0, s, lps, act, out);
+int launch_rv_ctrl(RevLP *lps, const int *act, int nact, RevOut *out, const RevGeom &g) {
+    return rv_launch(k_rv_ctrl, dim3(nact), dim3(kBlock), 0, g.stream, lps, act, out);
 }
-void launch_rv_exchange(RevLP *lps, const int *act, int nact, int nn_max, size_t lds, int ck2, int inplace, hipStream_t s) {
-    const auto kx = ck2 > 0 ? (inplace ? k_rv_exch<true, true> : k_rv_exch<false, true>) : (inplace ? k_rv_exch<true, false> : k_rv_exch<false, false>);
-    hipLaunchKernelGGL(kx, dim3(nn_max, nact), dim3(kBlock), rv_lds(lds, ck2), s, lps, act, ck2);
-    hipLaunchKernelGGL(k_rv_exch_pick, dim3(nact), dim3(64), 0, s, lps, act);
+int launch_rv_exchange(RevLP *lps, const int *act, int nact, const RevGeom &g) {
+    const auto kx = g.ck2 > 0 ? (g.inplace ? k_rv_exch<true, true> : k_rv_exch<false, true>) : (g.inplace ? k_rv_exch<true, false> : k_rv_exch<false, false>);
+    const int n = rv_launch(kx, dim3(g.nn_max, nact), dim3(kBlock), rv_lds(g.lds, g.ck2), g.stream, lps, act, g.ck2);
+    return n + rv_launch(k_rv_exch_pick, dim3(nact), dim3(64), 0, g.stream, lps, act);
 }
-void launch_rv_gen_start(RevLP *lps, int count, int m_max, hipStream_t s) {
-    hipLaunchKernelGGL(k_rv_gen_start, dim3(m_max, count), dim3(kBlock), 0, s, lps);
+int launch_rv_gen_start(RevLP *lps, int count, const RevGeom &g) {
+    return rv_launch(k_rv_gen_start, dim3(g.m_max, count), dim3(kBlock), 0, g.stream, lps);
 }
-void launch_rv_gen_art(RevLP *lps, int count, int inplace, hipStream_t s) {
-    hipLaunchKernelGGL(inplace ? k_rv_gen_art<true> : k_rv_gen_art<false>, dim3(count), dim3(kBlock), 0, s, lps);
+int launch_rv_gen_art(RevLP *lps, int count, const RevGeom &g) {
+    return rv_launch(g.inplace ? k_rv_gen_art<true> : k_rv_gen_art<false>, dim3(count), dim3(kBlock), 0, g.stream, lps);
 }
 // (one-pass forms only: a wave with a searched start does not stage in chunks)
-void launch_rv_pivot_g(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, int inplace, hipStream_t s) {
-    hipLaunchKernelGGL((inplace ? k_rv_price<true, false, true> : k_rv_price<false, false, true>), dim3(gp, nact), dim3(kBlock), lds, s, lps, act, 0);
-    hipLaunchKernelGGL((inplace ? k_rv_ftran<RR_LOOP, true, false, true> : k_rv_ftran<RR_LOOP, false, false, true>), dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gp, 0);
-    hipLaunchKernelGGL((k_rv_update<RR_LOOP, false, true>), dim3(gr, nact), dim3(kBlock), lds, s, lps, act, gr, 0);
+int launch_rv_pivot_g(RevLP *lps, const int *act, int nact, const RevGeom &g) {
+    int n = rv_launch((g.inplace ? k_rv_price<true, false, true> : k_rv_price<false, false, true>), dim3(g.gp, nact), dim3(kBlock), g.lds, g.stream, lps, act, 0);
+    n += rv_launch((g.inplace ? k_rv_ftran<RR_LOOP, true, false, true> : k_rv_ftran<RR_LOOP, false, false, true>), dim3(g.gr, nact), dim3(kBlock), g.lds, g.stream, lps, act, g.gp, 0);
+    return n + rv_launch((k_rv_update<RR_LOOP, false, true>), dim3(g.gr, nact), dim3(kBlock), g.lds, g.stream, lps, act, g.gr, 0);
 }
-void launch_rv_warm_binv(RevLP *lps, int count, int m_max, hipStream_t s) {
-    hipLaunchKernelGGL(k_rv_warm_binv, dim3(m_max, count), dim3(kBlock), 0, s, lps);
+int launch_rv_warm_binv(RevLP *lps, int count, const RevGeom &g) {
+    return rv_launch(k_rv_warm_binv, dim3(g.m_max, count), dim3(kBlock), 0, g.stream, lps);
 }
-// (ck2d > 0: the CK = true pricing kernel, its TWO vectors ck2d double2 each, else the one-pass one with lds2 bytes; ck2: K2 / K3 as in
-// launch_rv_pivot)
-void launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, int gp, int gr, size_t lds, size_t lds2, int ck2, int ck2d, int inplace, hipStream_t s) {
-    hipLaunchKernelGGL(k_rv_dual_leave, dim3(nact), dim3(kBlock), 0, s, lps, act);
-    const auto k1 = ck2d > 0 ? (inplace ? k_rv_dual_price<true, true> : k_rv_dual_price<false, true>)
-                             : (inplace ? k_rv_dual_price<true, false> : k_rv_dual_price<false, false>);
-    hipLaunchKernelGGL(k1, dim3(gp, nact), dim3(kBlock), rv_lds(lds2, 2 * ck2d), s, lps, act, ck2d);
-    launch_rv_k23<RR_DUAL>(lps, act, nact, gr, gp, lds, ck2, inplace, s);
+// (ck2d > 0: the CK = true pricing kernel, its TWO vectors ck2d double2 each, else the one-pass one with its two vectors' 2 * lds bytes;
+// ck2: K2 / K3 as in launch_rv_pivot)
+int launch_rv_dual_pivot(RevLP *lps, const int *act, int nact, const RevGeom &g) {
+    int n = rv_launch(k_rv_dual_leave, dim3(nact), dim3(kBlock), 0, g.stream, lps, act);
+    const auto k1 = g.ck2d > 0 ? (g.inplace ? k_rv_dual_price<true, true> : k_rv_dual_price<false, true>)
+                               : (g.inplace ? k_rv_dual_price<true, false> : k_rv_dual_price<false, false>);
+    n += rv_launch(k1, dim3(g.gp, nact), dim3(kBlock), rv_lds(2 * g.lds, 2 * g.ck2d), g.stream, lps, act, g.ck2d);
+    return n + launch_rv_k23<RR_DUAL>(lps, act, nact, g.gp, g);
 }
 
 }  // namespace gomilp

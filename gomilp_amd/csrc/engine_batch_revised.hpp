@@ -49,8 +49,8 @@ class RevBatchEngine {
             const WarmSpec *warm = nullptr);
 
     // pool knob rev_exchange: a relaxation whose Phase I ends with the artificial basic at level zero exchanges it on the device (the
-    // candidate scan of batch_revised.hip: two launches in front of the set-up launches of the supersteps that have such a relaxation,
-    // none elsewhere; Outcome::art_exchanges) and goes on to Phase II; off: it is handed over as BS_HOST.  The |x_art| band
+    // candidate scan of batch_revised.hip: launch_rv_exchange in front of the set-up launches of the supersteps that have such a
+    // relaxation, nowhere else; Outcome::art_exchanges) and goes on to Phase II; off: it is handed over as BS_HOST.  The |x_art| band
     // (1e-13 < |x_art| < 1e-11) is BS_HOST either way: its verdict needs a fresh gonum-order solve.
     void set_exchange(bool on) { exchange_ = on; }
 
@@ -83,6 +83,7 @@ class RevBatchEngine {
 
    private:
     struct Buf;
+    struct Wave;   // one call of run: its arguments, what the steps derive from them, the steps (engine_batch_revised.cpp)
     int device_;
     bool exchange_ = true;
     bool large_rows_ = false;

@@ -381,3 +381,47 @@ def test_warm_call_with_an_extra_root_present():
         for i in range(len(a.status)):
             if a.has_x[i]:
                 assert abs(a.z[i] - b.z[i]) <= 1e-9 * max(1.0, abs(b.z[i])), (gen, i, a.z[i], b.z[i])
+
+
+# ---- 9 ----
+
+def test_launch_count_of_a_cold_wave():
+    """kernel_launches against the schedule's own definition, where it can be derived by hand: one cold wave of 4 one-row children of the
+    66 x 200 root (the first four down branches on its optimum), assembled (rev_inplace = 0) and in place (rev_inplace = 1).
+
+    From the wrapper bodies of batch_revised.hip: the start of a cold wave of slack roots is launch_rv_assemble (k_rv_assemble; none with
+    rev_inplace) + launch_rv_init (k_rv_init) = 2 launches, 1 in place.  A superstep s without a dual loop, a searched start or an
+    exchange is launch_rv_setup (K2 + K3 of the forced pivot, k_rv_lists, k_rv_matvec, k_rv_y_partial, k_rv_y_reduce, k_rv_check = 7),
+    chunk_s times launch_rv_pivot (k_rv_bland, K1, K2, K3 = 4) with chunk_s = 8 for s < 2 and 32 behind, and launch_rv_ctrl (1).  So the
+    schedule launches 2 + sum over s < supersteps of (7 + 4 chunk_s + 1) kernels, and one fewer in place.
+
+    The pool reports the schedule's launches and those of the workers' final solves (worker_step) as one sum and exposes neither alone, so
+    what is asserted is the part that the two runs pin between them: the same supersteps, and exactly one launch more assembled than in
+    place — the assemble term.  (The final solves are the same launches in both runs: the bases are equal bit for bit.)  The closed form
+    and what the pool reports beyond it are printed."""
+    mm, nv, _ = SMALL[66]
+
+    def pool(inplace):
+        return _pool("small-66", (66,), workers=4, exact_degenerate=0, rev_inplace=inplace, large_rows=0)
+
+    try:
+        r0 = pool(0).solve([[]])
+        assert r0.status[0] == lp.OK
+        kids = down_branches(r0.x[0][: nv + mm], synth.integrality_mask(nv, mm))[:4]
+        assert len(kids) == 4 and all(len(c) == 1 for c in kids)
+        runs = []
+        for inplace in (0, 1):
+            r = pool(inplace).solve(kids)
+            s = r.stats
+            _say("4 one-row children of the 66-row root, rev_inplace = %d" % inplace, r)
+            closed = (2 - inplace) + sum(7 + 4 * (8 if t < 2 else 32) + 1 for t in range(s["supersteps"]))
+            print("  art_exchanges %d, warm_started %d; the schedule's closed form: %d launches, reported beyond it: %d" % (
+                s["art_exchanges"], s["warm_started"], closed, s["kernel_launches"] - closed))
+            assert (s["batched_relaxations"], s["host_fallbacks"], s["art_exchanges"], s["warm_started"]) == (4, 0, 0, 0)
+            runs.append(r)
+    finally:
+        pool(0)
+    a, b = runs
+    _same_bits(a, b, [_width(66)] * 4)
+    assert a.stats["supersteps"] == b.stats["supersteps"] > 0
+    assert a.stats["kernel_launches"] - b.stats["kernel_launches"] == 1
